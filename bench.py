@@ -1,9 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the dense-vision hot path on MI355X — prints ONE compact JSON line (< 4 KB, the driver's contract) as the
-LAST line of stdout and writes the full record (kernel tables, micro-benchmarks, traffic detail, samples: everything named
-below) to the sidecar ``bench_detail.json`` (``compact_line`` / ``write_detail``; tests/test_bench_line.py holds the size).
+LAST line of stdout and, with ``--full`` (or ``--detail-out``), writes the full record (kernel tables, micro-benchmarks, traffic
+detail, samples: everything named below) to the sidecar ``bench_detail.json`` (``compact_line`` / ``write_detail``;
+tests/test_bench_line.py holds the size).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline only: it builds the model and the inputs, warms up, times the K steps, writes what the last
+step computed when ``--dump-outputs`` is given, and prints the line.  Everything else listed below runs with ``--full``.
 
 N > 1: one process per GPU.  Started under ``torch.distributed.run`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) every
 process is one rank; started plainly — ``python bench.py --gpus 8`` — it spawns its own N ranks through
@@ -15,7 +19,12 @@ frames per GPU in bf16 — BASELINE.json configs[1].  ``value`` = frames/s of th
 exactly K steps between barrier + synchronize fences, max over ranks.  Frames shard by batch across ranks, no data-path
 collective (weak scaling).  Inputs are resident in HBM before the timed region starts.
 
-Beside it (numbers in the line, the full objects in the sidecar):
+``--dump-outputs DIR`` (after the timed steps, rank 0): what the last timed step handed its caller, as float32 ``DIR/<name>.npy`` —
+``pred_logits`` / ``pred_boxes`` of the forward, the per-query ``scores`` / ``labels`` that ``inference()`` thresholds and the
+``counts`` it kept per frame; every array has a fixed shape.  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared file by file.
+
+With ``--full``, beside it (numbers in the line, the full objects in the sidecar):
   roofline      the dominant hand-written kernel (MSDA forward, encoder call Lq = S = 22223), timed live with HIP events on
                 the launch stream: algorithmic bytes / average launch time vs the 8 TB/s HBM peak.
                 ``ms_per_launch`` (what ``achieved`` uses; agrees with rocprofv3's per-kernel average) = mean of the
@@ -44,6 +53,7 @@ Beside it (numbers in the line, the full objects in the sidecar):
                 (``cpu_kernels``: one MSDA encoder call at B = 8; correlation build + 32 lookups at B = 4).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -52,6 +62,7 @@ import time
 # RCCL / device-tensor sharing between the ranks of one node needs dmabuf IPC on this driver (already exported on the GPU boxes)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -212,7 +223,15 @@ def parse():
     ap.add_argument("--print-detail", action="store_true", help="also print the full record, on stderr, before the contract line")
     ap.add_argument("--selftest", action="store_true",
                     help="CPU/gloo dry run of the launch, sharding, fencing and max-over-ranks logic (no GPU, no kernels)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement: the eager, fp32, trained-like, RAFT, training and panoptic legs, kernel "
+                         "tables and rooflines, micro-benchmarks, PMC passes and CPU baselines (their own options apply only with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def visible_gpu_count():
@@ -854,18 +873,47 @@ def kernel_report(summary):
     return rep
 
 
-def detection_leg(a, rank, world, device, dtype, steps, warmup, eager_steps, full_table, trained_like=False):
+def step_outputs(model, out, preds):
+    """What one detection step hands its caller, as host float32 arrays of a fixed shape: the forward's ``pred_logits`` /
+    ``pred_boxes``, the per-query ``scores`` / ``labels`` that ``inference()`` thresholds (B, Q), and how many detections it kept
+    per frame (B,).  The kept boxes are the rows of ``pred_boxes`` whose score passed, so they are not written again: their number
+    varies with the weights and is zero for the random-init model."""
+    host = lambda t: t.as_subclass(torch.Tensor).detach().float().cpu().numpy()  # noqa: E731
+    logits, boxes, act = out["pred_logits"], out["pred_boxes"], out.get("activation_fn") or model.activation_fn
+    packed = model._packed_detections(logits, boxes, act)
+    if packed is None:   # no pack left by the forward: derive the same (score, label) columns on a copy
+        logits = logits.detach().clone()
+        model._pack_detections(logits, boxes, act)
+        packed = logits._alo_detections[0]
+    res = {k: host(out[k]) for k in ("pred_logits", "pred_boxes")}
+    res["scores"], res["labels"] = host(packed[..., 0]), host(packed[..., 1])
+    res["counts"] = host(torch.tensor([b.shape[0] for b in preds]))
+    return res
+
+
+def dump_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def detection_leg(a, rank, world, device, dtype, steps, warmup, eager_steps, full_table, trained_like=False, instrument=True,
+                  keep_outputs=False):
     """DeformableDETR-R50 inference on one resident batch: ``steps`` timed steps (HIP-graph replay unless --no-graph), then
     ``eager_steps`` timed steps with eager launches whose MSDA-forward launches carry HIP-event pairs (the in-step roofline
-    figure), then — ``full_table`` — two un-timed eager steps with an event pair around every launch of this library."""
+    figure), then — ``full_table`` — two un-timed eager steps with an event pair around every launch of this library.
+    ``instrument=False`` (a plain run): the timed steps alone, no event pair anywhere.  ``keep_outputs``: ``outputs`` holds
+    ``step_outputs`` of the last timed step."""
     model = build_detector(device, dtype, trained_like)
     frames = detection_inputs(a.batch, rank, device, dtype)
     spread = offset_spread_px(model, frames) if trained_like else None
+    last = {}   # the latest step's forward output and detections
 
     def eager_step():
         with torch.no_grad():
-            out = model(frames)
-            return model.inference(out)  # ends with boxes.cpu(): the step is complete when it returns
+            last["out"] = model(frames)
+            last["preds"] = model.inference(last["out"])  # ends with boxes.cpu(): the step is complete when it returns
+            return last["preds"]
 
     graph = not a.no_graph
     det_step = eager_step
@@ -880,7 +928,9 @@ def detection_leg(a, rank, world, device, dtype, steps, warmup, eager_steps, ful
 
         def det_step():
             with torch.no_grad():
-                return model.inference(graphed(frames))
+                last["out"] = graphed(frames)
+                last["preds"] = model.inference(last["out"])
+                return last["preds"]
 
         try:
             graphed(frames)  # capture outside the timed region (as the eager path's first-call caches are)
@@ -893,33 +943,36 @@ def detection_leg(a, rank, world, device, dtype, steps, warmup, eager_steps, ful
     # pair around each of the ~150 launches of this library per step costs the GPU more than a millisecond of dispatch
     # bubbles.  Graph replay: no host-side wrapper runs, so nothing is instrumented inside the timed steps at all; the pairs
     # then come from the eager steps timed right after them.
-    with alo_hip.LaunchTimer(only="msda_fwd") as timer:
+    with alo_hip.LaunchTimer(only="msda_fwd") if instrument else contextlib.nullcontext() as timer:
         seconds = timed_steps(det_step, steps, warmup, world, device)
         rank_seconds = list(LAST_RANK_SECONDS)
+        outputs = step_outputs(model, last["out"], last["preds"]) if keep_outputs else None
         eager_seconds = None
         if graph and eager_steps > 0:
             eager_seconds = timed_steps(eager_step, eager_steps, 1, world, device)
-        elif graph:
+        elif graph and instrument:
             eager_step()
             eager_step()
-    kernels = {}
-    src_timer = timer
-    if full_table:
-        with alo_hip.LaunchTimer() as full_timer:   # the table of every kernel of this library: two extra, un-timed EAGER steps
-            eager_step()
-            eager_step()
-        kernels = kernel_report(full_timer.summary())
-        if not any(k.startswith("msda_fwd") for k in timer.relaunch):
-            src_timer = full_timer
-    kernels.update(kernel_report(timer.summary()))  # includes warm-up launches of the same shapes
-    # the dominant kernel once more, 20 launches back to back on the buffers of its last in-model call: a single-launch
-    # event pair also spans the dispatch gaps around the launch (tens of microseconds), a train does not
-    enc_tag = next((k for k in src_timer.relaunch if k.startswith("msda_fwd") and k.endswith("Lq=22223")), None)
-    enc_b2b_ms = src_timer.replay_ms(enc_tag, 20) if enc_tag else None
-    del model, frames
+    kernels, enc_b2b_ms = {}, None
+    if instrument:
+        src_timer = timer
+        if full_table:
+            with alo_hip.LaunchTimer() as full_timer:   # the table of every kernel of this library: two extra, un-timed EAGER steps
+                eager_step()
+                eager_step()
+            kernels = kernel_report(full_timer.summary())
+            if not any(k.startswith("msda_fwd") for k in timer.relaunch):
+                src_timer = full_timer
+        kernels.update(kernel_report(timer.summary()))  # includes warm-up launches of the same shapes
+        # the dominant kernel once more, 20 launches back to back on the buffers of its last in-model call: a single-launch
+        # event pair also spans the dispatch gaps around the launch (tens of microseconds), a train does not
+        enc_tag = next((k for k in src_timer.relaunch if k.startswith("msda_fwd") and k.endswith("Lq=22223")), None)
+        enc_b2b_ms = src_timer.replay_ms(enc_tag, 20) if enc_tag else None
+    del model, frames, last
     torch.cuda.empty_cache()
     return {"seconds": seconds, "eager_seconds": eager_seconds, "kernels": kernels, "enc_b2b_ms": enc_b2b_ms,
-            "launch": "HIP graph replay" if graph else "eager", "graph": graph, "offset_spread_px": spread, "rank_seconds": rank_seconds}
+            "launch": "HIP graph replay" if graph else "eager", "graph": graph, "offset_spread_px": spread, "rank_seconds": rank_seconds,
+            "outputs": outputs}
 
 
 def selftest(a):
@@ -964,6 +1017,9 @@ def main():
     self_launch(a)   # --gpus N > 1 without a torch.distributed environment: re-executes under torch.distributed.run and exits
     if a.selftest:
         return selftest(a)
+    if not a.full:   # a plain run: set-up, warm-up, the timed headline steps, the outputs and the line, nothing else
+        a.eager_steps = a.fp32_steps = a.trained_steps = a.train_steps = a.panoptic_steps = a.micro_reps = 0
+        a.no_raft = a.no_pmc = a.no_cpu_baseline = True
     rank, world, local = init_dist(a.gpus, share_gpu=a.share_gpu, force=a.force_dist)
     device = torch.device("cuda", local)
     rank_cpus = None
@@ -975,9 +1031,12 @@ def main():
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
 
     # ---- detection: the headline workload ---------------------------------------------------------------------------
-    det = detection_leg(a, rank, world, device, dtype, a.steps, a.warmup, a.eager_steps, full_table=True)
+    det = detection_leg(a, rank, world, device, dtype, a.steps, a.warmup, a.eager_steps, full_table=a.full, instrument=a.full,
+                        keep_outputs=bool(a.dump_outputs) and rank == 0)
     det_seconds, kernels, enc_b2b_ms = det["seconds"], det["kernels"], det["enc_b2b_ms"]
     det_fps = a.batch * world * a.steps / det_seconds
+    if det["outputs"] is not None:
+        dump_outputs(det["outputs"], a.dump_outputs)
     # the same workload in fp32: the reference op is float / double only, and the north-star's <= 1e-3 bar is an fp32 statement
     fp32 = None
     if a.fp32_steps > 0 and dtype != torch.float32:
@@ -1326,8 +1385,11 @@ def main():
 
 
 def emit(line, a):
-    """Sidecar first, then the compact contract line as the LAST thing on stdout."""
-    written = write_detail(line, getattr(a, "detail_out", None))
+    """Sidecar first (a plain run writes none unless --detail-out names it), then the compact contract line as the LAST thing
+    on stdout."""
+    written = None
+    if getattr(a, "full", True) or getattr(a, "detail_out", None):
+        written = write_detail(line, getattr(a, "detail_out", None))
     line["detail_file"] = os.path.relpath(written, ROOT) if written else None
     if getattr(a, "print_detail", False):
         print(json.dumps(line), file=sys.stderr, flush=True)

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/seq
-rocprofv3 --kernel-trace --output-format csv -d /tmp/seq -- python $ROOT/bench.py --no-raft --train-steps 0 --panoptic-steps 0 --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-graph --steps 3 --warmup 2 > /dev/null 2> /tmp/seq.log
+rocprofv3 --kernel-trace --output-format csv -d /tmp/seq -- python $ROOT/bench.py --full --no-raft --train-steps 0 --panoptic-steps 0 --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-graph --steps 3 --warmup 2 > /dev/null 2> /tmp/seq.log
 f=$(find /tmp/seq -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY'
 import csv, re, sys

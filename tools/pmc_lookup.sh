@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/pmc_lookup.txt
 mkdir -p $ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 : > $OUT
-MODEL="python $ROOT/bench.py --steps 1 --warmup 1 --raft-steps 2 --raft-warmup 1 --train-steps 0 --no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --panoptic-steps 0 --trained-steps 0 --no-graph"
+MODEL="python $ROOT/bench.py --full --steps 1 --warmup 1 --raft-steps 2 --raft-warmup 1 --train-steps 0 --no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --panoptic-steps 0 --trained-steps 0 --no-graph"
 ALONE="python $ROOT/tools/kbench.py --which corr_lookup --reps 10"
 $MODEL > /dev/null 2>&1   # MIOpen's find database warm
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do

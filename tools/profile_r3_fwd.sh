@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/r03_stats
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r03_stats -- python $ROOT/bench.py --no-raft --train-steps 0 --panoptic-steps 0 --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-graph --steps 40 > $OUT/detr_bench_under_rocprof.json 2> /tmp/r03_stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r03_stats -- python $ROOT/bench.py --full --no-raft --train-steps 0 --panoptic-steps 0 --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-graph --steps 40 > $OUT/detr_bench_under_rocprof.json 2> /tmp/r03_stats.log
 f=$(find /tmp/r03_stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/r03_detr_kernel_stats.csv
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU" "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_MFMA SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VMEM" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVES"; do

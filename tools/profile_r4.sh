@@ -9,12 +9,12 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args
   rm -rf /tmp/r04_$1
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r04_$1 -- python $ROOT/bench.py $2 > $OUT/$1_bench_under_rocprof.json 2> /tmp/r04_$1.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r04_$1 -- python $ROOT/bench.py --full $2 > $OUT/$1_bench_under_rocprof.json 2> /tmp/r04_$1.err
   f=$(find /tmp/r04_$1 -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/r04_$1_kernel_stats.csv
 }
 # MIOpen's find database warm (RAFT / training convolutions): the first process of a shape benchmarks candidates
-python $ROOT/bench.py --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-pmc > /dev/null 2>&1
+python $ROOT/bench.py --full --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --no-pmc > /dev/null 2>&1
 COMMON="--no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --panoptic-steps 0"
 stats detr "--no-raft --train-steps 0 --no-graph --steps 40 $COMMON"
 stats raft "--steps 1 --warmup 1 --raft-steps 5 --raft-warmup 2 --train-steps 0 $COMMON"
@@ -43,7 +43,7 @@ cd $ROOT
 (tools/micro/hipblaslt_corr 2>&1 | grep -v "amdgpu.ids\|algo ") > $OUT/hipblaslt_corr.txt
 (tools/micro/lds_atomic; tools/micro/atomic_width; tools/micro/atomic_scope) 2>&1 | grep -v amdgpu.ids > $OUT/atomic_micro.txt
 python tools/kbench.py --which $FWD,msda_enc,msda_survey,msda_rand,msda_bwd,msda_bwd_rand,corr_build,corr_lookup --reps 40 2>/dev/null | grep kernel > $OUT/kbench.txt
-python bench.py > $OUT/r04_bench_line.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r04_bench_line.json 2> $OUT/bench.err
 tail -c 600 $OUT/r04_bench_line.json; head -8 $OUT/r04_raft_kernel_stats.csv | cut -c1-150; cat $OUT/hipblaslt_corr.txt
 # the panoptic leg alone (configs[4] per-GPU share) under rocprofv3
 stats panoptic "--steps 2 --warmup 1 --no-raft --train-steps 0 --panoptic-steps 10 --no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0"

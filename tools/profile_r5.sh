@@ -8,12 +8,12 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args
   rm -rf /tmp/r05_$1
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_$1 -- python $ROOT/bench.py $2 > $OUT/$1_bench_under_rocprof.json 2> /tmp/r05_$1.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_$1 -- python $ROOT/bench.py --full $2 > $OUT/$1_bench_under_rocprof.json 2> /tmp/r05_$1.err
   f=$(find /tmp/r05_$1 -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/r05_$1_kernel_stats.csv
 }
 # MIOpen's find database warm (RAFT / training convolutions)
-python $ROOT/bench.py --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --trained-steps 0 --no-pmc > /dev/null 2>&1
+python $ROOT/bench.py --full --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --trained-steps 0 --no-pmc > /dev/null 2>&1
 COMMON="--no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --panoptic-steps 0 --trained-steps 0"
 stats detr "--no-raft --train-steps 0 --no-graph --steps 40 $COMMON"
 stats raft "--steps 1 --warmup 1 --raft-steps 5 --raft-warmup 2 --train-steps 0 $COMMON"
@@ -39,5 +39,5 @@ done
 cd $ROOT
 FWD=msda_fused_hm,msda_fused_hm_plain,msda_fused_hm_survey,msda_fused_hm_trained,msda_fused_hm_uniform
 python tools/kbench.py --which $FWD,msda_enc,msda_survey,msda_trained,msda_rand,msda_bwd,msda_bwd_rand,corr_build,corr_lookup --reps 40 2>/dev/null | grep kernel > $OUT/kbench.txt
-python bench.py > $OUT/r05_bench_line.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r05_bench_line.json 2> $OUT/bench.err
 tail -c 400 $OUT/r05_bench_line.json; echo; head -6 $OUT/r05_detr_kernel_stats.csv | cut -c1-160; cat $OUT/kbench.txt | cut -c1-200

@@ -8,12 +8,12 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args
   rm -rf /tmp/r06_$1
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_$1 -- python $ROOT/bench.py $2 --detail-out /tmp/r06_$1_detail.json > $OUT/$1_bench_under_rocprof.json 2> /tmp/r06_$1.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r06_$1 -- python $ROOT/bench.py --full $2 --detail-out /tmp/r06_$1_detail.json > $OUT/$1_bench_under_rocprof.json 2> /tmp/r06_$1.err
   f=$(find /tmp/r06_$1 -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/r06_$1_kernel_stats.csv
 }
 # MIOpen's find database warm (RAFT / training convolutions)
-python $ROOT/bench.py --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --trained-steps 0 --no-pmc --detail-out /tmp/r06_warm.json > /dev/null 2>&1
+python $ROOT/bench.py --full --steps 2 --warmup 1 --raft-steps 1 --raft-warmup 1 --no-cpu-baseline --train-steps 1 --panoptic-steps 1 --micro-reps 0 --fp32-steps 0 --eager-steps 0 --trained-steps 0 --no-pmc --detail-out /tmp/r06_warm.json > /dev/null 2>&1
 COMMON="--no-pmc --no-cpu-baseline --micro-reps 0 --fp32-steps 0 --eager-steps 0 --panoptic-steps 0 --trained-steps 0"
 stats detr "--no-raft --train-steps 0 --no-graph --steps 40 $COMMON"
 stats raft "--steps 1 --warmup 1 --raft-steps 5 --raft-warmup 2 --train-steps 0 $COMMON"
@@ -43,6 +43,6 @@ ALO_MSDA_BWD=tiled python tools/kbench.py --which msda_bwd_all --reps 40 2>/dev/
 for d in 32 64; do for dt in f32 bf16; do python tools/exp/bwd_wide_check.py --N 4 --D $d --dtype $dt --kinds ring,trained 2>/dev/null | grep kind | sed "s/^/D=$d /"; done; done > $OUT/bwd_wide_check.txt
 python tools/exp/lookup_mall_probe.py 2>/dev/null | grep flush > $OUT/lookup_mall_probe.txt
 python tools/exp/fwd_f32_hm_probe.py 8 2>/dev/null | grep kind > $OUT/fwd_f32_hm_probe.txt
-python bench.py > $OUT/r06_bench_line.json 2> $OUT/bench.err
+python bench.py --full > $OUT/r06_bench_line.json 2> $OUT/bench.err
 cp $ROOT/bench_detail.json $OUT/r06_bench_detail.json
 tail -c 600 $OUT/r06_bench_line.json; echo; head -6 $OUT/r06_train_kernel_stats.csv | cut -c1-160; cat $OUT/kbench.txt | cut -c1-200

@@ -27,7 +27,7 @@ trap 'rm -rf "$TMP"' EXIT
 for n in ${GPUS//,/ }; do
     echo "[scale] --gpus $n" >&2
     # a failing N (fewer devices than asked for, a rank that dies) is recorded, not fatal: the other points still make a curve
-    if python "$ROOT/bench.py" --gpus "$n" "${EXTRA[@]}" > "$TMP/out_$n.txt" 2> "$TMP/err_$n.txt"; then
+    if python "$ROOT/bench.py" --full --gpus "$n" "${EXTRA[@]}" > "$TMP/out_$n.txt" 2> "$TMP/err_$n.txt"; then
         grep '^{' "$TMP/out_$n.txt" | tail -1 > "$TMP/line_$n.json" || true
     else
         echo "[scale] --gpus $n failed: $(tail -2 "$TMP/err_$n.txt" | tr '\n' ' ')" >&2
