@@ -1281,10 +1281,12 @@ msda_bwd_tiled_kernel(const float* __restrict__ value, const int32_t* __restrict
         }
     }
     {
+#pragma clang fp contract(off)
         const float xs[4] = {l0[0], l0[2], l1[0], l1[2]}, ys[4] = {l0[1], l0[3], l1[1], l1[3]};
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const float h_im = ys[p] * (float)Hl - 0.5f, w_im = xs[p] * (float)Wl - 0.5f;
+            // one rounding, as make_tap: the side of a pixel edge a sample lands on must not depend on the compiler's fusing
+            const float h_im = __builtin_fmaf(ys[p], (float)Hl, -0.5f), w_im = __builtin_fmaf(xs[p], (float)Wl, -0.5f);
             const bool valid = live && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hl) && (w_im < (float)Wl);
             const float hs = valid ? h_im : 0.f, ws = valid ? w_im : 0.f;
             const float hf = floorf(hs), wf = floorf(ws);

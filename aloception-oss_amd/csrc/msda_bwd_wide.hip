@@ -169,8 +169,10 @@ struct Tap {
     unsigned flags;   // bit k: corner k inside the map; bit 4: the sample counts (cuh:285-291, :38-78)
 };
 __device__ __forceinline__ Tap make_tap_w(float x, float y, int Hl, int Wl, bool live) {
+#pragma clang fp contract(off)
     Tap t;
-    const float h_im = y * (float)Hl - 0.5f, w_im = x * (float)Wl - 0.5f;
+    // one rounding, as make_tap (msda.hip): the side of a pixel edge a sample lands on must not depend on the compiler's fusing
+    const float h_im = __builtin_fmaf(y, (float)Hl, -0.5f), w_im = __builtin_fmaf(x, (float)Wl, -0.5f);
     const bool valid = live && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hl) && (w_im < (float)Wl);
     const float hs = valid ? h_im : 0.f, ws = valid ? w_im : 0.f;
     const float hf = floorf(hs), wf = floorf(ws);

@@ -128,3 +128,104 @@ def g17_inputs(g):
         if hashlib.sha256(t.numpy().tobytes()).digest() != g[key].tobytes():
             return None
     return value, loc, attn
+
+
+# ---- grad_sampling_loc on pixel edges ------------------------------------------------------------------------------------------
+# grad_sampling_loc is the derivative of a piecewise-bilinear function: a component JUMPS where its image coordinate
+# t = loc * size - 0.5 crosses an integer.  The reference maps a float32 location with one fused multiply-add and takes floor() of
+# the float32 result r; the float64 oracle takes floor(t) of the exact value.  They disagree only where r is an integer k that t
+# lies just below: the device then works in the cell [k, k + 1] (or drops the sample, at k = -1 or k = size), the oracle in the cell
+# below.  Inside one cell d/dx is constant along x, so the device's component is the oracle's with that coordinate moved to k + 0.5.
+def _edge_sizes(shapes, L):
+    shapes = np.asarray(shapes, np.int64)
+    return np.stack([shapes[:, 1], shapes[:, 0]], -1).astype(np.float64).reshape(1, 1, 1, L, 1, 2)   # (x, y) -> (W, H)
+
+
+def _oracle_grad_loc(value, shapes, start, loc64, attn, grad_out):
+    import oracle as O
+
+    return O.msda_backward(value, shapes, start, loc64, attn, grad_out)[1]
+
+
+def grad_loc_reference(value, shapes, start, loc, attn, grad_out, queries=None):
+    """The grad_sampling_loc a float32 device computes for float32 ``loc`` (N, Lq, M, L, P, 2), every sample included, in float64.
+
+    ``queries`` (index / slice / mask on the query axis): only those queries' rows are computed and returned — a sample's
+    grad_loc depends on its own query's inputs alone, so the oracle then runs on Lq' < Lq queries.  Three oracle runs at most."""
+    loc = np.asarray(loc)
+    assert loc.dtype == np.float32, "grad_loc_reference models the float32 mapping; use grad_loc_one_sided for float64 launches"
+    if queries is not None:
+        loc, attn, grad_out = loc[:, queries], np.asarray(attn)[:, queries], np.asarray(grad_out)[:, queries]
+    value, attn, grad_out = (np.asarray(a, np.float64) for a in (value, attn, grad_out))
+    loc64 = loc.astype(np.float64)
+    size = _edge_sizes(shapes, loc.shape[3])
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = loc64 * size - 0.5                   # exact: 24-bit mantissa x an integer below 2^15
+        r = t.astype(np.float32).astype(np.float64)   # the correctly rounded fma
+        edge = np.isfinite(r) & (r == np.floor(r))
+        inner = edge & (r >= 0) & (r <= size - 1)
+        dropped = (edge & ((r == -1) | (r == size))).any(-1)
+    out = _oracle_grad_loc(value, shapes, start, loc64, attn, grad_out)
+    for axis in (0, 1):
+        sel = inner[..., axis]
+        if sel.any():
+            moved = loc64.copy()
+            moved[..., axis] = np.where(sel, (r[..., axis] + 1.0) / size[..., axis], loc64[..., axis])   # t -> k + 0.5
+            out[..., axis] = np.where(sel, _oracle_grad_loc(value, shapes, start, moved, attn, grad_out)[..., axis], out[..., axis])
+    out[dropped] = 0.0
+    return out
+
+
+def grad_loc_one_sided(value, shapes, start, loc, attn, grad_out, eps=1e-9):
+    """For float64 launches (whose fma cannot be emulated portably): a (K, N, Lq, M, L, P, 2) float64 stack of candidates such that
+    each component of the device's grad_sampling_loc must equal one of them.  Away from a pixel edge every candidate is the oracle.
+    A component within ``eps`` px of an integer k has the two one-sided derivatives (the oracle with that coordinate moved to
+    k -+ 0.5, which is 0 where that side drops the sample); a coordinate on the border of validity (k = -1 or k = size) adds 0 for
+    the OTHER component (the sample may be dropped as a whole)."""
+    value, attn, grad_out, loc = (np.asarray(a, np.float64) for a in (value, attn, grad_out, loc))
+    size = _edge_sizes(shapes, loc.shape[3])
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = loc * size - 0.5
+        k = np.round(t)
+        near = np.isfinite(t) & (np.abs(t - k) <= eps)
+        border = (near & ((k == -1) | (k == size)))[..., ::-1]   # the other component's coordinate sits on the border
+    plain = _oracle_grad_loc(value, shapes, start, loc, attn, grad_out)
+    lo, hi = plain.copy(), plain.copy()
+    for axis in (0, 1):
+        sel = near[..., axis]
+        if sel.any():
+            for side, dst in ((-0.5, lo), (0.5, hi)):
+                moved = loc.copy()
+                moved[..., axis] = np.where(sel, (k[..., axis] + side + 0.5) / size[..., axis], loc[..., axis])
+                dst[..., axis] = np.where(sel, _oracle_grad_loc(value, shapes, start, moved, attn, grad_out)[..., axis], dst[..., axis])
+    return np.stack([lo, hi, np.where(border, 0.0, lo), np.where(border, 0.0, hi)])
+
+
+def assert_one_of(got, candidates, atol):
+    """Every component of ``got`` within ``atol`` of one of ``candidates`` (from grad_loc_one_sided)."""
+    ok = (np.abs(np.asarray(got)[None] - candidates) <= atol).any(0)
+    assert ok.all(), f"{(~ok).sum()} grad_loc components match no side of their edge; first at {np.argwhere(~ok)[:3].tolist()}"
+
+
+DYADIC_SHAPES = [(32, 64), (16, 32), (8, 16), (4, 8)]   # power-of-two sizes: loc = (t + 0.5) / size is exact in float32 and float64
+
+
+def exact_edge_case(seed, N, M, D, Lq, shapes=DYADIC_SHAPES, P=4, dtype=np.float32):
+    """An msda case whose sampling points sit EXACTLY on pixel edges (power-of-two sizes, image coordinates on a 2^-10 grid): per
+    sample x only, y only or both on an integer k, or neither; k = 0, size - 1 (high corner off the map), -1 and size (dropped), an
+    interior k, and -1 + 2^-10 (the lowest coordinate that counts)."""
+    rng = np.random.default_rng(seed)
+    c = msda_case(seed, N, M, D, Lq, shapes, P, dtype)
+    L = len(shapes)
+    size = _edge_sizes(shapes, L)[0, 0, 0, :, 0, :]            # (L, 2)
+    t = np.round(rng.uniform(-1.4, 1.0, (N, Lq, M, L, P, 2)) * (size + 1.0) * 1024) / 1024   # free: a 2^-10 grid over the map
+    kind = rng.integers(0, 4, (N, Lq, M, L, P))                 # 0 free, 1 x on an edge, 2 y on an edge, 3 both
+    for axis, on in ((0, (kind == 1) | (kind == 3)), (1, (kind == 2) | (kind == 3))):
+        sz = np.broadcast_to(size[None, None, None, :, None, axis], on.shape)
+        pick = rng.integers(0, 6, on.shape)
+        k = np.select([pick == 0, pick == 1, pick == 2, pick == 3, pick == 4],
+                      [0.0, sz - 1, -1.0, sz, -1.0 + 2.0 ** -10], np.floor(rng.uniform(1, sz - 1)))
+        t[..., axis] = np.where(on, k, t[..., axis])
+    c["loc"] = ((t + 0.5) / size[None, None, None, :, None, :]).astype(dtype)
+    assert np.array_equal(c["loc"].astype(np.float64) * size[None, None, None, :, None, :] - 0.5, t)   # exact in dtype
+    return c

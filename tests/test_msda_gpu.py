@@ -5,7 +5,7 @@ import torch
 
 import alo_hip
 import oracle as O
-from helpers import DETR_SHAPES, level_start, msda_case
+from helpers import DETR_SHAPES, grad_loc_reference, level_start, msda_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -21,7 +21,27 @@ def hip_forward(c, dtype):
                                 dev(c["loc"], dtype), dev(c["attn"], dtype), 64)
 
 
-def hip_backward(c, dtype):
+PER_CORNER, TILED, WIDE = 0, 1, 2   # alo_msda_backward_path: msda_bwd_kernel, msda_bwd_tiled_kernel, msda_bwd_wide_kernel
+
+
+def backward_path(c, dtype):
+    """The kernel alo_hip.msda_backward takes for case ``c``: the wrapper hands the dispatcher a host copy of the shapes exactly for
+    the launches ``_tiled_backward_eligible`` admits, and ``alo_msda_backward_path`` answers the dispatch for that hint (and for the
+    ALO_MSDA_BWD of the moment)."""
+    import ctypes
+
+    N, S, M, D = c["value"].shape
+    _, Lq, _, L, P, _ = c["loc"].shape
+    ldt = alo_hip.ALO_F64 if dtype == torch.float64 else alo_hip.ALO_F32
+    hint = None
+    if alo_hip._tiled_backward_eligible(torch.empty(0, dtype=dtype), (N, S, M, D, L, Lq, P), ldt):
+        hint = (ctypes.c_int32 * (2 * L))(*[int(v) for v in np.asarray(c["shapes"]).reshape(-1)])
+    return alo_hip.lib().alo_msda_backward_path(N, S, M, D, L, Lq, P, alo_hip._DTYPE_CODE[dtype], ldt, hint)
+
+
+def hip_backward(c, dtype, path):
+    """alo_hip.msda_backward on case ``c``, after asserting that the launch takes kernel ``path``."""
+    assert backward_path(c, dtype) == path, f"this launch takes backward path {backward_path(c, dtype)}, not {path}"
     return alo_hip.msda_backward(dev(c["value"], dtype), dev(c["shapes"]), dev(c["level_start"]),
                                  dev(c["loc"], dtype), dev(c["attn"], dtype), dev(c["grad_out"], dtype), 64)
 
@@ -49,7 +69,7 @@ def test_g2_gradcheck_set_fp64(golden, D):
     g = golden(f"g2_msda_grad_D{D}.npz")
     c = {k: g[k] for k in ("value", "shapes", "level_start", "loc", "attn", "grad_out")}
     np.testing.assert_allclose(hip_forward(c, torch.float64).cpu().numpy(), g["out"], rtol=1e-12, atol=1e-15)
-    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float64))
+    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float64, PER_CORNER))
     np.testing.assert_allclose(gv, g["grad_value"], rtol=1e-10, atol=1e-13)
     np.testing.assert_allclose(gl, g["grad_loc"], rtol=1e-10, atol=1e-13)
     np.testing.assert_allclose(ga, g["grad_attn"], rtol=1e-10, atol=1e-13)
@@ -60,7 +80,7 @@ def test_g3_borders_fwd_bwd(golden, dtype, atol):
     g = golden("g3_msda_medium.npz")
     c = {k: g[k] for k in ("value", "shapes", "level_start", "loc", "attn", "grad_out")}
     np.testing.assert_allclose(hip_forward(c, dtype).double().cpu().numpy(), g["out"], rtol=0, atol=atol)
-    gv, gl, ga = (x.double().cpu().numpy() for x in hip_backward(c, dtype))
+    gv, gl, ga = (x.double().cpu().numpy() for x in hip_backward(c, dtype, TILED if dtype == torch.float32 else PER_CORNER))
     np.testing.assert_allclose(gv, g["grad_value"], rtol=1e-5, atol=max(atol, 2e-6))
     np.testing.assert_allclose(gl, g["grad_loc"], rtol=1e-5, atol=2e-4)  # |grad_loc| reaches 160 here
     np.testing.assert_allclose(ga, g["grad_attn"], rtol=1e-5, atol=max(atol, 1e-5))
@@ -99,27 +119,27 @@ def test_g17_the_reference_trt_plugin_test_case_at_full_size(golden):
 
 
 # ---- oracle on seeded inputs: every kernel variant ---------------------------------------------------------------
-CASES = [  # (N, M, D, Lq, shapes, P)          which plan it exercises (fp32)
-    (2, 8, 32, 77, [(16, 21), (8, 11), (4, 6), (2, 3)], 4),  # vec4 / group 8 / unrolled LP=16  (the DETR shape)
-    (1, 8, 32, 300, [(20, 27), (10, 14), (5, 7), (3, 4)], 4),  # decoder-like query count
-    (2, 4, 16, 33, [(9, 7), (5, 4)], 8),  # vec4 / group 4 / unrolled LP=16
-    (1, 2, 64, 19, [(6, 5), (3, 3), (2, 2)], 2),  # vec4 / group 16 / runtime LP
-    (1, 1, 256, 9, [(5, 5)], 3),  # vec4 / group 64
-    (1, 2, 512, 5, [(4, 6)], 2),  # vec4 / group 64, two channel chunks
-    (1, 3, 30, 21, [(6, 4), (3, 2)], 2),  # scalar path (D % 4 != 0), group 64
-    (2, 2, 71, 11, [(6, 4), (3, 2)], 2),  # scalar path, two chunks
-    (1, 2, 2, 2, [(6, 4), (3, 2)], 2),  # scalar path, group 8 (the reference test's D)
-    (1, 2, 8, 13, [(7, 3)], 1),  # vec4 / group 4, L*P = 1
-    (2, 8, 32, 454, [(16, 21), (8, 11), (4, 6), (2, 3)], 4),  # Lq == S: the tiled backward groups queries as 8x8 blocks
-    (1, 4, 32, 130, [(9, 13), (5, 7), (3, 4), (2, 2)], 4),  # tiled backward, 16-query runs with a ragged tail, 4 heads
-    (1, 6, 32, 168, [(9, 13), (5, 7), (3, 4), (2, 2)], 4),  # tiled backward, Lq == S, a head count that is not a power of two
+CASES = [  # (N, M, D, Lq, shapes, P, fp32 backward)   which plan it exercises (fp32)
+    (2, 8, 32, 77, [(16, 21), (8, 11), (4, 6), (2, 3)], 4, TILED),  # vec4 / group 8 / unrolled LP=16  (the DETR shape)
+    (1, 8, 32, 300, [(20, 27), (10, 14), (5, 7), (3, 4)], 4, TILED),  # decoder-like query count
+    (2, 4, 16, 33, [(9, 7), (5, 4)], 8, PER_CORNER),  # vec4 / group 4 / unrolled LP=16
+    (1, 2, 64, 19, [(6, 5), (3, 3), (2, 2)], 2, PER_CORNER),  # vec4 / group 16 / runtime LP
+    (1, 1, 256, 9, [(5, 5)], 3, PER_CORNER),  # vec4 / group 64
+    (1, 2, 512, 5, [(4, 6)], 2, PER_CORNER),  # vec4 / group 64, two channel chunks
+    (1, 3, 30, 21, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path (D % 4 != 0), group 64
+    (2, 2, 71, 11, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path, two chunks
+    (1, 2, 2, 2, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path, group 8 (the reference test's D)
+    (1, 2, 8, 13, [(7, 3)], 1, PER_CORNER),  # vec4 / group 4, L*P = 1
+    (2, 8, 32, 454, [(16, 21), (8, 11), (4, 6), (2, 3)], 4, WIDE),  # Lq == S: the wide backward's 16x16 query blocks
+    (1, 4, 32, 130, [(9, 13), (5, 7), (3, 4), (2, 2)], 4, TILED),  # tiled backward, 16-query runs with a ragged tail, 4 heads
+    (1, 6, 32, 168, [(9, 13), (5, 7), (3, 4), (2, 2)], 4, WIDE),  # wide backward, Lq == S, a head count that is not a power of two
 ]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"N{c[0]}M{c[1]}D{c[2]}Lq{c[3]}L{len(c[4])}P{c[5]}")
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_forward_backward_vs_oracle(case, dtype):
-    N, M, D, Lq, shapes, P = case
+    N, M, D, Lq, shapes, P, path32 = case
     npdt = np.float32 if dtype == torch.float32 else np.float64
     c = msda_case(1234 + D + Lq, N, M, D, Lq, shapes, P, npdt, loc_range=(-0.3, 1.3))
     ref = O.msda_forward(c["value"].astype(np.float64), c["shapes"], c["level_start"], c["loc"].astype(np.float64),
@@ -128,7 +148,7 @@ def test_forward_backward_vs_oracle(case, dtype):
                                     c["loc"].astype(np.float64), c["attn"].astype(np.float64),
                                     c["grad_out"].astype(np.float64))
     out = hip_forward(c, dtype).double().cpu().numpy()
-    gv, gl, ga = (x.double().cpu().numpy() for x in hip_backward(c, dtype))
+    gv, gl, ga = (x.double().cpu().numpy() for x in hip_backward(c, dtype, path32 if dtype == torch.float32 else PER_CORNER))
     if dtype == torch.float64:
         tol = dict(rtol=1e-11, atol=1e-11)
         np.testing.assert_allclose(out, ref, **tol)
@@ -155,6 +175,7 @@ def test_bf16_storage_matches_oracle_on_bf16_rounded_inputs():
     assert np.all(err <= np.abs(ref) * 2.0 ** -8 + 1e-6)  # half an ulp of bf16 (8 significant bits) + fp32 noise
     # gradients of the bf16 path accumulate in fp32
     go = dev(c["grad_out"]).bfloat16()
+    assert backward_path(c, torch.bfloat16) == PER_CORNER
     gv, gl, ga = alo_hip.msda_backward(vb, dev(c["shapes"]), dev(c["level_start"]), dev(c["loc"]), dev(c["attn"]), go, 64)
     rgv, rgl, rga = O.msda_backward(vb.float().cpu().numpy().astype(np.float64), c["shapes"], c["level_start"],
                                     c["loc"].astype(np.float64), c["attn"].astype(np.float64),
@@ -492,13 +513,12 @@ def test_bench_kernel_full_size_on_the_wider_sampling_distributions(kind):
 
 
 # ---- backward at the config-4 encoder size -------------------------------------------------------------------------------
-def _away_from_pixel_edges(loc, shapes_l, eps=1e-3):
-    """grad_sampling_loc is the derivative of a piecewise-bilinear function: it JUMPS where a coordinate crosses an integer.
-    A sample within fp32 rounding of such an edge may legitimately take either side (fp32 vs fp64 evaluation of loc * size - 0.5,
-    fused or unfused): mask those samples out of the grad_loc comparison.  (N, Lq, M, L, P, 1) bool."""
-    size = np.array([[w, h] for h, w in shapes_l], np.float64)[None, None, None, :, None, :]
-    im = loc.astype(np.float64) * size - 0.5
-    return (np.abs(im - np.round(im)) > eps).all(-1, keepdims=True)
+def _grad_loc_error(gl, c, queries=None):
+    """max |grad_sampling_loc - reference| over EVERY sample (pixel edges included: helpers.grad_loc_reference) of ``queries``, and
+    the reference's max |.|."""
+    ref = grad_loc_reference(c["value"], c["shapes"], c["level_start"], c["loc"], c["attn"], c["grad_out"], queries)
+    got = gl if queries is None else gl[:, queries]
+    return np.abs(got - ref).max(), np.abs(ref).max()
 
 
 def _encoder_like_loc(N, shapes_l, rng, spread_px=4.0):
@@ -515,11 +535,19 @@ def _encoder_like_loc(N, shapes_l, rng, spread_px=4.0):
     return (ref[None, :, None, None, None, :] + off).astype(np.float32)
 
 
-@pytest.mark.parametrize("kind,N", [("encoder", 1), ("uniform", 1), ("encoder", 4), ("trained", 4)])
-def test_full_size_backward_vs_oracle(kind, N):
-    """alo_msda_backward at S = Lq = 22223 (fp32) against the C oracle: encoder-like locations (the tiled path) and uniformly
-    random ones (no locality at all: the per-corner path) at N = 1; at N = 4 — BASELINE configs[3]'s per-GPU batch, the launch
-    bench.py's training leg times — encoder-like locations and the trained-like offsets of tools/kbench.py."""
+@pytest.mark.parametrize("kind,N,path", [pytest.param("encoder", 1, WIDE, id="encoder-1"), pytest.param("uniform", 1, WIDE, id="uniform-1"),
+                                         pytest.param("encoder", 4, WIDE, id="encoder-4"), pytest.param("trained", 4, WIDE, id="trained-4"),
+                                         pytest.param("encoder", 4, TILED, id="encoder-4-tiled"),
+                                         pytest.param("trained", 4, TILED, id="trained-4-tiled")])
+def test_full_size_backward_vs_oracle(kind, N, path, monkeypatch):
+    """alo_msda_backward at S = Lq = 22223 (fp32) against the C oracle.  The wrapper hands these launches a host copy of the shapes,
+    so they take msda_bwd_wide_kernel: encoder-like locations and uniformly random ones (no locality at all: its per-corner route) at
+    N = 1; at N = 4 — BASELINE configs[3]'s per-GPU batch, the launch bench.py's training leg times — encoder-like locations and the
+    trained-like offsets of tools/kbench.py.  The N = 4 cases again under ALO_MSDA_BWD=tiled: msda_bwd_tiled_kernel's encoder route
+    (4x4 query tiles of each level).  grad_sampling_loc of every sample of every 5th query and of the last ones against the
+    edge-aware reference."""
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
     rng = np.random.default_rng(21)
     c = _full_size_case(N, 22223, 13)
     if kind == "encoder":
@@ -531,20 +559,33 @@ def test_full_size_backward_vs_oracle(kind, N):
 
         c["loc"] = kbench.msda_inputs(N, 22223, "trained", torch.float32, seed=3)[3].cpu().numpy()
     c["grad_out"] = rng.standard_normal((N, 22223, 256)).astype(np.float32)
-    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32))
+    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32, path))
     rgv, rgl, rga = O.msda_backward(c["value"].astype(np.float64), c["shapes"], c["level_start"], c["loc"].astype(np.float64),
                                     c["attn"].astype(np.float64), c["grad_out"].astype(np.float64))
     assert np.abs(gv - rgv).max() <= 2e-4 * max(1.0, np.abs(rgv).max())   # sums of up to hundreds of fp32 terms per pixel
     assert np.abs(ga - rga).max() <= 1e-4 * max(1.0, np.abs(rga).max())   # 32-term fp32 dot products of O(1) values
-    ok = _away_from_pixel_edges(c["loc"], DETR_SHAPES)
-    assert ok.mean() > 0.99 and np.abs((gl - rgl) * ok).max() <= 1e-4 * max(1.0, np.abs(rgl).max())
+    for qsel in (slice(0, None, 5), slice(22223 - 64, None)):
+        err, scale = _grad_loc_error(gl, c, qsel)
+        assert err <= 1e-4 * max(1.0, scale)
 
 
 @pytest.mark.parametrize("spread", [1.5, 6.0, 40.0])
-def test_tiled_backward_on_encoder_like_locations(spread):
+def test_tiled_backward_on_encoder_like_locations(spread, monkeypatch):
+    _encoder_like_locations_vs_oracle(spread, TILED, monkeypatch)
+
+
+@pytest.mark.parametrize("spread", [1.5, 6.0, 40.0])
+def test_wide_backward_on_encoder_like_locations(spread, monkeypatch):
+    _encoder_like_locations_vs_oracle(spread, WIDE, monkeypatch)
+
+
+def _encoder_like_locations_vs_oracle(spread, path, monkeypatch):
     """The window-dense route of the tiled fp32 backward (Lq == S, taps within `spread` pixels of the query's own position on
     every level: windows resident in LDS for small spreads, per-corner route for the levels whose window outgrows it), incl.
-    taps off the border and queries whose whole window is outside, against the float64 oracle."""
+    taps off the border and queries whose whole window is outside, against the float64 oracle.  The same launch without
+    ALO_MSDA_BWD=tiled takes the wide kernel."""
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
     shapes_l = [(21, 30), (11, 15), (6, 8), (3, 4)]
     rng = np.random.default_rng(int(spread * 10))
     N, M = 2, 8
@@ -557,13 +598,12 @@ def test_tiled_backward_on_encoder_like_locations(spread):
     go = rng.standard_normal((N, S, M * 32)).astype(np.float32)
     shapes = np.asarray(shapes_l, np.int32)
     c = dict(value=value, shapes=shapes, level_start=level_start(shapes), loc=loc, attn=attn, grad_out=go)
-    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32))
+    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32, path))
     rgv, rgl, rga = O.msda_backward(value.astype(np.float64), shapes, c["level_start"], loc.astype(np.float64),
                                     attn.astype(np.float64), go.astype(np.float64))
     assert np.abs(gv - rgv).max() <= 1e-4 * max(1.0, np.abs(rgv).max())
     assert np.abs(ga - rga).max() <= 1e-4 * max(1.0, np.abs(rga).max())
-    ok = _away_from_pixel_edges(loc, shapes_l)
-    assert ok.mean() > 0.98 and np.abs((gl - rgl) * ok).max() <= 1e-4 * max(1.0, np.abs(rgl).max())
+    assert _grad_loc_error(gl, c)[0] <= 1e-4 * max(1.0, np.abs(rgl).max())
 
 
 def _touched_pixels(loc, shapes_l):
@@ -586,11 +626,21 @@ def _touched_pixels(loc, shapes_l):
     return hit
 
 
-def test_tiled_backward_with_nan_outside_the_sampled_footprint():
+def test_tiled_backward_with_nan_outside_the_sampled_footprint(monkeypatch):
+    _nan_outside_the_footprint(TILED, monkeypatch)
+
+
+def test_wide_backward_with_nan_outside_the_sampled_footprint(monkeypatch):
+    _nan_outside_the_footprint(WIDE, monkeypatch)
+
+
+def _nan_outside_the_footprint(path, monkeypatch):
     """The window-dense backward reads every value row of a tile's bounding box, touched or not (they go straight into the matrix
     operand); a row no sample touches must still not reach any gradient — the reference's guarded loads never see it.  NaN in
     every untouched pixel (inside the windows too): grad_sampling_loc / grad_attn_weight bit-equal to the clean run, grad_value
-    equal up to the order of the atomic sums and exactly zero on the untouched pixels."""
+    equal up to the order of the atomic sums and exactly zero on the untouched pixels.  On the tiled kernel and on the wide one."""
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
     shapes_l = [(21, 30), (11, 15), (6, 8), (3, 4)]
     rng = np.random.default_rng(9)
     N, M = 2, 8
@@ -608,12 +658,12 @@ def test_tiled_backward_with_nan_outside_the_sampled_footprint():
     go = rng.standard_normal((N, S, M * 32)).astype(np.float32)
     shapes = np.asarray(shapes_l, np.int32)
     c = dict(value=value, shapes=shapes, level_start=level_start(shapes), loc=loc, attn=attn, grad_out=go)
-    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32))
+    gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32, path))
     hit = _touched_pixels(loc, shapes_l)
     assert 0.05 < hit.mean() < 0.9
     poisoned = value.copy()
     poisoned[~hit] = np.nan
-    pv, pl, pa = (x.cpu().numpy() for x in hip_backward(dict(c, value=poisoned), torch.float32))
+    pv, pl, pa = (x.cpu().numpy() for x in hip_backward(dict(c, value=poisoned), torch.float32, path))
     assert np.isfinite(pv).all() and np.isfinite(pl).all() and np.isfinite(pa).all()
     assert np.array_equal(pl, gl) and np.array_equal(pa, ga)
     assert np.abs(pv - gv).max() <= 1e-5 * max(1.0, np.abs(gv).max()) and np.all(pv[~hit] == 0)
@@ -628,6 +678,7 @@ def test_backward_is_linear_in_grad_out_at_batch4():
     v, loc, attn = dev(c["value"]), dev(c["loc"]), dev(c["attn"])
     g1 = torch.randn(4, 22223, 256, device=DEV)
     g2 = torch.randn(4, 22223, 256, device=DEV)
+    assert backward_path(c, torch.float32) == WIDE
     a = alo_hip.msda_backward(v, sh, st, loc, attn, g1, 64)
     b = alo_hip.msda_backward(v, sh, st, loc, attn, g2, 64)
     ab = alo_hip.msda_backward(v, sh, st, loc, attn, 2 * g1 + g2, 64)
@@ -635,11 +686,21 @@ def test_backward_is_linear_in_grad_out_at_batch4():
         assert (z - (2 * x + y)).abs().max().item() <= 1e-3 * max(1.0, z.abs().max().item())
 
 
-def test_tiled_backward_with_two_pyramids_of_the_same_total_size():
+def test_tiled_backward_with_two_pyramids_of_the_same_total_size(monkeypatch):
+    _two_pyramids_of_the_same_total_size(TILED, monkeypatch)
+
+
+def test_wide_backward_with_two_pyramids_of_the_same_total_size(monkeypatch):
+    _two_pyramids_of_the_same_total_size(WIDE, monkeypatch)
+
+
+def _two_pyramids_of_the_same_total_size(path, monkeypatch):
     """Two pyramids with the same S but different level shapes, their `spatial_shapes` tensors built fresh per call the way the
     reference transformer builds them (freed and re-allocated, possibly at the same address): each backward must tile the
     queries by ITS pyramid.  (Round-2 advisor finding: a host cache keyed on the storage pointer handed the second call the first
     call's shapes; the kernel now derives the tiling from the device copy and the host copy rides on the tensor object.)"""
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
     rng = np.random.default_rng(5)
     N, M = 1, 8
     for shapes_l in ([(20, 30), (10, 15), (5, 8), (3, 4)], [(30, 20), (15, 10), (8, 5), (4, 3)], [(20, 30), (10, 15), (5, 8), (3, 4)]):
@@ -652,21 +713,31 @@ def test_tiled_backward_with_two_pyramids_of_the_same_total_size():
         go = rng.standard_normal((N, S, M * 32)).astype(np.float32)
         shapes = np.asarray(shapes_l, np.int32)
         c = dict(value=value, shapes=shapes, level_start=level_start(shapes), loc=loc, attn=attn, grad_out=go)
-        gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32))   # fresh device tensors, dropped on return
+        gv, gl, ga = (x.cpu().numpy() for x in hip_backward(c, torch.float32, path))   # fresh device tensors, dropped on return
         rgv, rgl, rga = O.msda_backward(value.astype(np.float64), shapes, c["level_start"], loc.astype(np.float64),
                                         attn.astype(np.float64), go.astype(np.float64))
         assert np.isfinite(gl).all() and np.isfinite(ga).all()
         assert np.abs(gv - rgv).max() <= 1e-4 * max(1.0, np.abs(rgv).max())
         assert np.abs(ga - rga).max() <= 1e-4 * max(1.0, np.abs(rga).max())
-        ok = _away_from_pixel_edges(loc, shapes_l)
-        assert np.abs((gl - rgl) * ok).max() <= 1e-4 * max(1.0, np.abs(rgl).max())
+        assert _grad_loc_error(gl, c)[0] <= 1e-4 * max(1.0, np.abs(rgl).max())
 
 
-def test_tiled_backward_survives_a_host_hint_that_disagrees_with_the_device_shapes():
+def test_tiled_backward_survives_a_host_hint_that_disagrees_with_the_device_shapes(monkeypatch):
+    _hint_that_disagrees(TILED, monkeypatch)
+
+
+def test_wide_backward_survives_a_host_hint_that_disagrees_with_the_device_shapes(monkeypatch):
+    _hint_that_disagrees(WIDE, monkeypatch)
+
+
+def _hint_that_disagrees(path, monkeypatch):
     """The C ABI's host copy of the shapes only sizes the grid: handing alo_msda_backward_hinted the shapes of ANOTHER pyramid
     with the same S and the same tile count must not change a bit of which queries are served (transposed levels: 25 x 38 tiles
-    either way)."""
+    either way).  On the tiled kernel and on the wide one."""
     import ctypes
+
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
 
     rng = np.random.default_rng(6)
     shapes_l = [(20, 28), (10, 14), (5, 8), (3, 4)]
@@ -683,6 +754,7 @@ def test_tiled_backward_survives_a_host_hint_that_disagrees_with_the_device_shap
     for hint_shapes in (shapes_l, wrong):
         gv, gl, ga = torch.empty_like(value), torch.full_like(tl, float("nan")), torch.full_like(attn, float("nan"))
         hint = (ctypes.c_int32 * 8)(*[int(v) for hw in hint_shapes for v in hw])
+        assert alo_hip.lib().alo_msda_backward_path(1, S, 8, 32, 4, S, 4, alo_hip.ALO_F32, alo_hip.ALO_F32, hint) == path
         rc = alo_hip.lib().alo_msda_backward_hinted(
             *(ctypes.c_void_p(t.data_ptr()) for t in (value, sh, st, tl, attn, go, gv, gl, ga)), 1, S, 8, 32, 4, S, 4,
             alo_hip.ALO_F32, alo_hip.ALO_F32, hint, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -696,12 +768,23 @@ def test_tiled_backward_survives_a_host_hint_that_disagrees_with_the_device_shap
         assert (outs[0][i] - outs[1][i]).abs().max().item() <= 1e-5 * max(1.0, outs[0][i].abs().max().item())
 
 
-def test_tiled_backward_with_a_host_hint_that_under_counts_the_device_tiles():
+def test_tiled_backward_with_a_host_hint_that_under_counts_the_device_tiles(monkeypatch):
+    _hint_that_under_counts(TILED, monkeypatch)
+
+
+def test_wide_backward_with_a_host_hint_that_under_counts_the_device_tiles(monkeypatch):
+    _hint_that_under_counts(WIDE, monkeypatch)
+
+
+def _hint_that_under_counts(path, monkeypatch):
     """Round-3 advisor finding: a host copy with the same S but FEWER 4x4 tiles than the device shapes have ((5, 8) -> 4 tiles,
     (2, 20) -> 5) sized a grid that left the device's last tiles — their queries' grad_loc / grad_attn rows — unserved, silently.
     The kernel now compares the two counts and, on an under-count, groups the whole launch 16 queries in a row (the host's grid
-    always holds ceil(Lq / 16) groups): every query served, results those of the oracle."""
+    always holds ceil(Lq / 16) groups): every query served, results those of the oracle.  On the tiled kernel and on the wide one."""
     import ctypes
+
+    if path == TILED:
+        monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
 
     rng = np.random.default_rng(16)
     shapes_l = [(20, 28), (10, 14), (2, 20), (3, 4)]
@@ -720,6 +803,7 @@ def test_tiled_backward_with_a_host_hint_that_under_counts_the_device_tiles():
     sh, st = dev(shapes), dev(level_start(shapes))
     gv, gl, ga = torch.empty_like(value), torch.full_like(tl, float("nan")), torch.full_like(attn, float("nan"))
     hint = (ctypes.c_int32 * 8)(*[int(v) for hw in under for v in hw])
+    assert alo_hip.lib().alo_msda_backward_path(1, S, 8, 32, 4, S, 4, alo_hip.ALO_F32, alo_hip.ALO_F32, hint) == path
     rc = alo_hip.lib().alo_msda_backward_hinted(
         *(ctypes.c_void_p(t.data_ptr()) for t in (value, sh, st, tl, attn, go, gv, gl, ga)), 1, S, 8, 32, 4, S, 4,
         alo_hip.ALO_F32, alo_hip.ALO_F32, hint, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -730,8 +814,8 @@ def test_tiled_backward_with_a_host_hint_that_under_counts_the_device_tiles():
                                     attn_np.astype(np.float64), go_np.astype(np.float64))
     assert np.abs(gv.cpu().numpy() - rgv).max() <= 2e-4 * max(1.0, np.abs(rgv).max())
     assert np.abs(ga.cpu().numpy() - rga).max() <= 1e-4 * max(1.0, np.abs(rga).max())
-    ok = _away_from_pixel_edges(loc, shapes_l)
-    assert np.abs((gl.cpu().numpy() - rgl) * ok).max() <= 1e-4 * max(1.0, np.abs(rgl).max())
+    c = dict(value=value_np, shapes=shapes, level_start=level_start(shapes), loc=loc, attn=attn_np, grad_out=go_np)
+    assert _grad_loc_error(gl.cpu().numpy(), c)[0] <= 1e-4 * max(1.0, np.abs(rgl).max())
 
 
 # ---- coarse levels resident in LDS (alo_msda_forward_fused_hm_resident) ---------------------------------------------------------------
