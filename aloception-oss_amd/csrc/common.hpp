@@ -70,6 +70,10 @@ struct bf16_t {
     uint16_t bits;
 };
 
+// ReLU with torch's semantics: NaN is kept (fmaxf(NaN, 0) is 0 under IEEE maxNum) and -0 becomes +0 (the stem max-pools bf16
+// bit patterns as uint16, where 0x8000 would beat every positive value)
+__device__ __forceinline__ float relu_keep_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
+
 __device__ __forceinline__ float bf16_to_f32(uint16_t b) { return __uint_as_float(((unsigned)b) << 16); }
 // fp32 -> bf16, round to nearest even: gfx950 converts in hardware (v_cvt_pk_bf16_f32, two values per instruction)
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {

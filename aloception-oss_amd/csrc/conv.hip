@@ -259,7 +259,7 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
                     for (int a = 0; a < 2; ++a) {
                         float v0 = acc[a][b][4 * q] + bb[0], v1 = acc[a][b][4 * q + 1] + bb[1];
                         float v2 = acc[a][b][4 * q + 2] + bb[2], v3 = acc[a][b][4 * q + 3] + bb[3];
-                        if (dm.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+                        if (dm.relu) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
                         *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
                     }
                 }
@@ -299,7 +299,7 @@ conv_splitk_finalize_kernel(const float* __restrict__ partial, const bf16_t* __r
         }
         if (relu)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+            for (int j = 0; j < 8; ++j) v[j] = relu_keep_nan(v[j]);
         *reinterpret_cast<u32x4*>(Y + e) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
     }
 }

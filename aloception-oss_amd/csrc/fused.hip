@@ -131,7 +131,7 @@ bias_act_kernel(const T* x, const T* __restrict__ bias, const T* res, T* y,  // 
         }
         if constexpr (RELU) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
+            for (int k = 0; k < 4; ++k) v[k] = relu_keep_nan(v[k]);
         }
         store4(y + e, v);
     }
@@ -173,7 +173,7 @@ bias_act_nchw_kernel(const float* x, const float* __restrict__ bias, float* y, l
         load4(x + i * 4, v);
         const float b = bias[c];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] += b; if (RELU) v[k] = fmaxf(v[k], 0.f); }
+        for (int k = 0; k < 4; ++k) { v[k] += b; if (RELU) v[k] = relu_keep_nan(v[k]); }
         store4(y + i * 4, v);
     }
 }

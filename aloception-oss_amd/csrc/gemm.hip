@@ -142,7 +142,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         float v0 = acc[t][4 * q], v1 = acc[t][4 * q + 1], v2 = acc[t][4 * q + 2], v3 = acc[t][4 * q + 3];
-                        if (RELU && !HAS_RES) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+                        if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
                         *reinterpret_cast<u32x2*>(obuf + (32 * half + nl) * kOutStride + (32 * t + 8 * q + 4 * kg) * 2) =
                             u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
                     }
@@ -185,7 +185,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                         for (int i = 0; i < 4; ++i) {
                             float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
                             float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
-                            if (RELU) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
+                            if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
                             o4[i] = pack_bf16x2(lo, hi);
                         }
                         v = u32x4{o4[0], o4[1], o4[2], o4[3]};
@@ -401,8 +401,8 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
                     const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + r0 + col);
 #pragma unroll
                     for (int a = 0; a < 2; ++a) {
-                        const float v0 = fmaxf(acc1[a][t][4 * q] + bb[0], 0.f), v1 = fmaxf(acc1[a][t][4 * q + 1] + bb[1], 0.f);
-                        const float v2 = fmaxf(acc1[a][t][4 * q + 2] + bb[2], 0.f), v3 = fmaxf(acc1[a][t][4 * q + 3] + bb[3], 0.f);
+                        const float v0 = relu_keep_nan(acc1[a][t][4 * q] + bb[0]), v1 = relu_keep_nan(acc1[a][t][4 * q + 1] + bb[1]);
+                        const float v2 = relu_keep_nan(acc1[a][t][4 * q + 2] + bb[2]), v3 = relu_keep_nan(acc1[a][t][4 * q + 3] + bb[3]);
                         *reinterpret_cast<u32x2*>(hs + (32 * a + nl) * kFfnStride + col * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
                     }
                 }

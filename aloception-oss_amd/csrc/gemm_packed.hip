@@ -145,7 +145,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
             for (int a = 0; a < 2; ++a) {
                 float v0 = acc[a][t][4 * q] + bb[0], v1 = acc[a][t][4 * q + 1] + bb[1];
                 float v2 = acc[a][t][4 * q + 2] + bb[2], v3 = acc[a][t][4 * q + 3] + bb[3];
-                if (RELU && !HAS_RES) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
+                if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
                 *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
             }
         }
@@ -167,7 +167,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
                 for (int i = 0; i < 4; ++i) {
                     float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
                     float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
-                    if (RELU) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
+                    if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
                     o4[i] = pack_bf16x2(lo, hi);
                 }
                 v = u32x4{o4[0], o4[1], o4[2], o4[3]};

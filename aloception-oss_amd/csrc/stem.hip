@@ -136,7 +136,13 @@ stem_conv_pool_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W
                 const int g0 = 2 * s, g1 = 2 * s + 1;
                 const int off = kg ? (g1 / 3) * kInStride + (g1 % 3) * 16 : (g0 / 3) * kInStride + (g0 % 3) * 16;
                 const unsigned* ap = reinterpret_cast<const unsigned*>(a_base + off);
-                const u32x4 a = {ap[0], ap[1], ap[2], ap[3]};
+                u32x4 a = {ap[0], ap[1], ap[2], ap[3]};
+                // the zero-weight columns must contribute 0, not 0 x Inf / 0 x NaN: elements 21..23 of a tap row (fragment
+                // elements 5..7 of k-groups G % 3 == 2) hold the real pixel 2 lc + 7, or for lc = 14 the row's unstaged pad, and
+                // k-group 21 (G = 21, tap row 7) reads input row 2 lr + 7
+                const int G = kg ? g1 : g0;
+                if (G == 21) a = u32x4{0u, 0u, 0u, 0u};
+                else if (G % 3 == 2) { a.z &= 0x0000ffffu; a.w = 0u; }
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
                     acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wreg[s][ct]), as_bf16x8(a), acc[ct], 0, 0, 0);
@@ -153,8 +159,8 @@ stem_conv_pool_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W
                         unsigned lo = 0u, hi = 0u;
                         if (ok) {
                             const float v0 = acc[ct][4 * q], v1 = acc[ct][4 * q + 1], v2 = acc[ct][4 * q + 2], v3 = acc[ct][4 * q + 3];
-                            lo = pack_bf16x2(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f);
-                            hi = pack_bf16x2(v2 > 0.f ? v2 : 0.f, v3 > 0.f ? v3 : 0.f);
+                            lo = pack_bf16x2(relu_keep_nan(v0), relu_keep_nan(v1));
+                            hi = pack_bf16x2(relu_keep_nan(v2), relu_keep_nan(v3));
                         }
                         *reinterpret_cast<u32x2*>(conv_lds + m * kConvStride + (32 * ct + 8 * q + 4 * kg) * 2) = u32x2{lo, hi};
                     }

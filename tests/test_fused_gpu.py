@@ -273,6 +273,9 @@ def test_conv3x3_matches_fp32_convolution(shape, stride, relu, with_bias):
     assert got.shape == ref.shape and got.is_contiguous(memory_format=torch.channels_last)
     # |result| is O(1): half a bf16 ulp of the largest value plus fp32 summation-order noise
     assert (got.float() - ref).abs().max().item() <= 2.0 ** -8 * max(1.0, ref.abs().max().item())
+    # and element by element against fp64: 2^-8 |ref| + c(9 Cin) * (|x| * |w| + |b|) (test_backbone_kernels_gpu.py)
+    from test_backbone_kernels_gpu import check_conv3x3
+    check_conv3x3(x, wt, b, relu, stride, got)
 
 
 @pytest.mark.gpu
