@@ -1,4 +1,4 @@
-"""ctypes binding of ``libalo_hotpath.so`` (the C ABI declared in ``include/alo_hotpath.h``).
+"""ctypes binding of ``libalo_hotpath.so`` (the C ABI declared in ``include/alo_hotpath.h`` and ``include/alo_corr_alt.h``).
 
 This is the only place the host code touches the native library.  PyTorch is used for what it is good at here —
 device memory, streams, dtypes — and nothing else: every function below takes torch tensors, validates them the way
@@ -85,6 +85,12 @@ def _declare(lib):
     lib.alo_corr_lookup_backward.argtypes = [c.POINTER(vp), vp, vp] + [ip] * 5 + [vp]
     lib.alo_corr_lookup_backward_coords.restype = ip
     lib.alo_corr_lookup_backward_coords.argtypes = [c.POINTER(vp), vp, vp, vp] + [ip] * 5 + [vp]
+    lib.alo_corr_alt_workspace_bytes.restype = sz
+    lib.alo_corr_alt_workspace_bytes.argtypes = [ip] * 5
+    lib.alo_corr_alt_prepare.restype = ip
+    lib.alo_corr_alt_prepare.argtypes = [vp, c.POINTER(vp), vp, sz] + [ip] * 5 + [vp]
+    lib.alo_corr_alt_lookup.restype = ip
+    lib.alo_corr_alt_lookup.argtypes = [vp, sz, vp, vp] + [ip] * 6 + [vp]
     lib.alo_msda_forward_fused_hm.restype = ip
     lib.alo_msda_forward_fused_hm_rows.restype = ip
     lib.alo_msda_forward_fused_hm_rows.argtypes = [vp] * 5 + [c.c_long, c.c_long, vp, vp] + [ip] * 9 + [vp]
@@ -632,6 +638,48 @@ def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
 
 
 # ---- one-pass epilogues around the attention op (alo_add_layernorm / alo_bias_act) ---------------------------------------
+def corr_alt_prepare(fmap1, fmap2_levels):
+    """AlternateCorrBlock.__init__ (corr.py:63-71): fmap1 (B,C,H,W) and the 2x2-mean chain of fmap2 (level l: (B,C,h_l,w_l)) ->
+    the workspace of :func:`corr_alt_lookup` (uint8 tensor): channels-last copies of fmap1 and of every level, made once."""
+    _require_f32_cuda("fmap1", fmap1, 4)
+    for lvl, t in enumerate(fmap2_levels):
+        _require_f32_cuda(f"fmap2_levels[{lvl}]", t, 4)
+    B, C, H, W = fmap1.shape
+    L = len(fmap2_levels)
+    for lvl, ((h, w), t) in enumerate(zip(corr_level_shapes(H, W, L), fmap2_levels)):
+        if tuple(t.shape) != (B, C, h, w) or t.device != fmap1.device:
+            raise RuntimeError(f"fmap2_levels[{lvl}] must be ({B}, {C}, {h}, {w}) on {fmap1.device}, got {tuple(t.shape)} on {t.device}")
+    fmap1 = fmap1.contiguous()
+    levels = [t.contiguous() for t in fmap2_levels]
+    nbytes = lib().alo_corr_alt_workspace_bytes(B, C, H, W, L)   # 0 past the limits: the call below says which
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=fmap1.device)
+    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels])
+    moved = 4.0 * 2 * (fmap1.numel() + sum(t.numel() for t in levels))
+    with torch.cuda.device(fmap1.device), _timed("corr_alt_prepare", moved):
+        _check(lib().alo_corr_alt_prepare(_ptr(fmap1), ptrs, _ptr(ws), nbytes, B, C, H, W, L, _stream(fmap1.device)))
+    return ws
+
+
+def corr_alt_lookup(workspace, coords, channels, num_levels, radius=4):
+    """AlternateCorrBlock.__call__ (corr.py:73-91): workspace from :func:`corr_alt_prepare` (same feature maps' C = ``channels``
+    and ``num_levels``), coords (B,2,H,W) -> (B, L*(2r+1)^2, H, W) float32, the layout and value of :func:`corr_lookup`."""
+    _require_f32_cuda("coords", coords, 4)
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.device != coords.device:
+        raise RuntimeError("workspace must be the uint8 CUDA tensor corr_alt_prepare returned, on the device of coords")
+    coords = coords.contiguous()
+    B, two, H, W = coords.shape
+    if two != 2:
+        raise RuntimeError("coords must be (B,2,H,W)")
+    L, C, win = num_levels, channels, (2 * radius + 1) ** 2
+    out = torch.empty((B, L * win, H, W), dtype=torch.float32, device=coords.device)
+    flops = 2.0 * B * H * W * L * (2 * radius + 2) ** 2 * C          # the lattice's inner products (the mixes are noise)
+    nbytes = 4.0 * B * H * W * (L * win + 2 + L * C)                 # out + coords + fmap1 once per level (footprints: cache hits)
+    with torch.cuda.device(coords.device), _timed("corr_alt_lookup", nbytes, flops):
+        _check(lib().alo_corr_alt_lookup(_ptr(workspace), workspace.numel(), _ptr(coords), _ptr(out), B, C, H, W, radius, L,
+                                         _stream(coords.device)))
+    return out
+
+
 def fusable(*tensors):
     """True when the fused epilogues may replace the stock ops: inference (no autograd graph), CUDA, fp32 or bf16."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):

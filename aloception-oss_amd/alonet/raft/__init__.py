@@ -1,5 +1,5 @@
-from .corr import CorrBlock
+from .corr import AlternateCorrBlock, CorrBlock
 from .raft import RAFT, RAFTBase
 from .raft_small import RAFTSmall
 
-__all__ = ["CorrBlock", "RAFT", "RAFTBase", "RAFTSmall"]
+__all__ = ["AlternateCorrBlock", "CorrBlock", "RAFT", "RAFTBase", "RAFTSmall"]

@@ -4,8 +4,9 @@ two-term operand split, three products — csrc/corr.hip), windowed lookup as a 
 Drop-in for the reference's ``CorrBlock`` (alonet/raft/corr.py:12-60) through RAFT's ``corr_block=`` constructor
 hook (alonet/raft/raft.py:47-60,168,185): ``CorrBlock(fmap1, fmap2, num_levels=4, radius=4)`` builds
 ``corr_pyramid`` (list of ``(B*H*W, 1, h_l, w_l)`` float32 tensors) and ``corr_fn(coords)`` returns the
-``(B, num_levels*(2r+1)^2, H, W)`` float32 window features.  ``AlternateCorrBlock`` is not provided: the reference's
-version needs the absent third-party ``alt_cuda_corr`` extension and is unreachable (corr.py:5-9,86).
+``(B, num_levels*(2r+1)^2, H, W)`` float32 window features.  ``AlternateCorrBlock`` (corr.py:63-91) is the memory-light
+variant: it keeps the feature maps instead of the volume and computes each lookup's inner products on the fly
+(csrc/corr_alt.hip); see its docstring.
 
 Differentiability.  The reference's block is plain autograd-able torch code, so RAFT can be fine-tuned through it.  Here, when
 the feature maps require a gradient:
@@ -264,3 +265,109 @@ class CorrBlock:
         else:
             (vol,) = alo_hip.corr_build(fmap1, fmap2, 1)
         return vol.view(B, H, W, 1, H, W)
+
+
+# ---- the memory-light block (corr.py:63-91) ----------------------------------------------------------------------------------------
+def _alt_pyramid(fmap1, fmap2, num_levels):
+    """corr.py:66-71: ``[(fmap1, fmap2)]`` + one 2x2 mean (floor) of both per level.  The reference pools ``num_levels`` times and
+    never reads the last pair; that pair is left out where the last level read is one pixel wide or high (nothing to pool)."""
+    B, C, H, W = fmap1.shape
+    h, w = H, W
+    for lvl in range(num_levels):
+        if h == 0 or w == 0:
+            raise RuntimeError(f"AlternateCorrBlock: pyramid level {lvl} of a {H}x{W} grid is empty (num_levels={num_levels})")
+        h, w = h // 2, w // 2
+    pyramid = [(fmap1, fmap2)]
+    for lvl in range(num_levels):
+        if lvl == num_levels - 1 and (fmap2.shape[-2] < 2 or fmap2.shape[-1] < 2):
+            break
+        fmap1, fmap2 = F.avg_pool2d(fmap1, 2, stride=2), F.avg_pool2d(fmap2, 2, stride=2)
+        pyramid.append((fmap1, fmap2))
+    return pyramid
+
+
+class AlternateCorrBlock:
+    """RAFT's memory-light correlation block (the reference's ``AlternateCorrBlock``, corr.py:63-91), on the gfx950 kernels of
+    csrc/corr_alt.hip.  ``AlternateCorrBlock(fmap1, fmap2, num_levels=4, radius=4)``; ``blk(coords)`` -> ``(B,
+    num_levels*(2r+1)^2, H, W)`` float32.  ``RAFT(corr_block=AlternateCorrBlock)`` works unchanged.
+
+    Memory: only the feature maps are kept (O(HW*C)), not the O((HW)^2) all-pairs volume of :class:`CorrBlock`; every lookup
+    computes the (2r+2)^2 inner products under each query's window.  4 x 1280x720 frames take 4.4 GB of pyramid with CorrBlock and
+    59 MB of feature map here; 7680x4320 runs, where ``alo_corr_build`` refuses the grid.
+
+    Value.  The reference's lookup calls the third-party ``alt_cuda_corr`` extension, whose source is not vendored here; the pin is
+    therefore CorrBlock's golden outputs.  A 2x2 mean commutes with the inner product, so this block computes the SAME function as
+    ``CorrBlock(fmap1, fmap2, num_levels, radius)(coords)`` up to fp32 rounding, channel layout included: the level is the outer
+    index, within a window the first axis offsets x and the second offsets y, scale 1/sqrt(C).  Level l looks up ``fmap2``
+    2x2-pooled l times at ``coords / 2^l`` against the full-resolution ``fmap1``.  Coordinates are plain pixel coordinates with
+    zeros outside the map (no ``2x/(w-1)-1`` round trip), so levels one pixel wide or high give finite values (CorrBlock gives NaN
+    there); NaN, +-inf and |coords / 2^l| >= 1e6 read as all-zero windows; a non-finite feature reaches exactly the outputs whose
+    taps touch it.
+
+    No autograd, as in the reference (``alt_cuda_corr.forward`` is called outside any ``autograd.Function``): the output never
+    requires a gradient, even when the feature maps do.
+
+    Attributes: ``num_levels``, ``radius`` and ``pyramid``, the reference's list of ``(fmap1_i, fmap2_i)`` NCHW pairs.  The
+    channels-last copies the kernel reads are made once, here; the reference re-permutes on every lookup.  Construction and lookup
+    make no host synchronisation (CUDA-graph capturable).
+    """
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        self.num_levels = num_levels
+        self.radius = radius
+        fmap1, fmap2 = fmap1.float(), fmap2.float()
+        alo_hip._require_f32_cuda("fmap1", fmap1, 4)
+        alo_hip._require_f32_cuda("fmap2", fmap2, 4)
+        if fmap1.shape != fmap2.shape:
+            raise RuntimeError("fmap1 and fmap2 must have the same shape")
+        if not 0 <= radius <= 7:
+            raise RuntimeError(f"AlternateCorrBlock: radius must be in [0,7], got {radius}")
+        with torch.no_grad():
+            fmap1, fmap2 = fmap1.detach().contiguous(), fmap2.detach().contiguous()
+            self.pyramid = _alt_pyramid(fmap1, fmap2, num_levels)
+            self._channels = fmap1.shape[1]
+            self._workspace = alo_hip.corr_alt_prepare(fmap1, [f2 for _, f2 in self.pyramid[:num_levels]])
+
+    def __call__(self, coords):
+        return alo_hip.corr_alt_lookup(self._workspace, coords.detach().float(), self._channels, self.num_levels, self.radius)
+
+
+def lookup_alt_torch(pyramid, coords, num_levels, radius):
+    """What :class:`AlternateCorrBlock` computes, on stock torch ops: the inner product of fmap1 with fmap2_l sampled bilinearly
+    (zeros outside) at every tap (interpolation commutes with the inner product), pixel coordinates mapped exactly onto
+    ``grid_sample(align_corners=False)``'s grid so that maps one pixel wide work too."""
+    B, _, H, W = coords.shape
+    r = radius
+    f1 = pyramid[0][0]
+    C = f1.shape[1]
+    steps = torch.arange(-r, r + 1, device=coords.device, dtype=coords.dtype)
+    dx = steps.view(-1, 1).expand(2 * r + 1, 2 * r + 1)   # first window axis: x offset
+    dy = steps.view(1, -1).expand(2 * r + 1, 2 * r + 1)
+    x, y = coords[:, 0].reshape(B, H * W, 1), coords[:, 1].reshape(B, H * W, 1)
+    valid = (x.abs() < 1e6) & (y.abs() < 1e6)
+    outs = []
+    for lvl in range(num_levels):
+        f2 = pyramid[lvl][1]
+        h, w = f2.shape[-2:]
+        xl = torch.where(valid, x, torch.zeros_like(x)) / 2 ** lvl
+        yl = torch.where(valid, y, torch.zeros_like(y)) / 2 ** lvl
+        valid_l = valid & (xl.abs() < 1e6) & (yl.abs() < 1e6)
+        gx = (2 * (xl + dx.reshape(1, 1, -1)) + 1) / w - 1
+        gy = (2 * (yl + dy.reshape(1, 1, -1)) + 1) / h - 1
+        grid = torch.stack([gx, gy], dim=-1)                                       # (B, HW, WIN^2, 2)
+        taps = F.grid_sample(f2, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # (B, C, HW, WIN^2)
+        corr = (f1.reshape(B, C, H * W, 1) * taps).sum(1) / math.sqrt(C)           # (B, HW, WIN^2)
+        outs.append(torch.where(valid_l, corr, torch.zeros_like(corr)))
+    return torch.cat(outs, dim=-1).permute(0, 2, 1).reshape(B, -1, H, W).contiguous().float()
+
+
+class TorchAlternateCorrBlock:
+    """:class:`AlternateCorrBlock` on stock torch ops only (any device; the CPU yardstick, as :class:`TorchCorrBlock` is for
+    CorrBlock).  Differentiable, unlike the HIP block."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        self.num_levels, self.radius = num_levels, radius
+        self.pyramid = _alt_pyramid(fmap1.float(), fmap2.float(), num_levels)
+
+    def __call__(self, coords):
+        return lookup_alt_torch(self.pyramid, coords.float(), self.num_levels, self.radius)

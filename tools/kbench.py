@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel-level micro-benchmarks of the hot path at BASELINE.json sizes (HIP events on the launch stream).
 
-    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup] [--reps 20] [--dtype f32|bf16]
+    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup,alt_corr_lookup] [--reps 20] [--dtype f32|bf16]
 
 Prints one JSON object per kernel: average launch time, algorithmic bytes / flops (SURVEY.md section 8d formulas),
 achieved GB/s or TFLOP/s.  Tuning knobs are environment variables of the library (ALO_MSDA_FWD_WAVES, ALO_MSDA_ITERS).
@@ -262,6 +262,30 @@ def bench_corr_lookup(B, reps, H=90, W=160, C=256):
     return dict(kernel="corr_lookup", B=B, ms=t * 1e3, alg_bytes=nbytes, GBps=nbytes / t / 1e9)
 
 
+def bench_alt_corr_lookup(B, reps, H=90, W=160, C=256, r=4, L=4):
+    """AlternateCorrBlock's lookup (csrc/corr_alt.hip) at configs[2] size, two coordinate sets: smooth (identity grid + a smooth
+    flow of a few pixels) and random (uniform over the map).  alg_flops = the (2r+2)^2 inner products per query and level."""
+    from alonet.raft.corr import AlternateCorrBlock
+
+    f1, f2 = corr_inputs(B, C, H, W)
+    blk = AlternateCorrBlock(f1, f2, num_levels=L, radius=r)
+    ys, xs = torch.meshgrid(torch.arange(H, device=DEV), torch.arange(W, device=DEV), indexing="ij")
+    flow = torch.stack([3 * torch.sin(ys / 9.0) + 2 * torch.cos(xs / 13.0), 2 * torch.cos(xs / 11.0) - 1.5 * torch.sin(ys / 7.0)])
+    gen = torch.Generator(device=DEV).manual_seed(1)
+    sets = {"smooth": torch.stack([xs, ys]).float()[None].repeat(B, 1, 1, 1) + flow[None],
+            "random": torch.stack([torch.rand(B, H, W, generator=gen, device=DEV) * W,
+                                   torch.rand(B, H, W, generator=gen, device=DEV) * H], 1)}
+    HW = H * W
+    flops = 2.0 * B * HW * L * (2 * r + 2) ** 2 * C
+    nbytes = 4.0 * B * HW * (L * (2 * r + 1) ** 2 + 2 + L * C)   # out + coords + fmap1 per level (fmap2 footprints: cache)
+    out = []
+    for name, coords in sets.items():
+        t = time_launches(lambda: blk(coords), reps)
+        out.append(dict(kernel="alt_corr_lookup", coords=name, B=B, H=H, W=W, C=C, radius=r, levels=L, ms=t * 1e3,
+                        alg_flops=flops, GFLOPs=flops / t / 1e9, alg_bytes=nbytes, GBps=nbytes / t / 1e9))
+    return out
+
+
 def bench_corr_lookup_bwd(B, reps, H=90, W=160):
     """The lookup's adjoint: read the 324 output gradients, read-modify-write the 4 x 10 x 10 footprints (the gradient maps)."""
     shapes = alo_hip.corr_level_shapes(H, W, 4)
@@ -350,6 +374,8 @@ def main():
             res = [bench_corr_lookup_bwd(4, a.reps)]
         elif w == "corr_lookup":
             res = [bench_corr_lookup(a.B, a.reps)]
+        elif w == "alt_corr_lookup":
+            res = bench_alt_corr_lookup(a.B, a.reps)
         elif w == "epilogues":
             res = [r for dt in dts for r in bench_epilogues(a.N, dt, a.reps)]
         for r in res:
