@@ -42,7 +42,27 @@ def tensor_version(t):
                           "every call instead of being cached — results are right, the forward is slower.  Build / load the model outside "
                           "inference_mode() (torch.no_grad() is enough for inference).", RuntimeWarning, stacklevel=3)
         return object()
-    return None if t.is_inference() else t._version
+    return t._version
+
+
+_DERIVED = "_alo_derived"      # owner.__dict__[_DERIVED] = {name: (key, payload)}: every derived tensor of this package lives there
+_EPOCH = "_alo_cache_epoch"    # model.__dict__[_EPOCH]: how often invalidate_caches ran on it
+
+
+def derived(owner, name, sources, build, no_grad=True):
+    """What ``build()`` makes (a tensor or a tuple of them) from the tensors in ``sources`` (``None`` stands for an absent bias),
+    cached on ``owner`` (an ``nn.Module`` or a tensor) under ``name`` until a source changes: its version counter (in-place
+    updates), its pointer (``p.data = other``), its dtype or its device (``module.to(...)``).  A pack rides on the tensor
+    it was packed from and dies with it; a derived tensor may own derived tensors in turn.  ``build`` runs under
+    ``torch.no_grad()`` unless ``no_grad=False`` (then in the caller's grad mode).  An owner without a ``__dict__`` gets no
+    caching.  Writes through ``.data`` bump no version counter: :func:`invalidate_caches` is for those."""
+    entries = owner.__dict__.setdefault(_DERIVED, {}) if hasattr(owner, "__dict__") else {}
+    key = tuple([None if t is None else (tensor_version(t), t.data_ptr(), t.dtype, t.device) for t in sources])
+    hit = entries.get(name)
+    if hit is None or hit[0] != key:
+        with torch.set_grad_enabled(torch.is_grad_enabled() and not no_grad):
+            hit = entries[name] = (key, build())
+    return hit[1]
 
 
 class HotpathUnavailable(RuntimeError):
@@ -345,6 +365,19 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
     return out
 
 
+def _check_fused_operands(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, dims):
+    """Dtype and shape checks the two fused forwards share -> the last dim of ``reference_points`` (2 or 4)."""
+    N, Lq, M, L, P = dims
+    if sampling_offsets.dtype != value.dtype or attn_logits.dtype != value.dtype:
+        raise RuntimeError("sampling_offsets and attn_logits must have the dtype of value")
+    if spatial_shapes.dtype != torch.int32 or level_start_index.dtype != torch.int32:
+        raise RuntimeError("spatial_shapes and level_start_index must be int32 tensors")
+    ref_dim = reference_points.shape[-1]
+    if tuple(reference_points.shape) != (N, Lq, L, ref_dim) or attn_logits.numel() != N * Lq * M * L * P:
+        raise RuntimeError("reference_points must be (N,Lq,L,2|4) and attn_logits (N,Lq,M,L*P)")
+    return ref_dim
+
+
 def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points):
     """MSDeformAttn's prologue + gather in one launch (inference): raw offsets (N,Lq,M,L,P,2) and raw attention logits
     (N,Lq,M,L*P) in ``value``'s dtype, reference points (N,Lq,L,2|4) in fp32 (fp64 for fp64 values) -> (N,Lq,M*D)."""
@@ -357,13 +390,8 @@ def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offset
     _require_cuda_contiguous([("value", value), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index),
                               ("sampling_offsets", sampling_offsets), ("attn_logits", attn_logits),
                               ("reference_points", reference_points)])
-    if sampling_offsets.dtype != value.dtype or attn_logits.dtype != value.dtype:
-        raise RuntimeError("sampling_offsets and attn_logits must have the dtype of value")
-    if spatial_shapes.dtype != torch.int32 or level_start_index.dtype != torch.int32:
-        raise RuntimeError("spatial_shapes and level_start_index must be int32 tensors")
-    ref_dim = reference_points.shape[-1]
-    if tuple(reference_points.shape) != (N, Lq, L, ref_dim) or attn_logits.numel() != N * Lq * M * L * P:
-        raise RuntimeError("reference_points must be (N,Lq,L,2|4) and attn_logits (N,Lq,M,L*P)")
+    ref_dim = _check_fused_operands(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
+                                    (N, Lq, M, L, P))
     vdt = _DTYPE_CODE.get(value.dtype)
     if vdt is None:
         raise RuntimeError(f"ms_deform_attn: unsupported value dtype {value.dtype}")
@@ -435,13 +463,8 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     _, Lq, _, L, P, _ = sampling_offsets.shape
     reference_points = reference_points.float().contiguous()
     _require_cuda_contiguous([("value", value_hm), ("spatial_shapes", spatial_shapes), ("level_start_index", level_start_index)])
-    if sampling_offsets.dtype != value_hm.dtype or attn_logits.dtype != value_hm.dtype:
-        raise RuntimeError("sampling_offsets and attn_logits must have the dtype of value")
-    if spatial_shapes.dtype != torch.int32 or level_start_index.dtype != torch.int32:
-        raise RuntimeError("spatial_shapes and level_start_index must be int32 tensors")
-    ref_dim = reference_points.shape[-1]
-    if tuple(reference_points.shape) != (N, Lq, L, ref_dim) or attn_logits.numel() != N * Lq * M * L * P:
-        raise RuntimeError("reference_points must be (N,Lq,L,2|4) and attn_logits (N,Lq,M,L*P)")
+    ref_dim = _check_fused_operands(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
+                                    (N, Lq, M, L, P))
     off_rs, log_rs = _query_rows(sampling_offsets, M * L * P * 2), _query_rows(attn_logits, M * L * P)
     if off_rs is None or log_rs is None or off_rs % 8 or log_rs % 8 or not sampling_offsets.is_cuda or not attn_logits.is_cuda:
         sampling_offsets, attn_logits = sampling_offsets.contiguous(), attn_logits.contiguous()
@@ -451,10 +474,7 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     nbytes = e * (N * S * M * D + N * Lq * M * D + N * Lq * M * L * P * 3) + 4 * reference_points.numel()
     # coarse levels resident in LDS: needs a HOST copy of the shapes (it picks the resident levels, fixes the LDS layout and sizes the
     # grid; the kernel re-checks it against the device copy).  Only a copy that is already at hand is used — no device read in a forward.
-    host = getattr(spatial_shapes, "_alo_shapes", None) if resident else None
-    if host is None and resident:
-        hit = getattr(spatial_shapes, "_alo_shapes_read", None)
-        host = hit[1] if hit is not None and hit[0] == tensor_version(spatial_shapes) else None
+    host = _host_spatial_shapes(spatial_shapes, read=False) if resident else None
     starts = None
     if host is not None and D == 32 and len(host) == L and sum(int(h) * int(w) for h, w in host) == S:
         starts = (ctypes.c_int32 * (2 * L))(*[int(v) for hw in host for v in hw])
@@ -479,17 +499,20 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     return out
 
 
-def _host_spatial_shapes(spatial_shapes):
+def _host_spatial_shapes(spatial_shapes, read=True):
     """Host copy of a device ``spatial_shapes`` tensor.  It rides on the tensor OBJECT (``_alo_shapes``, tagged with the version
     counter it was read at; DeformableTransformer attaches its own list when it builds the tensor), so it dies with the tensor: a cache
     keyed on the storage pointer would hand a stale copy to the next 32-byte tensor the caching allocator places at that address.
-    Without the attribute: one device-to-host read, then cached on the object."""
+    Without the attribute: one device-to-host read, then cached on the object — or, with ``read=False``, None unless an earlier
+    read is still valid."""
     host = getattr(spatial_shapes, "_alo_shapes", None)   # attached by the model that built the tensor
     if host is not None:
         return host
     hit = getattr(spatial_shapes, "_alo_shapes_read", None)
     if hit is not None and hit[0] == tensor_version(spatial_shapes):
         return hit[1]
+    if not read:
+        return None
     host = [tuple(int(v) for v in hw) for hw in spatial_shapes.tolist()]
     spatial_shapes._alo_shapes_read = (tensor_version(spatial_shapes), host)
     return host
@@ -569,20 +592,32 @@ def corr_build(fmap1, fmap2, num_levels=4):
     return levels
 
 
-def corr_lookup(levels, coords, radius=4):
-    """levels from :func:`corr_build`, coords (B,2,H,W) -> (B, L*(2r+1)^2, H, W) float32  (corr.py:29-50)."""
+def _corr_lookup_args(levels, levels_name, coords, radius, grad_out=None, fn=None):
+    """What the three lookup entry points check alike -> (coords, grad_out) contiguous, the level pointers, (B, H, W, L).
+    ``fn``: the name the backward entry points put before their message on coords / grad_out."""
     _require_f32_cuda("coords", coords, 4)
     coords = coords.contiguous()
     B, two, H, W = coords.shape
-    if two != 2:
-        raise RuntimeError("coords must be (B,2,H,W)")
     L = len(levels)
+    if grad_out is None:
+        if two != 2:
+            raise RuntimeError("coords must be (B,2,H,W)")
+    else:
+        _require_f32_cuda("grad_out", grad_out, 4)
+        grad_out = grad_out.contiguous()
+        if two != 2 or tuple(grad_out.shape) != (B, L * (2 * radius + 1) ** 2, H, W):
+            raise RuntimeError(f"{fn}: coords must be (B,2,H,W) and grad_out (B, L*(2r+1)^2, H, W)")
     for lvl, t in enumerate(levels):
-        _require_f32_cuda(f"corr_pyramid[{lvl}]", t, 4)
+        _require_f32_cuda(f"{levels_name}[{lvl}]", t, 4)
         if not t.is_contiguous() or t.shape[0] != B * H * W:
-            raise RuntimeError(f"corr_pyramid[{lvl}] must be a contiguous (B*H*W,1,h,w) tensor")
+            raise RuntimeError(f"{levels_name}[{lvl}] must be a contiguous (B*H*W,1,h,w) tensor")
+    return coords, grad_out, (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels]), (B, H, W, L)
+
+
+def corr_lookup(levels, coords, radius=4):
+    """levels from :func:`corr_build`, coords (B,2,H,W) -> (B, L*(2r+1)^2, H, W) float32  (corr.py:29-50)."""
+    coords, _, ptrs, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius)
     out = torch.empty((B, L * (2 * radius + 1) ** 2, H, W), dtype=torch.float32, device=coords.device)
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels])
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2)
     with torch.cuda.device(coords.device), _timed("corr_lookup", nbytes):
@@ -594,18 +629,8 @@ def corr_lookup_backward(grad_levels, coords, grad_out, radius=4):
     """Adds the pyramid gradients of ONE lookup to ``grad_levels`` (tensors shaped like the pyramid, zeroed by the caller before the
     first lookup whose gradients are to be summed): the adjoint of :func:`corr_lookup` with respect to the levels (autograd through
     the reference's bilinear_sampler, corr.py:29-50).  In place; returns ``grad_levels``."""
-    _require_f32_cuda("coords", coords, 4)
-    _require_f32_cuda("grad_out", grad_out, 4)
-    coords, grad_out = coords.contiguous(), grad_out.contiguous()
-    B, two, H, W = coords.shape
-    L = len(grad_levels)
-    if two != 2 or tuple(grad_out.shape) != (B, L * (2 * radius + 1) ** 2, H, W):
-        raise RuntimeError("corr_lookup_backward: coords must be (B,2,H,W) and grad_out (B, L*(2r+1)^2, H, W)")
-    for lvl, t in enumerate(grad_levels):
-        _require_f32_cuda(f"grad_levels[{lvl}]", t, 4)
-        if not t.is_contiguous() or t.shape[0] != B * H * W:
-            raise RuntimeError(f"grad_levels[{lvl}] must be a contiguous (B*H*W,1,h,w) tensor")
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grad_levels])
+    coords, grad_out, ptrs, (B, H, W, L) = _corr_lookup_args(grad_levels, "grad_levels", coords, radius, grad_out,
+                                                             "corr_lookup_backward")
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + 2 * L * taps + 2)
     with torch.cuda.device(coords.device), _timed("corr_lookup_backward", nbytes):
@@ -616,19 +641,9 @@ def corr_lookup_backward(grad_levels, coords, grad_out, radius=4):
 def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
     """Gradient of :func:`corr_lookup` with respect to ``coords`` -> (B, 2, H, W): grid_sample's gradient with respect to the grid
     chained through the reference's coordinate arithmetic (corr.py:29-50); per-level maps from the kernel, added here."""
-    _require_f32_cuda("coords", coords, 4)
-    _require_f32_cuda("grad_out", grad_out, 4)
-    coords, grad_out = coords.contiguous(), grad_out.contiguous()
-    B, two, H, W = coords.shape
-    L = len(levels)
-    if two != 2 or tuple(grad_out.shape) != (B, L * (2 * radius + 1) ** 2, H, W):
-        raise RuntimeError("corr_lookup_backward_coords: coords must be (B,2,H,W) and grad_out (B, L*(2r+1)^2, H, W)")
-    for lvl, t in enumerate(levels):
-        _require_f32_cuda(f"corr_pyramid[{lvl}]", t, 4)
-        if not t.is_contiguous() or t.shape[0] != B * H * W:
-            raise RuntimeError(f"corr_pyramid[{lvl}] must be a contiguous (B*H*W,1,h,w) tensor")
+    coords, grad_out, ptrs, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius, grad_out,
+                                                             "corr_lookup_backward_coords")
     per_level = torch.empty((B, L, 2, H, W), dtype=torch.float32, device=coords.device)
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels])
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2 + 2 * L)
     with torch.cuda.device(coords.device), _timed("corr_lookup_backward_coords", nbytes):
@@ -637,7 +652,6 @@ def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
     return per_level.sum(1)
 
 
-# ---- one-pass epilogues around the attention op (alo_add_layernorm / alo_bias_act) ---------------------------------------
 def corr_alt_prepare(fmap1, fmap2_levels):
     """AlternateCorrBlock.__init__ (corr.py:63-71): fmap1 (B,C,H,W) and the 2x2-mean chain of fmap2 (level l: (B,C,h_l,w_l)) ->
     the workspace of :func:`corr_alt_lookup` (uint8 tensor): channels-last copies of fmap1 and of every level, made once."""
@@ -696,25 +710,22 @@ def add_layernorm_supported(x):
 
 
 def invalidate_caches(module):
-    """Drop every derived inference-time tensor this library cached on ``module``'s parameters and sub-modules (packed MFMA
-    weights, folded batch-norm convolutions, merged projections).  The caches are keyed on ``(tensor._version, data_ptr)``;
-    in-place writes through ``.data`` (``p.data.copy_``, EMA updates, ``nn.init.*_(w.data)``) do not bump the version
-    counter, so call this after such weight surgery — ``alonet.common.load_weights`` and ``GraphedForward`` do."""
-    module.__dict__["_cache_epoch_alo"] = module.__dict__.get("_cache_epoch_alo", 0) + 1   # GraphedForward re-captures on a new epoch
-    for p in list(module.parameters()) + list(module.buffers()):
-        for key in ("_alo_packed", "_alo_2d"):
-            if key in getattr(p, "__dict__", {}):
-                delattr(p, key)
-    for m in module.modules():
-        for key in [k for k in m.__dict__ if k.startswith("_alo_") or k in ("_folded", "_mask_quarter") or k.startswith("_zr")]:
-            del m.__dict__[key]
+    """Drop every derived inference-time tensor (:func:`derived`: packed MFMA weights, folded batch-norm convolutions, merged
+    projections) held by ``module``'s sub-modules, parameters and buffers; what those derived tensors own in turn goes with
+    them.  In-place writes through ``.data`` (``p.data.copy_``, EMA updates, ``nn.init.*_(w.data)``) do not bump the version
+    counter the entries are keyed on, so call this after such weight surgery — ``alonet.common.load_weights`` and
+    ``GraphedForward`` do."""
+    module.__dict__[_EPOCH] = cache_epoch(module) + 1   # GraphedForward re-captures on a new epoch
+    for owner in (*module.modules(), *module.parameters(), *module.buffers()):
+        owner.__dict__.pop(_DERIVED, None)
 
 
 def cache_epoch(module):
     """How many times :func:`invalidate_caches` ran on ``module`` — graphs captured under an older epoch read freed tensors."""
-    return module.__dict__.get("_cache_epoch_alo", 0)
+    return module.__dict__.get(_EPOCH, 0)
 
 
+# ---- one-pass epilogues around the attention op (alo_add_layernorm / alo_bias_act) ---------------------------------------
 def add_layernorm(x, residual, weight, bias, eps=1e-5, pos=None):
     """``LayerNorm(x + residual)`` over the last dim in one pass; with ``pos`` also returns ``out + pos`` (the next
     layer's ``with_pos_embed``).  Replaces ``norm(src + dropout(src2))`` of the (de)formable transformer layers at
@@ -952,18 +963,17 @@ def ffn256_supported(x, w1, w2):
 
 
 def pack_mfma_b(weight):
-    """(N, K) bf16 weight -> MFMA B-fragment order.  The packed copy rides on the weight tensor object itself, tagged
-    with the version counter it was made from: packed once per weight update, gone with the tensor."""
-    tag = (tensor_version(weight), weight.data_ptr())
-    hit = getattr(weight, "_alo_packed", None)
-    if hit is None or hit[0] != tag:
-        w = weight.detach().contiguous()
-        packed = torch.empty_like(w)
-        with torch.cuda.device(w.device):
-            _check(lib().alo_pack_mfma_b(_ptr(w), _ptr(packed), w.shape[0], w.shape[1], ALO_BF16, _stream(w.device)))
-        hit = (tag, packed)
-        weight._alo_packed = hit
-    return hit[1]
+    """(N, K) bf16 weight -> MFMA B-fragment order.  The packed copy rides on the weight tensor object itself
+    (:func:`derived`): packed once per weight update, gone with the tensor."""
+    return derived(weight, "mfma_b", (weight,), lambda: _pack_mfma_b(weight.contiguous()))
+
+
+def _pack_mfma_b(w):
+    """The pack kernel on a contiguous (N, K) bf16 matrix."""
+    packed = torch.empty_like(w)
+    with torch.cuda.device(w.device):
+        _check(lib().alo_pack_mfma_b(_ptr(w), _ptr(packed), w.shape[0], w.shape[1], ALO_BF16, _stream(w.device)))
+    return packed
 
 
 def ffn256(x, w1, b1, w2, b2):
@@ -1002,23 +1012,16 @@ def conv3x3(x, weight, bias=None, relu=False, stride=1):
                            "Cout % 64 == 0, stride 1 or 2, no autograd")
     n, cin, h, w_ = x.shape
     cout = weight.shape[0]
-    tag = (tensor_version(weight), weight.data_ptr())
-    hit = getattr(weight, "_alo_packed", None)
-    if hit is None or hit[0] != tag:
-        # (Cout, ky, kx, Cin) row-major = the channels-last memory of the weight; pack it as a (Cout, 9 Cin) matrix
-        wm = weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()
-        packed = torch.empty_like(wm)
-        with torch.cuda.device(x.device):
-            _check(lib().alo_pack_mfma_b(_ptr(wm), _ptr(packed), cout, 9 * cin, ALO_BF16, _stream(x.device)))
-        hit = (tag, packed)
-        weight._alo_packed = hit
+    # (Cout, ky, kx, Cin) row-major = the channels-last memory of the weight; pack it as a (Cout, 9 Cin) matrix
+    packed = derived(weight, "conv3x3_b", (weight,),
+                     lambda: _pack_mfma_b(weight.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()))
     ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.contiguous()
     ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, stride)   # split-K partial sums (few-tile shapes only)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
     with torch.cuda.device(x.device), _timed(f"conv3x3/C={cin}/s={stride}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel()):
-        _check(lib().alo_conv3x3_nhwc(_ptr(x), _ptr(hit[1]), None if bias_c is None else _ptr(bias_c), _ptr(y),
+        _check(lib().alo_conv3x3_nhwc(_ptr(x), _ptr(packed), None if bias_c is None else _ptr(bias_c), _ptr(y),
                                       None if ws is None else _ptr(ws), n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16,
                                       _stream(x.device)))
     return y
@@ -1036,25 +1039,21 @@ def stem_conv_pool(x, weight, bias=None):
     if not stem_conv_pool_supported(x, weight):
         raise RuntimeError("stem_conv_pool: needs a bf16 CUDA (N, 3, H, W) image, a (64, 3, 7, 7) bf16 weight, no autograd")
     n, _, h, w_ = x.shape
-    tag = (tensor_version(weight), weight.data_ptr())
-    hit = getattr(weight, "_alo_packed", None)
-    if hit is None or hit[0] != tag:
+
+    def pack():
         # (64, 7 tap rows x 24): per tap row the 7 taps x 3 channels interleaved as the image rows are, then 3 zero columns
         wm = torch.zeros((64, 8, 24), dtype=weight.dtype, device=weight.device)
-        wm[:, :7, :21] = weight.detach().permute(0, 2, 3, 1).reshape(64, 7, 21)
-        wm = wm.reshape(64, 192)[:, :176].contiguous()
-        packed = torch.empty_like(wm)
-        with torch.cuda.device(x.device):
-            _check(lib().alo_pack_mfma_b(_ptr(wm), _ptr(packed), 64, 176, ALO_BF16, _stream(x.device)))
-        hit = (tag, packed)
-        weight._alo_packed = hit
+        wm[:, :7, :21] = weight.permute(0, 2, 3, 1).reshape(64, 7, 21)
+        return _pack_mfma_b(wm.reshape(64, 192)[:, :176].contiguous())
+
+    packed = derived(weight, "stem_b", (weight,), pack)
     hc, wc = (h - 1) // 2 + 1, (w_ - 1) // 2 + 1
     hp, wp = (hc - 1) // 2 + 1, (wc - 1) // 2 + 1
     y = torch.empty((n, 64, hp, wp), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.contiguous()
     sn, sc, sh, sw = x.stride()
     with torch.cuda.device(x.device), _timed("stem_conv_pool", 2.0 * (x.numel() + y.numel()), 2.0 * 147 * 64 * n * hc * wc):
-        _check(lib().alo_stem_conv_pool(_ptr(x), _ptr(hit[1]), None if bias_c is None else _ptr(bias_c), _ptr(y), n, h, w_,
+        _check(lib().alo_stem_conv_pool(_ptr(x), _ptr(packed), None if bias_c is None else _ptr(bias_c), _ptr(y), n, h, w_,
                                         sn, sc, sh, sw, ALO_BF16, _stream(x.device)))
     return y
 
@@ -1108,20 +1107,18 @@ def conv3x3_small_supported(x, conv):
 def _small_conv_operands(conv):
     """(w_frag, bias32) of alo_conv3x3_small_nhwc, cached on the module per weight / bias version."""
     w, b = conv.weight, conv.bias
-    key = (tensor_version(w), w.data_ptr(), None if b is None else (tensor_version(b), b.data_ptr()))
-    hit = conv.__dict__.get("_alo_small_frag")
-    if hit is None or hit[0] != key:
+
+    def build():
         cout, cin = w.shape[:2]
-        with torch.no_grad():
-            full = torch.zeros((32, 3, 3, cin), dtype=w.dtype, device=w.device)
-            full[:cout] = w.detach().permute(0, 2, 3, 1)                                   # (m, ky, kx, c)
-            frag = full.view(32, 9, cin // 16, 2, 8).permute(1, 2, 3, 0, 4).contiguous()   # (tap, cs, kg, m, 8) = [k-step][lane][8]
-            bias32 = torch.zeros(32, dtype=torch.float32, device=w.device)
-            if b is not None:
-                bias32[:cout] = b.detach().float()
-        hit = (key, frag, bias32)
-        conv.__dict__["_alo_small_frag"] = hit
-    return hit[1], hit[2]
+        full = torch.zeros((32, 3, 3, cin), dtype=w.dtype, device=w.device)
+        full[:cout] = w.permute(0, 2, 3, 1)                                            # (m, ky, kx, c)
+        frag = full.view(32, 9, cin // 16, 2, 8).permute(1, 2, 3, 0, 4).contiguous()   # (tap, cs, kg, m, 8) = [k-step][lane][8]
+        bias32 = torch.zeros(32, dtype=torch.float32, device=w.device)
+        if b is not None:
+            bias32[:cout] = b.float()
+        return frag, bias32
+
+    return derived(conv, "small_frag", (w, b), build)
 
 
 def conv3x3_small(x, conv):

@@ -76,14 +76,9 @@ class MSDeformAttn(nn.Module):
     def _merged_query_projection(self):
         """[sampling_offsets; attention_weights] as one (3*M*L*P, C) weight + bias, rebuilt when either parameter changes."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (alo_hip.tensor_version(so.weight), alo_hip.tensor_version(so.bias), alo_hip.tensor_version(aw.weight), alo_hip.tensor_version(aw.bias), so.weight.data_ptr(), aw.weight.data_ptr(),
-               so.weight.dtype, so.weight.device)
-        hit = self.__dict__.get("_alo_merged")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous())
-            self.__dict__["_alo_merged"] = hit
-        return hit[1], hit[2]
+        return alo_hip.derived(self, "merged", (so.weight, so.bias, aw.weight, aw.bias),
+                               lambda: (torch.cat([so.weight, aw.weight], 0).contiguous(),
+                                        torch.cat([so.bias, aw.bias], 0).contiguous()))
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None, **kwargs):

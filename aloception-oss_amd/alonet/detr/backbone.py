@@ -39,14 +39,7 @@ class FrozenBatchNorm2d(nn.Module):
 
 def _weight_2d(weight):
     """(Cout, Cin, 1, 1) -> (Cout, Cin), the SAME view object every call: the packed copy the streaming kernels make rides on it."""
-    w2 = weight.__dict__.get("_alo_2d") if hasattr(weight, "__dict__") else None
-    if w2 is None or alo_hip.tensor_version(w2) != alo_hip.tensor_version(weight) or w2.data_ptr() != weight.data_ptr():
-        w2 = weight.reshape(weight.shape[0], -1)
-        try:
-            weight._alo_2d = w2
-        except AttributeError:
-            pass
-    return w2
+    return alo_hip.derived(weight, "2d", (weight,), lambda: weight.reshape(weight.shape[0], -1), no_grad=False)   # autograd kept
 
 
 def conv1x1_as_gemm(x, weight, bias, stride=(1, 1), relu=False, residual=None):
@@ -71,18 +64,14 @@ def folded_conv_bn(conv, bn):
     """``(w', b')`` with ``bn(conv(x)) == conv'(x)``: ``w' = w * scale[:, None, None, None]`` (channels-last), ``b' = shift``.
     In eval mode the folded tensors are cached (keyed on the parameter versions); in training mode they are rebuilt every
     call so autograd still reaches ``conv.weight``."""
-    key = (conv.weight.data_ptr(), alo_hip.tensor_version(conv.weight), conv.weight.dtype, bn.weight.data_ptr(), alo_hip.tensor_version(bn.weight),
-           alo_hip.tensor_version(bn.running_var), alo_hip.tensor_version(bn.running_mean), alo_hip.tensor_version(bn.bias))
-    cached = conv.__dict__.get("_folded")
-    if conv.training or torch.is_grad_enabled() and conv.weight.requires_grad or cached is None or cached[0] != key:
+    def fold():
         scale, shift = bn.scale_shift()
         w = (conv.weight.float() * scale.float().reshape(-1, 1, 1, 1)).to(conv.weight.dtype)
-        w = w.contiguous(memory_format=torch.channels_last)
-        b = shift.to(conv.weight.dtype)
-        if not conv.training and not (torch.is_grad_enabled() and conv.weight.requires_grad):
-            conv.__dict__["_folded"] = (key, w.detach(), b.detach())
-        return w, b
-    return cached[1], cached[2]
+        return w.contiguous(memory_format=torch.channels_last), shift.to(conv.weight.dtype)
+
+    if conv.training or torch.is_grad_enabled() and conv.weight.requires_grad:
+        return fold()
+    return alo_hip.derived(conv, "folded", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), fold)
 
 
 def conv_bn(x, conv, bn, relu=False, residual=None):

@@ -49,18 +49,17 @@ class FPNstyleCNN(nn.Module):
 
     def _padded_weights(self, lay):
         w, b = lay.weight, lay.bias
-        key = (alo_hip.tensor_version(w), w.data_ptr(), None if b is None else alo_hip.tensor_version(b))
-        hit = lay.__dict__.get("_alo_padded")
-        if hit is None or hit[0] != key:
+
+        def pad():
             cout, cin = w.shape[:2]
             wp = torch.zeros((self._pad64(cout), self._pad64(cin), 3, 3), dtype=w.dtype, device=w.device)
-            wp[:cout, :cin] = w.detach()
+            wp[:cout, :cin] = w
             bp = torch.zeros(self._pad64(cout), dtype=w.dtype, device=w.device)
             if b is not None:
-                bp[:cout] = b.detach()
-            hit = (key, wp.contiguous(memory_format=torch.channels_last), bp)
-            lay.__dict__["_alo_padded"] = hit
-        return hit[1], hit[2]
+                bp[:cout] = b
+            return wp.contiguous(memory_format=torch.channels_last), bp
+
+        return alo_hip.derived(lay, "padded", (w, b), pad)
 
     def _wide_layers_fast(self, x, bbox_mask):
         """relu(gn2(lay2(relu(gn1(lay1(cat(expand(x), bbox_mask))))))) with both convolutions on the implicit-GEMM kernel."""

@@ -26,17 +26,6 @@ def _conv_act(conv, x, relu=True):
     return alo_hip.bias_act_nchw_(out, conv.bias, relu)
 
 
-def _cached(module, name, key_tensors, build):
-    """Derived inference-time tensors (merged / rescaled weights) cached on the module, keyed on parameter versions."""
-    key = tuple((t.data_ptr(), alo_hip.tensor_version(t)) for t in key_tensors)
-    hit = module.__dict__.get(name)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, build())
-        module.__dict__[name] = hit
-    return hit[1]
-
-
 class FlowHead(nn.Module):
     def __init__(self, input_dim=128, hidden_dim=256, out_planes=2):
         super().__init__()
@@ -99,9 +88,9 @@ class SepConvGRU(nn.Module):
         net = torch.empty_like(h)
         halves = ((self.convz1, self.convr1, self.convq1), (self.convz2, self.convr2, self.convq2))
         for i, (cz, cr, cq) in enumerate(halves):
-            wzr, bzr = _cached(self, f"_zr{i}", (cz.weight, cr.weight, cz.bias, cr.bias),
-                               lambda: (torch.cat([cz.weight, cr.weight], 0).contiguous(),
-                                        torch.cat([cz.bias, cr.bias], 0).contiguous()))
+            wzr, bzr = alo_hip.derived(self, f"zr{i}", (cz.weight, cr.weight, cz.bias, cr.bias),
+                                       lambda: (torch.cat([cz.weight, cr.weight], 0).contiguous(),
+                                                torch.cat([cz.bias, cr.bias], 0).contiguous()))
             zr = F.conv2d(hx, wzr, None, cz.stride, cz.padding)
             alo_hip.gru_gate_(zr, bzr, hx, rhx, C)
             q = F.conv2d(rhx, cq.weight, None, cq.stride, cq.padding)
@@ -175,7 +164,7 @@ class BasicUpdateBlock(nn.Module):
             fh, m0, m2 = self.flow_head, self.mask[0], self.mask[2]
             delta_flow = fh.conv2(_conv_act(fh.conv1, net))
             # the 0.25 of the original RAFT (gradient balancing) is folded into the last convolution's weight and bias
-            w2, b2 = _cached(self, "_mask_quarter", (m2.weight, m2.bias), lambda: (0.25 * m2.weight, 0.25 * m2.bias))
+            w2, b2 = alo_hip.derived(self, "mask_quarter", (m2.weight, m2.bias), lambda: (0.25 * m2.weight, 0.25 * m2.bias))
             up_mask = F.conv2d(_conv_act(m0, net), w2, b2, m2.stride, m2.padding)
             return net, up_mask, delta_flow
         delta_flow = self.flow_head(net)

@@ -279,7 +279,11 @@ def test_conv3x3_input_proj_without_workspace():
     x, wt, b = _conv_operands(n, cin, cout, h, w, seed=7)
     got_z = _run_conv(x, wt, b, False, stride)
     check_conv3x3(x, wt, b, False, stride, got_z, "conv3x3 split-K z = 8")
-    packed = wt._alo_packed[1]   # packed by the call above
+
+    def never():
+        raise AssertionError("the conv3x3 call above left no packed weight on wt")
+
+    packed = alo_hip.derived(wt, "conv3x3_b", (wt,), never)   # packed by the call above: a hit, the operand as the wrapper left it
     got_1 = torch.empty_like(got_z)
     with torch.cuda.device(x.device):
         rc = alo_hip.lib().alo_conv3x3_nhwc(x.data_ptr(), packed.data_ptr(), b.data_ptr(), got_1.data_ptr(), None, n, h, w, cin,

@@ -146,15 +146,174 @@ def test_joiner_skips_requested_positional_encodings():
 
 
 def test_cached_derived_weights_follow_parameter_updates():
-    from alonet.raft.update import _cached
+    from alo_hip import derived
 
     lin = torch.nn.Linear(3, 2)
-    first = _cached(lin, "_double", (lin.weight,), lambda: 2 * lin.weight)
-    assert _cached(lin, "_double", (lin.weight,), lambda: 2 * lin.weight) is first
+    first = derived(lin, "double", (lin.weight,), lambda: 2 * lin.weight)
+    assert derived(lin, "double", (lin.weight,), lambda: 2 * lin.weight) is first
     with torch.no_grad():
         lin.weight.add_(1.0)  # in-place update bumps the version counter
-    second = _cached(lin, "_double", (lin.weight,), lambda: 2 * lin.weight)
+    second = derived(lin, "double", (lin.weight,), lambda: 2 * lin.weight)
     assert second is not first and torch.equal(second, 2 * lin.weight)
+
+
+def _derived_store(owner):
+    """The entries alo_hip.derived keeps on ``owner`` (empty when there are none)."""
+    import alo_hip
+
+    return owner.__dict__.get(alo_hip._DERIVED, {})
+
+
+def test_derived_key_covers_version_pointer_dtype_and_an_absent_bias():
+    """Every way a source can change under an entry forces a rebuild; with nothing changed the very same object comes back."""
+    from alo_hip import derived
+
+    lin = torch.nn.Linear(3, 2, bias=False)
+    builds = []
+
+    def get():
+        def build():
+            builds.append(1)
+            return 2 * lin.weight if lin.bias is None else 2 * lin.weight + lin.bias[:, None]
+
+        return derived(lin, "double", (lin.weight, lin.bias), build)
+
+    def settled():
+        value = get()
+        n = len(builds)
+        assert get() is value and len(builds) == n   # unchanged sources: a hit
+        return value
+
+    seen = [settled()]
+    with torch.no_grad():
+        lin.weight.add_(1.0)                                        # version
+    seen.append(settled())
+    assert torch.equal(seen[-1], 2 * lin.weight)
+    version, pointer = lin.weight._version, lin.weight.data_ptr()
+    lin.weight.data = torch.full_like(lin.weight, 3.0)              # pointer alone: same shape, dtype and version counter
+    assert lin.weight._version == version and lin.weight.data_ptr() != pointer
+    seen.append(settled())
+    assert torch.equal(seen[-1], torch.full((2, 3), 6.0))
+    lin.to(torch.float64)                                           # dtype
+    seen.append(settled())
+    assert seen[-1].dtype == torch.float64
+    lin.bias = torch.nn.Parameter(torch.ones(2, dtype=torch.float64))   # a bias that was None
+    seen.append(settled())
+    assert torch.equal(seen[-1], torch.full((2, 3), 7.0, dtype=torch.float64))
+    assert len(builds) == 5 and len({id(v) for v in seen}) == 5
+    # dtype on its own: a reinterpreting view shares pointer and version counter with its base
+    base = torch.zeros(4)
+    as_int = base.view(torch.int32)
+    assert as_int.data_ptr() == base.data_ptr() and as_int._version == base._version
+    owner = torch.nn.Identity()
+    a = derived(owner, "x", (base,), lambda: torch.zeros(1))
+    assert derived(owner, "x", (as_int,), lambda: torch.ones(1)) is not a
+
+
+def test_derived_from_an_inference_tensor_is_rebuilt_on_every_call(monkeypatch):
+    import warnings
+
+    import alo_hip
+
+    with torch.inference_mode():
+        src = torch.ones(3)
+    owner, builds = torch.nn.Identity(), []
+
+    def build():
+        builds.append(1)
+        return 2 * src
+
+    monkeypatch.setattr(alo_hip, "_warned_inference_tensor", False)
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        got = [alo_hip.derived(owner, "double", (src,), build) for _ in range(3)]
+    assert len(builds) == 3 and len({id(g) for g in got}) == 3 and all(torch.equal(g, 2 * src) for g in got)
+    assert len([w for w in seen if "inference_mode" in str(w.message)]) == 1
+
+
+def test_invalidate_caches_removes_derived_entries_and_nothing_else():
+    import gc
+    import weakref
+
+    import alo_hip
+
+    root = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
+    lin, mean = root[0], root[1].running_mean
+    lin._alo_lean_bb_outputs = True    # a per-call hand-off flag of the models: not a cache
+    merged = alo_hip.derived(lin, "merged", (lin.weight, lin.bias), lambda: 2 * lin.weight)          # on a module
+    alo_hip.derived(merged, "mfma_b", (merged,), lambda: merged + 1)                                  # on a derived tensor
+    alo_hip.derived(lin.weight, "mfma_b", (lin.weight,), lambda: lin.weight + 1)                      # on a parameter
+    alo_hip.derived(mean, "half", (mean,), lambda: mean / 2)                                          # on a buffer
+    alo_hip.derived(root, "sum", (lin.weight, mean), lambda: lin.weight.sum() + mean.sum())           # on the root itself
+    owners = (root, lin, lin.weight, mean)
+    assert all(len(_derived_store(o)) == 1 for o in owners) and len(_derived_store(merged)) == 1
+    alive, epoch = weakref.ref(merged), alo_hip.cache_epoch(root)
+    del merged
+    alo_hip.invalidate_caches(root)
+    assert all(alo_hip._DERIVED not in o.__dict__ for o in owners)
+    gc.collect()
+    assert alive() is None             # the derived tensor went with its owner's store, and its own entry with it
+    assert alo_hip.cache_epoch(root) == epoch + 1
+    assert lin._alo_lean_bb_outputs is True
+
+
+def test_derived_names_on_one_owner_do_not_collide():
+    from alo_hip import derived
+
+    lin = torch.nn.Linear(3, 2)
+    for _ in range(2):
+        double = derived(lin.weight, "double", (lin.weight,), lambda: 2 * lin.weight)
+        triple = derived(lin.weight, "triple", (lin.weight,), lambda: 3 * lin.weight)
+        assert double is not triple and torch.equal(double, 2 * lin.weight) and torch.equal(triple, 3 * lin.weight)
+    assert derived(lin.weight, "double", (lin.weight,), lambda: None) is double
+    assert derived(lin.weight, "triple", (lin.weight,), lambda: None) is triple
+    assert set(_derived_store(lin.weight)) == {"double", "triple"}
+
+
+def test_folded_conv_bn_bypasses_the_cache_while_autograd_reaches_the_weight():
+    from alonet.detr.backbone import FrozenBatchNorm2d, folded_conv_bn
+
+    gen = torch.Generator().manual_seed(3)
+    conv, bn = torch.nn.Conv2d(3, 4, 3, bias=False), FrozenBatchNorm2d(4)
+    bn.weight.copy_(torch.rand(4, generator=gen) + 0.5)
+    bn.running_var.copy_(torch.rand(4, generator=gen) + 0.5)
+    bn.running_mean.copy_(torch.randn(4, generator=gen))
+    for mode in (conv.train, conv.eval):   # eval with a trainable weight under autograd is still a training step of some caller
+        mode()
+        (w1, b1), (w2, b2) = folded_conv_bn(conv, bn), folded_conv_bn(conv, bn)
+        assert w1 is not w2 and b1 is not b2 and w1.grad_fn is not None
+        (g,) = torch.autograd.grad(w1.sum(), conv.weight)
+        assert g.abs().sum() > 0
+        assert not _derived_store(conv)
+    with torch.no_grad():
+        conv.train()
+        assert folded_conv_bn(conv, bn)[0] is not folded_conv_bn(conv, bn)[0] and not _derived_store(conv)
+        conv.eval()
+        (w1, b1), (w2, b2) = folded_conv_bn(conv, bn), folded_conv_bn(conv, bn)
+    assert w1 is w2 and b1 is b2 and not w1.requires_grad and list(_derived_store(conv)) == ["folded"]
+    scale, shift = bn.scale_shift()
+    assert torch.equal(w1, (conv.weight * scale.reshape(-1, 1, 1, 1)).detach()) and torch.equal(b1, shift)
+    assert w1.is_contiguous(memory_format=torch.channels_last)
+
+
+def test_module_holding_derived_entries_pickles_and_deep_copies():
+    import copy
+    import pickle
+
+    from alo_hip import derived
+
+    lin = torch.nn.Linear(3, 2)
+    double = derived(lin, "double", (lin.weight,), lambda: 2 * lin.weight)
+    derived(lin.weight, "mfma_b", (lin.weight,), lambda: lin.weight + 1)
+    derived(double, "mfma_b", (double,), lambda: double + 1)
+    for clone in (copy.deepcopy(lin), pickle.loads(pickle.dumps(lin))):
+        assert torch.equal(clone.weight, lin.weight) and clone.weight.data_ptr() != lin.weight.data_ptr()
+        with torch.no_grad():
+            clone.weight.data.mul_(2.0)   # through .data: no version bump, so only the copy's own pointer can force the rebuild
+        builds = []
+        got = derived(clone, "double", (clone.weight,), lambda: builds.append(1) or 2 * clone.weight)
+        assert builds == [1] and torch.equal(got, 4 * lin.weight)
+    assert derived(lin, "double", (lin.weight,), lambda: None) is double
 
 
 # ---- round 2: API surface completed, advisor findings -----------------------------------------------------------------
@@ -311,10 +470,11 @@ def test_add_layernorm_support_gate_and_cache_invalidation():
     assert not alo_hip.add_layernorm_supported(torch.zeros(4, 1280))  # above the kernel's 1024-channel rows
     assert not alo_hip.add_layernorm_supported(torch.zeros(4, 30, dtype=torch.bfloat16))
     lin = torch.nn.Linear(4, 4)
-    lin.weight._alo_packed = ("tag", torch.zeros(1))
-    lin.__dict__["_alo_merged"] = ("key", None)
+    alo_hip.derived(lin, "merged", (lin.weight, lin.bias), lambda: lin.weight + lin.bias)
+    alo_hip.derived(lin.weight, "mfma_b", (lin.weight,), lambda: torch.zeros(1))
+    assert list(_derived_store(lin)) == ["merged"] and list(_derived_store(lin.weight)) == ["mfma_b"]
     alo_hip.invalidate_caches(lin)
-    assert not hasattr(lin.weight, "_alo_packed") and "_alo_merged" not in lin.__dict__
+    assert alo_hip._DERIVED not in lin.__dict__ and alo_hip._DERIVED not in lin.weight.__dict__
 
 
 def test_cache_keys_do_not_read_version_counters_of_inference_tensors():
@@ -347,7 +507,7 @@ def test_cache_keys_do_not_read_version_counters_of_inference_tensors():
     pkg = os.path.dirname(os.path.dirname(alo_hip.__file__))
     for path in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
         src = "\n".join(ln for ln in open(path).read().splitlines()
-                        if "else t._version" not in ln and "``(tensor._version" not in ln and "``t._version``" not in ln)
+                        if "return t._version" not in ln and "``(tensor._version" not in ln and "``t._version``" not in ln)
         if path.endswith(os.path.join("deformable_detr", "deformable_detr.py")):
             continue   # its two reads are guarded by is_inference() (the packed detections)
         assert "._version" not in src, path
