@@ -518,11 +518,15 @@ def _host_spatial_shapes(spatial_shapes, read=True):
     return host
 
 
-def _tiled_backward_eligible(value, dims, ldt):
-    """The launches msda_bwd_wide_kernel covers (csrc/msda_bwd_wide.hip): fp32 / bf16 values, D = 32 or 64, L = P = 4, queries = the
-    pyramid's own pixels.  Only then is the host copy of the shapes worth a device-to-host read."""
+def _wide_backward_wants_host_shapes(value, dims, ldt):
+    """Whether a host copy of the shapes is worth a device-to-host read: the launches msda_bwd_wide_kernel can take once it has
+    one (fp32 / bf16 values, D = 32 or 64, L = P = 4, queries = the pyramid's own pixels).  The library decides the route
+    (csrc/msda.hip plan_backward) but needs the host shapes to do so, hence this pre-filter; tests/test_cabi.py holds the two together."""
     N, S, M, D, L, Lq, P = dims
     return value.dtype in (torch.float32, torch.bfloat16) and ldt == ALO_F32 and D in (32, 64) and L == 4 and P == 4 and Lq == S
+
+
+_tiled_backward_eligible = _wide_backward_wants_host_shapes   # the helper's earlier name (it never described the tiled kernel): kept for callers
 
 
 def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step=64):
@@ -537,8 +541,8 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     grad_loc = torch.empty(loc.shape, dtype=gdt, device=value.device)
     grad_attn = torch.empty(attn.shape, dtype=gdt, device=value.device)
     nbytes = msda_backward_bytes(N, S, M, D, L, Lq, P, value.element_size(), loc.element_size())
-    # only the encoder's self-attention on the DETR-family shape can use the hint (it sizes the grid of 4x4 query tiles)
-    host = _host_spatial_shapes(spatial_shapes) if _tiled_backward_eligible(value, dims, ldt) else None
+    # only the encoder's self-attention on the DETR-family shape can use the hint (it sizes the grid of query blocks)
+    host = _host_spatial_shapes(spatial_shapes) if _wide_backward_wants_host_shapes(value, dims, ldt) else None
     hint = None if host is None else (ctypes.c_int32 * (2 * L))(*[int(v) for hw in host for v in hw])
 
     def launch():

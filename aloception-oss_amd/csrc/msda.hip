@@ -1576,24 +1576,23 @@ msda_bwd_tiled_kernel(const float* __restrict__ value, const int32_t* __restrict
 // ------------------------------------------------------------------------------------------------------------------
 // host dispatch
 // ------------------------------------------------------------------------------------------------------------------
+struct Shape {
+    int N, S, M, D, L, Lq, P, value_dtype;
+    size_t elem() const { return value_dtype == ALO_F64 ? 8 : (value_dtype == ALO_F32 ? 4 : 2); }
+};
+
 struct Plan {
     int vec, g;
     bool lp16;
 };
-
-inline int pick_group(int lanes_needed) {
-    static const int kGroups[] = {4, 8, 16, 64};
-    for (int g : kGroups)
-        if (lanes_needed <= g) return g;
-    return 64;
-}
 
 Plan make_plan(int D, int L, int P, size_t elem, bool aligned16) {
     Plan p;
     const int vec = (int)(16 / elem);
     if (aligned16 && D % vec == 0) {
         p.vec = vec;
-        p.g = pick_group(D / vec);
+        const int lanes = D / vec;
+        p.g = lanes <= 4 ? 4 : (lanes <= 8 ? 8 : (lanes <= 16 ? 16 : 64));
     } else {
         p.vec = 1;
         p.g = D <= 8 ? 8 : 64;
@@ -1602,18 +1601,18 @@ Plan make_plan(int D, int L, int P, size_t elem, bool aligned16) {
     return p;
 }
 
-Dims make_dims(int N, int S, int M, int D, int L, int Lq, int P, int G, long target_blocks = 4096) {
+Dims make_dims(const Shape& s, int G, long target_blocks = 4096) {
     Dims d;
-    d.S = S; d.M = M; d.D = D; d.L = L; d.P = P;
-    d.pairs_per_batch = Lq * M;
+    d.S = s.S; d.M = s.M; d.D = s.D; d.L = s.L; d.P = s.P;
+    d.pairs_per_batch = s.Lq * s.M;
     d.ref_dim = 0;
-    d.loc_row_elems = M * L * P * 2;
-    d.attn_row_elems = M * L * P;
-    d.p_shift = (P & (P - 1)) == 0 ? __builtin_ctz((unsigned)P) : -1;
-    d.m_shift = (M & (M - 1)) == 0 ? __builtin_ctz((unsigned)M) : -1;
+    d.loc_row_elems = s.M * s.L * s.P * 2;
+    d.attn_row_elems = s.M * s.L * s.P;
+    d.p_shift = (s.P & (s.P - 1)) == 0 ? __builtin_ctz((unsigned)s.P) : -1;
+    d.m_shift = (s.M & (s.M - 1)) == 0 ? __builtin_ctz((unsigned)s.M) : -1;
     const int pairs = kThreads / G;
     const long iters_total = ((long)d.pairs_per_batch + pairs - 1) / pairs;
-    long ipb = iters_total * N / target_blocks;  // keep >= ~4096 workgroups of 4 waves in flight when the problem allows it
+    long ipb = iters_total * s.N / target_blocks;  // keep >= ~4096 workgroups of 4 waves in flight when the problem allows it
     if (ipb < 1) ipb = 1;
     if (ipb > 4) ipb = 4;   // workgroups in flight sweep the image in query order: the shorter their shares, the narrower the band of rows
                             // the L2 has to hold (8 -> 4: fp32 survey 0.497 -> 0.473 ms, plain head-major 0.224 -> 0.216; 2 and 1 lose to
@@ -1621,35 +1620,38 @@ Dims make_dims(int N, int S, int M, int D, int L, int Lq, int P, int G, long tar
     d.iters_per_block = (int)ipb;
     d.runs_per_batch = (int)iters_total;
     d.blocks_per_batch = (int)((iters_total + ipb - 1) / ipb);
-    d.nblocks = (unsigned)(d.blocks_per_batch * N);
+    d.nblocks = (unsigned)(d.blocks_per_batch * s.N);
     return d;
 }
 
-template <typename K>
-int launch(K kernel, const Dims& dm, size_t lds, hipStream_t stream, const char* what, void** args, int threads = kThreads) {
-    if (lds > 160 * 1024) return fail(ALO_ERR_UNSUPPORTED, "%s: L*P too large for LDS (%zu bytes)", what, lds);
+// The one launch path of this file.  A launch that asks for more than 48 KiB of dynamic LDS raises the kernel's limit to the whole
+// LDS first, once per (kernel, device).
+constexpr int kLdsLimit = 160 * 1024;
+template <auto kernel>
+int launch(unsigned nblocks, int threads, size_t lds, hipStream_t stream, const char* what, void** args) {
+    if (lds > (size_t)kLdsLimit) return fail(ALO_ERR_UNSUPPORTED, "%s: L*P too large for LDS (%zu bytes)", what, lds);
+    const void* fn = reinterpret_cast<const void*>(kernel);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static unsigned long long attr_done = 0;   // one bit per device
+        hipError_t e = ensure_dynamic_lds(fn, kLdsLimit, &attr_done);
         if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     }
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(dm.nblocks), dim3(threads), args, lds,
-                                   stream);
+    hipError_t e = hipLaunchKernel(fn, dim3(nblocks), dim3(threads), args, lds, stream);
     if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     return check_launch(what);
 }
 
 #define ALO_FWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
-    if (plan.vec == VEC && plan.g == G && plan.lp16 == (LPCT == 16)) {                                             \
-        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)L * P * sizeof(FwdDesc<CT>) + 16);       \
+    if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
+        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(FwdDesc<CT>) + 16); \
         if (fused)                                                                                                 \
-            return launch(msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), true>, dm, lds, stream, "alo_msda_forward_fused", args); \
-        return launch(msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), false>, dm, lds, stream, "alo_msda_forward", args);     \
+            return launch<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), true>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_forward_fused", args); \
+        return launch<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), false>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_forward", args);     \
     }
 #define ALO_BWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
-    if (plan.vec == VEC && plan.g == G && plan.lp16 == (LPCT == 16)) {                                             \
-        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)L * P * sizeof(BwdDesc<CT>) + 16);       \
-        return launch(msda_bwd_kernel<T, LT, CT, VEC, G, LPCT>, dm, lds, stream, "alo_msda_backward", args);       \
+    if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
+        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(BwdDesc<CT>) + 16); \
+        return launch<msda_bwd_kernel<T, LT, CT, VEC, G, LPCT>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_backward", args); \
     }
 // every (vector width, group) pair a plan can produce for one dtype
 #define ALO_ALL_CASES(CASE, T, LT, CT, VECW)                                                       \
@@ -1657,20 +1659,157 @@ int launch(K kernel, const Dims& dm, size_t lds, hipStream_t stream, const char*
     CASE(T, LT, CT, VECW, 4, 0) CASE(T, LT, CT, VECW, 8, 0) CASE(T, LT, CT, VECW, 16, 0)            \
     CASE(T, LT, CT, VECW, 64, 0) CASE(T, LT, CT, 1, 8, 0) CASE(T, LT, CT, 1, 32, 0) CASE(T, LT, CT, 1, 64, 0)
 
-int validate(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
-             int N, int S, int M, int D, int L, int Lq, int P, int vdt, int ldt, size_t* elem_out) {
-    ALO_REQUIRE(value && shapes && lstart && loc && attn, ALO_ERR_INVALID_ARGUMENT, "msda: null pointer argument");
+// What the library accepts at all, pointers aside.  The path queries ask this too, so they never name a kernel for a refused launch.
+int validate(const Shape& s, int ldt) {
+    const auto [N, S, M, D, L, Lq, P, vdt] = s;
     ALO_REQUIRE(N > 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq > 0 && P > 0, ALO_ERR_INVALID_ARGUMENT,
                 "msda: dimensions must be positive (N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d)", N, S, M, D, L, Lq, P);
     ALO_REQUIRE(L <= kMaxLevels, ALO_ERR_UNSUPPORTED, "msda: at most %d levels are supported, got %d", kMaxLevels, L);
-    const bool ok = (vdt == ALO_F32 && ldt == ALO_F32) || (vdt == ALO_F64 && ldt == ALO_F64) ||
-                    (vdt == ALO_BF16 && ldt == ALO_F32);
-    ALO_REQUIRE(ok, ALO_ERR_UNSUPPORTED, "msda: unsupported dtype pair (value=%d, loc=%d)", vdt, ldt);
-    const size_t elem = vdt == ALO_F64 ? 8 : (vdt == ALO_F32 ? 4 : 2);
-    ALO_REQUIRE((double)S * M * D * elem < 3.0 * 1024 * 1024 * 1024, ALO_ERR_UNSUPPORTED,
+    ALO_REQUIRE((vdt == ALO_F32 && ldt == ALO_F32) || (vdt == ALO_F64 && ldt == ALO_F64) || (vdt == ALO_BF16 && ldt == ALO_F32),
+                ALO_ERR_UNSUPPORTED, "msda: unsupported dtype pair (value=%d, loc=%d)", vdt, ldt);
+    ALO_REQUIRE((double)S * M * D * s.elem() < 3.0 * 1024 * 1024 * 1024, ALO_ERR_UNSUPPORTED,
                 "msda: one batch item of value must stay below 3 GiB");
     ALO_REQUIRE((double)Lq * M < 2.0e9 && (double)Lq * M * L * P < 9.0e18, ALO_ERR_UNSUPPORTED, "msda: Lq*M too large");
-    *elem_out = elem;
+    return ALO_OK;
+}
+
+// Whether msda_fwd_bf16_resident_kernel serves a launch (levels 2 and 3 of every slab resident in LDS), from the HOST's copy of the
+// shapes; fills `rd` when it does.
+// policy ALO_RESIDENT_AUTO: only where the resident kernel is the faster one; ALO_RESIDENT_ALWAYS: wherever it can run.
+bool resident_plan(const int32_t* host_shapes, const Shape& s, int policy, ResDims* rd) {
+    const int S = s.S, Lq = s.Lq;
+    if (s.L != 4) return false;
+    long start[5] = {0, 0, 0, 0, 0};
+    for (int l = 0; l < 4; ++l) {
+        const long h = host_shapes[2 * l], w = host_shapes[2 * l + 1];
+        if (h <= 0 || w <= 0 || h * (w * 64 + kResRowPad) / kResRowPad >= (1L << 23)) return false;   // offsets in pad units must stay exact in fp32
+        start[l + 1] = start[l] + h * w;
+    }
+    if (start[4] != S) return false;
+    long bytes = 0;
+    for (int l = 2; l < 4; ++l) bytes += (long)host_shapes[2 * l] * (host_shapes[2 * l + 1] * 64L + kResRowPad);
+    // the zero row and the waves' work areas follow the image: keep them 16-byte aligned (the image itself is only 8-byte
+    // granular when H2 + H3 is odd, and the kernel writes its tables with 16-byte stores)
+    bytes = (bytes + 15) & ~15L;
+    if (bytes > kResMaxImage) return false;
+    int cus = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (cus < 1) cus = 256;
+    const long slabs = (long)s.N * s.M;
+    rd->runs_per_slab = (Lq + 15) / 16;
+    // Measured over frame sizes 256 x 320 ... 1333 x 800 and N = 1 ... 8 (tools/exp/res_sweep.py, HIP-graph replay): the resident kernel
+    // beats the plain one as soon as every wave of the chip gets a run (>= CUs x 12 runs in the launch; 0.77-0.86 of the plain kernel's
+    // time from there on, 1.2-1.6 x below), and splitting a slab over more workgroups — down to ONE run per wave — is never slower than
+    // fewer, longer workgroups: the copy of the coarse rows is cheap next to an idle CU.
+    if (policy != ALO_RESIDENT_ALWAYS && slabs * rd->runs_per_slab < (long)cus * kResWaves) return false;
+    long wps = slabs >= cus ? 1 : (cus + slabs - 1) / slabs;
+    const long wps_cap = rd->runs_per_slab / kResWaves;   // at least one run per wave
+    if (wps > wps_cap) wps = wps_cap;
+    if (wps < 1 || slabs * wps >= 0x7fffffffL) return false;
+    rd->res_row0 = (int)start[2];
+    rd->res_rows = (int)(S - start[2]);
+    rd->h[0] = host_shapes[4]; rd->w[0] = host_shapes[5];
+    rd->h[1] = host_shapes[6]; rd->w[1] = host_shapes[7];
+    rd->image_bytes = (int)bytes;
+    rd->wps = (int)wps;
+    rd->runs_per_wg = (int)((rd->runs_per_slab + wps - 1) / wps);
+    return true;
+}
+
+// What an entry point adds to the shape; forward_impl fills in the last three from the pointers.
+struct FwdArgs {
+    int ref_dim = 0;                             // fused prologue only
+    bool head_major = false;
+    long loc_row_elems = 0, attn_row_elems = 0;  // head-major only; 0: dense rows
+    const int32_t* host_shapes = nullptr;        // head-major only; non-null: the resident kernel may serve the launch
+    int resident_policy = ALO_RESIDENT_AUTO;
+    bool fused = false;                          // MSDeformAttn's prologue inside the kernel (reference_points given)
+    bool aligned = false, in_aligned = false;    // value and out on 16 bytes; loc, attn and ref too
+};
+
+// Forward routes.  NONE: head-major asked for a launch the wave kernel does not take; GENERIC: the msda_fwd_kernel that `plan` names;
+// WAVE / WAVE_HM: msda_fwd_bf16_mfma_kernel on a pixel-major / head-major value; RESIDENT: msda_fwd_bf16_resident_kernel, with `rd`.
+enum FwdRoute { FWD_NONE, FWD_GENERIC, FWD_WAVE, FWD_WAVE_HM, FWD_RESIDENT };
+
+// What a plan hands to the launch: the route and the dims of the kernel it names.
+struct LaunchPlan {
+    int route;     // forward: FwdRoute; backward: ALO_MSDA_BWD_*, or -1 when the grid would be too large
+    Plan plan;     // generic kernels
+    Dims dm;       // every kernel but the tiled and the wide backward
+    ResDims rd;    // resident forward
+    TileDims td;   // tiled backward
+};
+
+// Pure host logic: which forward kernel a launch takes and that kernel's dims.  forward_impl launches what this says,
+// alo_msda_resident_levels reports it.
+LaunchPlan plan_forward(const Shape& s, const FwdArgs& a) {
+    const auto [N, S, M, D, L, Lq, P, vdt] = s;
+    LaunchPlan fp;
+    fp.plan = make_plan(D, L, P, s.elem(), a.aligned);
+    // bf16 rows go to the matrix pipe untouched, one wave per 16 pairs (see msda_fwd_bf16_mfma_kernel)
+    const bool wave = vdt == ALO_BF16 && a.aligned && a.in_aligned && L == 4 && P == 4 && D % 8 == 0 && D <= 32 &&
+                      (size_t)M * D * 2 < (1u << 23) && S < (1 << 23);
+    fp.route = a.head_major ? (wave && a.fused ? FWD_WAVE_HM : FWD_NONE) : (wave ? FWD_WAVE : FWD_GENERIC);
+    Dims& dm = fp.dm;
+    dm = wave ? make_dims(s, 16, 16384) : make_dims(s, fp.plan.g);
+    dm.ref_dim = a.ref_dim;
+    if (fp.route != FWD_WAVE_HM) return fp;
+    if (a.loc_row_elems > 0) dm.loc_row_elems = (int)a.loc_row_elems;
+    if (a.attn_row_elems > 0) dm.attn_row_elems = (int)a.attn_row_elems;
+    // runs are (16 consecutive queries, head) tiles; heads of one query block stay on neighbouring waves
+    const long runs = (long)((Lq + 15) / 16) * M;
+    dm.runs_per_batch = (int)runs;
+    dm.blocks_per_batch = (int)((runs + dm.iters_per_block - 1) / dm.iters_per_block);
+    dm.nblocks = (unsigned)(dm.blocks_per_batch * N);
+    const bool offs32 = (double)Lq * dm.loc_row_elems < 4.0e9 && (double)Lq * dm.attn_row_elems < 4.0e9 &&
+                        (double)Lq * M * 32 < 4.0e9 && (double)Lq * 4 * a.ref_dim < 4.0e9;   // 32-bit element offsets per image
+    if (a.host_shapes && D == 32 && offs32 && resident_plan(a.host_shapes, s, a.resident_policy, &fp.rd)) {
+        // coarse levels resident in LDS: one 12-wave workgroup per CU pinned to an (image, head) slab
+        fp.route = FWD_RESIDENT;
+        dm.nblocks = (unsigned)((long)N * M * fp.rd.wps);
+    }
+    return fp;
+}
+
+int forward_impl(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index, const void* loc, const void* attn,
+                 const void* ref, void* out, const Shape& s, int loc_dtype, void* stream_, FwdArgs a) {
+    ALO_REQUIRE(value && spatial_shapes && level_start_index && loc && attn, ALO_ERR_INVALID_ARGUMENT, "msda: null pointer argument");
+    if (int rc = validate(s, loc_dtype)) return rc;
+    ALO_REQUIRE(out, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward: out is null");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const bool fused = a.fused = ref != nullptr;
+    a.aligned = (((uintptr_t)value | (uintptr_t)out) & 15) == 0;
+    a.in_aligned = (((uintptr_t)loc | (uintptr_t)attn | (uintptr_t)ref) & 15) == 0;
+    LaunchPlan lp = plan_forward(s, a);
+    const unsigned nblocks = lp.dm.nblocks;
+    void* args[] = {&value, &spatial_shapes, &level_start_index, &loc, &attn, &ref, &out, &lp.dm, &lp.rd};   // rd: resident kernel only
+    switch ((FwdRoute)lp.route) {
+    case FWD_NONE:
+        return fail(ALO_ERR_UNSUPPORTED,
+                    "alo_msda_forward_fused_hm: needs bf16, L = P = 4, D %% 8 == 0, D <= 32 and 16-byte aligned pointers");
+    case FWD_RESIDENT:
+        return launch<msda_fwd_bf16_resident_kernel>(nblocks, kResThreads, (size_t)lp.rd.image_bytes + kResFixed + kResWaves * kResWaveLds,
+                                                     stream, "alo_msda_forward_fused_hm_resident", args);
+    case FWD_WAVE_HM:
+        return launch<msda_fwd_bf16_mfma_kernel<4, true, true>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused_hm", args);
+    case FWD_WAVE:
+        if (fused) return launch<msda_fwd_bf16_mfma_kernel<4, true, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused", args);
+        return launch<msda_fwd_bf16_mfma_kernel<4, false, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward", args);
+    case FWD_GENERIC:;
+    }
+    if (s.value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_FWD_CASE, float, float, float, 4) }
+    if (s.value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_FWD_CASE, double, double, double, 2) }
+    if (s.value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_FWD_CASE, bf16_t, float, float, 8) }
+    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_forward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
+}
+
+// The argument checks the fused entry points share; `rows` = {offsets_row_elems, logits_row_elems} where the entry point takes them.
+int check_fused_args(const char* fn, const void* reference_points, int ref_dim, const Shape& s, const long* rows = nullptr) {
+    ALO_REQUIRE(reference_points, ALO_ERR_INVALID_ARGUMENT, "%s: reference_points is null", fn);
+    ALO_REQUIRE(ref_dim == 2 || ref_dim == 4, ALO_ERR_INVALID_ARGUMENT, "%s: last dim of reference_points must be 2 or 4, got %d", fn, ref_dim);
+    const long mlp = (long)s.M * s.L * s.P;
+    ALO_REQUIRE(!rows || (rows[0] >= mlp * 2 && rows[1] >= mlp && rows[0] % 8 == 0 && rows[1] % 8 == 0 && rows[0] < (1L << 30) && rows[1] < (1L << 30)),
+                ALO_ERR_INVALID_ARGUMENT, "%s: row strides must cover a query's M*L*P*2 offsets / M*L*P logits and keep 16-byte alignment", fn);
     return ALO_OK;
 }
 
@@ -1679,234 +1818,99 @@ int validate(const void* value, const int32_t* shapes, const int32_t* lstart, co
 
 using namespace alo;
 
-namespace {
-// Whether msda_fwd_bf16_resident_kernel serves a launch (levels 2 and 3 of every slab resident in LDS), from the HOST's copy of the
-// shapes: returns 2 (the first resident level) or 0 (the plain head-major kernel serves the launch).  Fills `rd` when non-zero.
-// policy ALO_RESIDENT_AUTO: only where the resident kernel is the faster one; ALO_RESIDENT_ALWAYS: wherever it can run.
-int resident_plan(const int32_t* host_shapes, int N, int S, int M, int L, int Lq, int policy, ResDims* rd) {
-    if (L != 4) return 0;
-    long start[5] = {0, 0, 0, 0, 0};
-    for (int l = 0; l < 4; ++l) {
-        const long h = host_shapes[2 * l], w = host_shapes[2 * l + 1];
-        if (h <= 0 || w <= 0 || h * (w * 64 + kResRowPad) / kResRowPad >= (1L << 23)) return 0;   // offsets in pad units must stay exact in fp32
-        start[l + 1] = start[l] + h * w;
-    }
-    if (start[4] != S) return 0;
-    long bytes = 0;
-    for (int l = 2; l < 4; ++l) bytes += (long)host_shapes[2 * l] * (host_shapes[2 * l + 1] * 64L + kResRowPad);
-    // the zero row and the waves' work areas follow the image: keep them 16-byte aligned (the image itself is only 8-byte
-    // granular when H2 + H3 is odd, and the kernel writes its tables with 16-byte stores)
-    bytes = (bytes + 15) & ~15L;
-    if (bytes > kResMaxImage) return 0;
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus < 1) cus = 256;
-    const long slabs = (long)N * M;
-    rd->runs_per_slab = (Lq + 15) / 16;
-    // Measured over frame sizes 256 x 320 ... 1333 x 800 and N = 1 ... 8 (tools/exp/res_sweep.py, HIP-graph replay): the resident kernel
-    // beats the plain one as soon as every wave of the chip gets a run (>= CUs x 12 runs in the launch; 0.77-0.86 of the plain kernel's
-    // time from there on, 1.2-1.6 x below), and splitting a slab over more workgroups — down to ONE run per wave — is never slower than
-    // fewer, longer workgroups: the copy of the coarse rows is cheap next to an idle CU.
-    if (policy != ALO_RESIDENT_ALWAYS && slabs * rd->runs_per_slab < (long)cus * kResWaves) return 0;
-    long wps = slabs >= cus ? 1 : (cus + slabs - 1) / slabs;
-    const long wps_cap = rd->runs_per_slab / kResWaves;   // at least one run per wave
-    if (wps > wps_cap) wps = wps_cap;
-    if (wps < 1 || slabs * wps >= 0x7fffffffL) return 0;
-    rd->res_row0 = (int)start[2];
-    rd->res_rows = (int)(S - start[2]);
-    rd->h[0] = host_shapes[4]; rd->w[0] = host_shapes[5];
-    rd->h[1] = host_shapes[6]; rd->w[1] = host_shapes[7];
-    rd->image_bytes = (int)bytes;
-    rd->wps = (int)wps;
-    rd->runs_per_wg = (int)((rd->runs_per_slab + wps - 1) / wps);
-    return 2;
+extern "C" int alo_msda_forward(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index, const void* sampling_loc,
+                                const void* attn_weight, void* out, int N, int S, int M, int D, int L, int Lq, int P, int value_dtype,
+                                int loc_dtype, void* stream_) {
+    return forward_impl(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, nullptr, out, {N, S, M, D, L, Lq, P, value_dtype},
+                        loc_dtype, stream_, {});
 }
 
-int forward_impl(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index, const void* loc,
-                 const void* attn, const void* ref, int ref_dim, void* out, int N, int S, int M, int D, int L, int Lq,
-                 int P, int value_dtype, int loc_dtype, void* stream_, bool head_major = false, long loc_row_elems = 0,
-                 long attn_row_elems = 0, const int32_t* host_shapes = nullptr, int resident_policy = ALO_RESIDENT_AUTO) {
-    size_t elem = 0;
-    if (int rc = validate(value, spatial_shapes, level_start_index, loc, attn, N, S, M, D, L, Lq, P, value_dtype,
-                          loc_dtype, &elem))
-        return rc;
-    ALO_REQUIRE(out, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward: out is null");
-    const bool fused = ref != nullptr;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const bool aligned = (((uintptr_t)value | (uintptr_t)out) & 15) == 0;
-    const Plan plan = make_plan(D, L, P, elem, aligned);
-    Dims dm = make_dims(N, S, M, D, L, Lq, P, plan.g);
-    dm.ref_dim = ref_dim;
-    void* args[] = {&value, &spatial_shapes, &level_start_index, &loc, &attn, &ref, &out, &dm};
-    const bool in_aligned = (((uintptr_t)loc | (uintptr_t)attn | (uintptr_t)(fused ? ref : nullptr)) & 15) == 0;
-    const bool wave_kernel = value_dtype == ALO_BF16 && aligned && in_aligned && L == 4 && P == 4 && D % 8 == 0 &&
-                             D <= 32 && (size_t)M * D * 2 < (1u << 23) && S < (1 << 23);
-    if (head_major) {
-        ALO_REQUIRE(wave_kernel && fused, ALO_ERR_UNSUPPORTED,
-                    "alo_msda_forward_fused_hm: needs bf16, L = P = 4, D %% 8 == 0, D <= 32 and 16-byte aligned pointers");
-        dm = make_dims(N, S, M, D, L, Lq, P, 16, 16384);
-        dm.ref_dim = ref_dim;
-        if (loc_row_elems > 0) dm.loc_row_elems = (int)loc_row_elems;
-        if (attn_row_elems > 0) dm.attn_row_elems = (int)attn_row_elems;
-        // runs are (16 consecutive queries, head) tiles; heads of one query block stay on neighbouring waves
-        const long runs = (long)((Lq + 15) / 16) * M;
-        dm.runs_per_batch = (int)runs;
-        dm.blocks_per_batch = (int)((runs + dm.iters_per_block - 1) / dm.iters_per_block);
-        dm.nblocks = (unsigned)(dm.blocks_per_batch * N);
-        ResDims rd;
-        const int rl = host_shapes && D == 32 ? resident_plan(host_shapes, N, S, M, L, Lq, resident_policy, &rd) : 0;
-        const bool offs32 = (double)Lq * dm.loc_row_elems < 4.0e9 && (double)Lq * dm.attn_row_elems < 4.0e9 &&
-                            (double)Lq * M * 32 < 4.0e9 && (double)Lq * 4 * ref_dim < 4.0e9;   // 32-bit element offsets per image
-        if (rl && offs32) {
-            // coarse levels resident in LDS (msda_fwd_bf16_resident_kernel): one 12-wave workgroup per CU pinned to an (image, head) slab
-            dm.nblocks = (unsigned)((long)N * M * rd.wps);
-            void* rargs[] = {&value, &spatial_shapes, &level_start_index, &loc, &attn, &ref, &out, &dm, &rd};
-            const size_t lds = (size_t)rd.image_bytes + kResFixed + (size_t)kResWaves * kResWaveLds;
-            static unsigned long long attr_done = 0;   // one bit per device
-            const void* fn = reinterpret_cast<const void*>(msda_fwd_bf16_resident_kernel);
-            hipError_t ea = ensure_dynamic_lds(fn, kResLdsTotal, &attr_done);
-            if (ea != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_forward_fused_hm_resident: %s", hipGetErrorString(ea));
-            hipError_t el = hipLaunchKernel(fn, dim3(dm.nblocks), dim3(kResThreads), rargs, lds, stream);
-            if (el != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_forward_fused_hm_resident: %s", hipGetErrorString(el));
-            return check_launch("alo_msda_forward_fused_hm_resident");
-        }
-        return launch(msda_fwd_bf16_mfma_kernel<4, true, true>, dm, kWaveLds, stream, "alo_msda_forward_fused_hm", args, 64);
-    }
-    if (wave_kernel) {
-        // bf16 rows go to the matrix pipe untouched, one wave per 16 pairs (see msda_fwd_bf16_mfma_kernel)
-        dm = make_dims(N, S, M, D, L, Lq, P, 16, 16384);
-        dm.ref_dim = ref_dim;
-        const char* what = fused ? "alo_msda_forward_fused" : "alo_msda_forward";
-        if (fused) {
-            return launch(msda_fwd_bf16_mfma_kernel<4, true, false>, dm, kWaveLds, stream, what, args, 64);
-        }
-        return launch(msda_fwd_bf16_mfma_kernel<4, false, false>, dm, kWaveLds, stream, what, args, 64);
-    }
-    if (value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_FWD_CASE, float, float, float, 4) }
-    if (value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_FWD_CASE, double, double, double, 2) }
-    if (value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_FWD_CASE, bf16_t, float, float, 8) }
-    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_forward: no kernel for vec=%d group=%d", plan.vec, plan.g);
-}
-}  // namespace
-
-extern "C" int alo_msda_forward(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
-                                const void* sampling_loc, const void* attn_weight, void* out, int N, int S, int M,
-                                int D, int L, int Lq, int P, int value_dtype, int loc_dtype, void* stream_) {
-    return forward_impl(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, nullptr, 0, out, N, S, M, D,
-                        L, Lq, P, value_dtype, loc_dtype, stream_);
-}
-
-extern "C" int alo_msda_forward_fused(const void* value, const int32_t* spatial_shapes,
-                                      const int32_t* level_start_index, const void* sampling_offsets,
-                                      const void* attn_logits, const void* reference_points, void* out, int N, int S,
-                                      int M, int D, int L, int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
-    ALO_REQUIRE(reference_points, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward_fused: reference_points is null");
-    ALO_REQUIRE(ref_dim == 2 || ref_dim == 4, ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused: last dim of reference_points must be 2 or 4, got %d", ref_dim);
+extern "C" int alo_msda_forward_fused(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                                      const void* sampling_offsets, const void* attn_logits, const void* reference_points, void* out, int N,
+                                      int S, int M, int D, int L, int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    if (int rc = check_fused_args("alo_msda_forward_fused", reference_points, ref_dim, s)) return rc;
     // the geometry dtype is implied: fp64 for fp64 values, fp32 otherwise (loc_dtype only steers validation here)
     const int loc_dtype = value_dtype == ALO_F64 ? ALO_F64 : ALO_F32;
-    return forward_impl(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
-                        ref_dim, out, N, S, M, D, L, Lq, P, value_dtype, loc_dtype, stream_);
+    return forward_impl(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, out, s, loc_dtype, stream_,
+                        {ref_dim});
 }
 
-extern "C" int alo_msda_forward_fused_hm(const void* value_hm, const int32_t* spatial_shapes,
-                                         const int32_t* level_start_index, const void* sampling_offsets,
-                                         const void* attn_logits, const void* reference_points, void* out, int N, int S,
-                                         int M, int D, int L, int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
-    ALO_REQUIRE(reference_points, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward_fused_hm: reference_points is null");
-    ALO_REQUIRE(ref_dim == 2 || ref_dim == 4, ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused_hm: last dim of reference_points must be 2 or 4, got %d", ref_dim);
-    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
-                        ref_dim, out, N, S, M, D, L, Lq, P, value_dtype, ALO_F32, stream_, true);
+extern "C" int alo_msda_forward_fused_hm(const void* value_hm, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                                         const void* sampling_offsets, const void* attn_logits, const void* reference_points, void* out,
+                                         int N, int S, int M, int D, int L, int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    if (int rc = check_fused_args("alo_msda_forward_fused_hm", reference_points, ref_dim, s)) return rc;
+    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, out, s, ALO_F32, stream_,
+                        {ref_dim, true});
 }
 
-extern "C" int alo_msda_forward_fused_hm_rows(const void* value_hm, const int32_t* spatial_shapes,
-                                              const int32_t* level_start_index, const void* sampling_offsets,
-                                              const void* attn_logits, long offsets_row_elems, long logits_row_elems,
-                                              const void* reference_points, void* out, int N, int S, int M, int D, int L,
-                                              int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
-    ALO_REQUIRE(reference_points, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward_fused_hm_rows: reference_points is null");
-    ALO_REQUIRE(ref_dim == 2 || ref_dim == 4, ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused_hm_rows: last dim of reference_points must be 2 or 4, got %d", ref_dim);
-    ALO_REQUIRE(offsets_row_elems >= (long)M * L * P * 2 && logits_row_elems >= (long)M * L * P && offsets_row_elems % 8 == 0 &&
-                    logits_row_elems % 8 == 0 && offsets_row_elems < (1L << 30) && logits_row_elems < (1L << 30),
-                ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused_hm_rows: row strides must cover a query's M*L*P*2 offsets / M*L*P logits and keep 16-byte alignment");
-    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
-                        ref_dim, out, N, S, M, D, L, Lq, P, value_dtype, ALO_F32, stream_, true, offsets_row_elems,
-                        logits_row_elems);
+extern "C" int alo_msda_forward_fused_hm_rows(const void* value_hm, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                                              const void* sampling_offsets, const void* attn_logits, long offsets_row_elems,
+                                              long logits_row_elems, const void* reference_points, void* out, int N, int S, int M, int D,
+                                              int L, int Lq, int P, int ref_dim, int value_dtype, void* stream_) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    const long rows[2] = {offsets_row_elems, logits_row_elems};
+    if (int rc = check_fused_args("alo_msda_forward_fused_hm_rows", reference_points, ref_dim, s, rows)) return rc;
+    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, out, s, ALO_F32, stream_,
+                        {ref_dim, true, offsets_row_elems, logits_row_elems});
 }
 
-extern "C" int alo_msda_forward_fused_hm_resident(const void* value_hm, const int32_t* spatial_shapes,
-                                                  const int32_t* level_start_index, const void* sampling_offsets,
-                                                  const void* attn_logits, long offsets_row_elems, long logits_row_elems,
-                                                  const void* reference_points, void* out, int N, int S, int M, int D, int L,
-                                                  int Lq, int P, int ref_dim, int value_dtype, const int32_t* host_spatial_shapes,
-                                                  int policy, void* stream_) {
+extern "C" int alo_msda_forward_fused_hm_resident(const void* value_hm, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                                                  const void* sampling_offsets, const void* attn_logits, long offsets_row_elems,
+                                                  long logits_row_elems, const void* reference_points, void* out, int N, int S, int M, int D,
+                                                  int L, int Lq, int P, int ref_dim, int value_dtype,
+                                                  const int32_t* host_spatial_shapes, int policy, void* stream_) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    const long rows[2] = {offsets_row_elems, logits_row_elems};
     ALO_REQUIRE(reference_points, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward_fused_hm_resident: reference_points is null");
     ALO_REQUIRE(host_spatial_shapes, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward_fused_hm_resident: host_spatial_shapes is null");
     ALO_REQUIRE(policy == ALO_RESIDENT_AUTO || policy == ALO_RESIDENT_ALWAYS, ALO_ERR_INVALID_ARGUMENT,
                 "alo_msda_forward_fused_hm_resident: policy must be ALO_RESIDENT_AUTO or ALO_RESIDENT_ALWAYS, got %d", policy);
-    ALO_REQUIRE(ref_dim == 2 || ref_dim == 4, ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused_hm_resident: last dim of reference_points must be 2 or 4, got %d", ref_dim);
-    ALO_REQUIRE(offsets_row_elems >= (long)M * L * P * 2 && logits_row_elems >= (long)M * L * P && offsets_row_elems % 8 == 0 &&
-                    logits_row_elems % 8 == 0 && offsets_row_elems < (1L << 30) && logits_row_elems < (1L << 30),
-                ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_forward_fused_hm_resident: row strides must cover a query's M*L*P*2 offsets / M*L*P logits and keep 16-byte alignment");
-    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
-                        ref_dim, out, N, S, M, D, L, Lq, P, value_dtype, ALO_F32, stream_, true, offsets_row_elems,
-                        logits_row_elems, host_spatial_shapes, policy);
+    if (int rc = check_fused_args("alo_msda_forward_fused_hm_resident", reference_points, ref_dim, s, rows)) return rc;
+    return forward_impl(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, out, s, ALO_F32, stream_,
+                        {ref_dim, true, offsets_row_elems, logits_row_elems, host_spatial_shapes, policy});
 }
 
+// The signature carries no D, P, dtype, row strides or pointers: the answer is for the launch alo_hip asks about (bf16, D = 32, P = 4,
+// dense rows, 16-byte aligned pointers), from the plan that launch itself follows.
 extern "C" int alo_msda_resident_levels(const int32_t* host_spatial_shapes, int N, int S, int M, int L, int Lq, int policy) {
-    ResDims rd;
-    return host_spatial_shapes ? resident_plan(host_spatial_shapes, N, S, M, L, Lq, policy, &rd) : 0;
+    const Shape s{N, S, M, 32, L, Lq, 4, ALO_BF16};
+    if (!host_spatial_shapes || validate(s, ALO_F32)) return 0;
+    return plan_forward(s, {2, true, 0, 0, host_spatial_shapes, policy, true, true, true}).route == FWD_RESIDENT ? 2 : 0;
 }
 
 namespace {
-// ALO_MSDA_BWD = "tiled" keeps msda_bwd_tiled_kernel for the encoder-shaped launches the wide path would take (measurement knob)
-int bwd_policy() {   // read per call: a test flips it inside one process
-    const char* e = getenv("ALO_MSDA_BWD");
-    return (e && !strcmp(e, "tiled")) ? 1 : 0;
-}
-
-int backward_impl(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
-                  const void* sampling_loc, const void* attn_weight, const void* grad_out, void* grad_value,
-                  void* grad_sampling_loc, void* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P,
-                  int value_dtype, int loc_dtype, const int32_t* host_shapes, void* stream_) {
-    size_t elem = 0;
-    if (int rc = validate(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
-                          value_dtype, loc_dtype, &elem))
-        return rc;
-    ALO_REQUIRE(grad_out && grad_value && grad_sampling_loc && grad_attn_weight, ALO_ERR_INVALID_ARGUMENT,
-                "alo_msda_backward: null gradient pointer");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t gelem = value_dtype == ALO_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * gelem, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward: memset: %s", hipGetErrorString(e));
-    const bool aligned = (((uintptr_t)value | (uintptr_t)grad_out) & 15) == 0;
-    const bool all_aligned = aligned && (((uintptr_t)sampling_loc | (uintptr_t)attn_weight | (uintptr_t)grad_value |
-                                          (uintptr_t)grad_sampling_loc | (uintptr_t)grad_attn_weight) & 15) == 0;
+// Pure host logic: which backward kernel a launch takes and that kernel's dims (the wide path sizes its own grid).
+// alo_msda_backward_hinted launches what this says, alo_msda_backward_path reports it.
+// `aligned`: value and grad_out on 16 bytes; `all_aligned`: every other tensor too.
+LaunchPlan plan_backward(const Shape& s, const int32_t* host_shapes, bool aligned, bool all_aligned) {
+    const auto [N, S, M, D, L, Lq, P, vdt] = s;
+    LaunchPlan bp;
+    // ALO_MSDA_BWD = "tiled" keeps msda_bwd_tiled_kernel for the encoder-shaped launches the wide path would take (measurement knob);
+    // read per call: a test flips it inside one process
+    const char* knob = getenv("ALO_MSDA_BWD");
+    const bool no_wide = knob && !strcmp(knob, "tiled");
     const bool frame32 = (double)S * M * 128 < 4.0e9 && (double)Lq * M * 32 < 2.0e9;   // 32-bit byte offsets inside one frame
-    if ((value_dtype == ALO_F32 || value_dtype == ALO_BF16) && (D == 32 || D == 64) && L == 4 && P == 4 && all_aligned && frame32 && host_shapes &&
-        Lq == S && bwd_policy() != 1) {
-        // queries = the pyramid's own pixels: 16x16 query blocks, sorted on chip (msda_bwd_wide.hip)
-        const int rc = msda_backward_wide(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
-                                          grad_sampling_loc, grad_attn_weight, N, S, M, D, Lq, value_dtype, host_shapes, stream);
-        if (rc != ALO_ERR_UNSUPPORTED) return rc;
-    }
-    if (value_dtype == ALO_F32 && D == 32 && L == 4 && P == 4 && all_aligned && frame32) {
+    const bool detr = L == 4 && P == 4 && all_aligned && frame32;
+    const bool pyramid = host_shapes && Lq == S;   // queries = the pyramid's own pixels (encoder self-attention)
+    // 16x16 query blocks, sorted on chip (msda_bwd_wide.hip).  That file's host side has the last word: a geometry its block table
+    // cannot describe goes to the kernels below.
+    if ((vdt == ALO_F32 || vdt == ALO_BF16) && (D == 32 || D == 64) && detr && pyramid && !no_wide &&
+        msda_backward_wide(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, S, M, D, Lq, vdt, host_shapes,
+                           nullptr, true) == ALO_OK) {
+        bp.route = ALO_MSDA_BWD_WIDE;
+    } else if (vdt == ALO_F32 && D == 32 && detr) {
         // the DETR-family shape: tiled, window-dense backward on the fp32 matrix cores (msda_bwd_tiled_kernel)
-        TileDims td;
+        bp.route = ALO_MSDA_BWD_TILED;
+        TileDims& td = bp.td;
         td.S = S; td.M = M; td.Lq = Lq;
-        td.pyramid = 0;
-        td.n_super = (Lq + 15) / 16;
+        td.pyramid = 0; td.n_super = (Lq + 15) / 16;
         const int tile = 4;
-        if (host_shapes && Lq == S) {
-            // queries = the pyramid's own pixels (encoder self-attention): 4x4 blocks of each level.  The host copy of the shapes
-            // only SIZES the grid; the kernel derives which queries a tile owns from the device copy.  A host copy that disagrees
-            // with the device one can therefore only leave tiles empty or — if it under-counts — miss queries, which is why the
-            // Python host never caches it across tensors (alo_hip.msda_backward).
+        if (pyramid) {
+            // 4x4 blocks of each level.  The host copy of the shapes only SIZES the grid; the kernel derives which queries a tile owns
+            // from the device copy.  A host copy that disagrees with the device one can therefore only leave tiles empty or — if it
+            // under-counts — miss queries, which is why the Python host never caches it across tensors (alo_hip.msda_backward).
             long total = 0;
             int tiles = 0;
             bool ok = true;
@@ -1919,69 +1923,63 @@ int backward_impl(const void* value, const int32_t* spatial_shapes, const int32_
             if (ok && total == S) { td.pyramid = 1; td.n_super = tiles; }
         }
         const long nb = (long)N * td.n_super * M;
-        ALO_REQUIRE(nb < 0x7fffffffL, ALO_ERR_UNSUPPORTED, "alo_msda_backward: grid too large");
+        if (nb >= 0x7fffffffL) bp.route = -1;
         td.nblocks = (unsigned)nb;
-        {
-            static unsigned long long attr_done = 0;   // one bit per device
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(msda_bwd_tiled_kernel), kTileLds, &attr_done);
-            if (ea != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward: %s", hipGetErrorString(ea));
+    } else {
+        bp.route = ALO_MSDA_BWD_GENERIC;
+        bp.plan = make_plan(D, L, P, s.elem(), aligned);
+        if (D <= 64) {
+            // one channel per lane: each of the four atomics of a sampling point then covers D consecutive elements of ONE row
+            // (a whole 128-byte line for D = 32 fp32) instead of every VEC-th element of it
+            bp.plan.vec = 1;
+            bp.plan.g = D <= 8 ? 8 : (D <= 32 ? 32 : 64);
+            bp.plan.lp16 = false;
         }
-        void* targs[] = {&value, &spatial_shapes, &level_start_index, &sampling_loc, &attn_weight, &grad_out,
-                         &grad_value, &grad_sampling_loc, &grad_attn_weight, &td};
-        hipError_t el = hipLaunchKernel(reinterpret_cast<const void*>(msda_bwd_tiled_kernel), dim3(td.nblocks), dim3(64),
-                                        targs, kTileLds, stream);
-        if (el != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward: %s", hipGetErrorString(el));
-        return check_launch("alo_msda_backward");
+        bp.dm = make_dims(s, bp.plan.g);
     }
-    Plan plan = make_plan(D, L, P, elem, aligned);
-    if (D <= 64) {
-        // one channel per lane: each of the four atomics of a sampling point then covers D consecutive elements of ONE row
-        // (a whole 128-byte line for D = 32 fp32) instead of every VEC-th element of it
-        plan.vec = 1;
-        plan.g = D <= 8 ? 8 : (D <= 32 ? 32 : 64);
-        plan.lp16 = false;
-    }
-    Dims dm = make_dims(N, S, M, D, L, Lq, P, plan.g);
-    void* args[] = {&value, &spatial_shapes, &level_start_index, &sampling_loc, &attn_weight, &grad_out,
-                    &grad_value, &grad_sampling_loc, &grad_attn_weight, &dm};
-    if (value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_BWD_CASE, float, float, float, 4) }
-    if (value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_BWD_CASE, double, double, double, 2) }
-    if (value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_BWD_CASE, bf16_t, float, float, 8) }
-    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_backward: no kernel for vec=%d group=%d", plan.vec, plan.g);
+    return bp;
 }
 }  // namespace
 
-extern "C" int alo_msda_backward(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
-                                 const void* sampling_loc, const void* attn_weight, const void* grad_out,
-                                 void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, int N, int S, int M,
-                                 int D, int L, int Lq, int P, int value_dtype, int loc_dtype, void* stream_) {
-    return backward_impl(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
-                         grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, value_dtype, loc_dtype, nullptr, stream_);
-}
-
 extern "C" int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
-                                        const void* sampling_loc, const void* attn_weight, const void* grad_out,
-                                        void* grad_value, void* grad_sampling_loc, void* grad_attn_weight, int N, int S,
-                                        int M, int D, int L, int Lq, int P, int value_dtype, int loc_dtype,
-                                        const int32_t* host_spatial_shapes, void* stream_) {
-    return backward_impl(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
-                         grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, value_dtype, loc_dtype,
-                         host_spatial_shapes, stream_);
+                                        const void* sampling_loc, const void* attn_weight, const void* grad_out, void* grad_value,
+                                        void* grad_sampling_loc, void* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P,
+                                        int value_dtype, int loc_dtype, const int32_t* host_spatial_shapes, void* stream_) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    ALO_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight, ALO_ERR_INVALID_ARGUMENT, "msda: null pointer argument");
+    if (int rc = validate(s, loc_dtype)) return rc;
+    ALO_REQUIRE(grad_out && grad_value && grad_sampling_loc && grad_attn_weight, ALO_ERR_INVALID_ARGUMENT, "alo_msda_backward: null gradient pointer");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const bool aligned = (((uintptr_t)value | (uintptr_t)grad_out) & 15) == 0;
+    const bool all_aligned = aligned && (((uintptr_t)sampling_loc | (uintptr_t)attn_weight | (uintptr_t)grad_value |
+                                          (uintptr_t)grad_sampling_loc | (uintptr_t)grad_attn_weight) & 15) == 0;
+    LaunchPlan lp = plan_backward(s, host_spatial_shapes, aligned, all_aligned);
+    ALO_REQUIRE(lp.route >= 0, ALO_ERR_UNSUPPORTED, "alo_msda_backward: grid too large");
+    hipError_t e = hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * (value_dtype == ALO_F64 ? 8 : 4), stream);
+    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward: memset: %s", hipGetErrorString(e));
+    if (lp.route == ALO_MSDA_BWD_WIDE)
+        return msda_backward_wide(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                                  grad_sampling_loc, grad_attn_weight, N, S, M, D, Lq, value_dtype, host_spatial_shapes, stream);
+    void* args[] = {&value, &spatial_shapes, &level_start_index, &sampling_loc, &attn_weight, &grad_out, &grad_value,
+                    &grad_sampling_loc, &grad_attn_weight, lp.route == ALO_MSDA_BWD_TILED ? (void*)&lp.td : (void*)&lp.dm};
+    if (lp.route == ALO_MSDA_BWD_TILED) return launch<msda_bwd_tiled_kernel>(lp.td.nblocks, 64, kTileLds, stream, "alo_msda_backward", args);
+    if (value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_BWD_CASE, float, float, float, 4) }
+    if (value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_BWD_CASE, double, double, double, 2) }
+    if (value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_BWD_CASE, bf16_t, float, float, 8) }
+    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_backward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
 }
 
-// Which kernel alo_msda_backward[_hinted] takes for a launch of these dimensions (16-byte aligned pointers assumed): the answer the
-// dispatch in backward_impl gives, without enqueuing anything.
+extern "C" int alo_msda_backward(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                                 const void* sampling_loc, const void* attn_weight, const void* grad_out, void* grad_value,
+                                 void* grad_sampling_loc, void* grad_attn_weight, int N, int S, int M, int D, int L, int Lq, int P,
+                                 int value_dtype, int loc_dtype, void* stream_) {
+    return alo_msda_backward_hinted(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                                    grad_sampling_loc, grad_attn_weight, N, S, M, D, L, Lq, P, value_dtype, loc_dtype, nullptr, stream_);
+}
+
+// The route plan_backward picks for these dimensions with 16-byte aligned pointers, nothing enqueued; -1 for a launch the library refuses.
 extern "C" int alo_msda_backward_path(int N, int S, int M, int D, int L, int Lq, int P, int value_dtype, int loc_dtype,
                                       const int32_t* host_spatial_shapes) {
-    const bool pair_ok = (value_dtype == ALO_F32 && loc_dtype == ALO_F32) || (value_dtype == ALO_F64 && loc_dtype == ALO_F64) ||
-                         (value_dtype == ALO_BF16 && loc_dtype == ALO_F32);
-    if (!pair_ok || N <= 0 || S <= 0 || M <= 0 || D <= 0 || L <= 0 || Lq <= 0 || P <= 0) return -1;
-    const bool frame32 = (double)S * M * 128 < 4.0e9 && (double)Lq * M * 32 < 2.0e9;
-    if ((value_dtype == ALO_F32 || value_dtype == ALO_BF16) && (D == 32 || D == 64) && L == 4 && P == 4 && frame32 && host_spatial_shapes && Lq == S &&
-        bwd_policy() != 1 &&
-        msda_backward_wide(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, S, M, D, Lq, value_dtype,
-                           host_spatial_shapes, nullptr, true) == ALO_OK)
-        return ALO_MSDA_BWD_WIDE;
-    if (value_dtype == ALO_F32 && D == 32 && L == 4 && P == 4 && frame32) return ALO_MSDA_BWD_TILED;
-    return ALO_MSDA_BWD_GENERIC;
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    return validate(s, loc_dtype) ? -1 : plan_backward(s, host_spatial_shapes, true, true).route;
 }

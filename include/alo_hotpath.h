@@ -134,7 +134,9 @@ int alo_msda_forward_fused_hm_rows(const void* value_hm, const int32_t* spatial_
  * below) — and the plain head-major kernel otherwise (small frames, the decoder's 300 queries): callers may use it unconditionally.
  * ALO_RESIDENT_ALWAYS takes the resident kernel wherever it can run (tests; callers that know better).  Results are bit-identical
  * to alo_msda_forward_fused_hm either way (same products, same order of the sum).
- * alo_msda_resident_levels reports what a launch of these dimensions would do under `policy`: 2 (levels 2-3 resident) or 0 (plain).
+ * alo_msda_resident_levels reports what a launch of these dimensions would do under `policy`: 2 (levels 2-3 resident) or 0 (plain),
+ * from the plan the launch itself follows.  Its signature has no D, P, dtype, row strides or pointers: it answers for bf16, D = 32,
+ * P = 4, dense rows and 16-byte aligned pointers (any other launch is plain or refused), and 0 for dimensions the library refuses.
  */
 #define ALO_RESIDENT_AUTO 0
 #define ALO_RESIDENT_ALWAYS 1
@@ -174,9 +176,9 @@ int alo_msda_backward(const void* value, const int32_t* spatial_shapes, const in
 
 /*
  * The same operation with a scheduling hint: `host_spatial_shapes` is a HOST copy of spatial_shapes (L x 2 int32, may be NULL).
- * When the queries are the pyramid's own pixels (Lq == S, the encoder's self-attention) the D = 32, L = P = 4 launches (fp32 or
+ * When the queries are the pyramid's own pixels (Lq == S, the encoder's self-attention) the D = 32 or 64, L = P = 4 launches (fp32 or
  * bf16 values) then group them as 16x16 blocks of their level, sort a block's sampling corners by pixel on chip and issue ONE atomic
- * row per touched pixel per block (msda_bwd_wide.hip); without the hint fp32 takes 4x4 tiles of 16 consecutive queries.  Results do not depend on
+ * row per touched pixel per block (msda_bwd_wide.hip); without the hint fp32 D = 32 takes 4x4 tiles of 16 consecutive queries.  Results do not depend on
  * the hint (up to the order of the floating-point additions, which atomics leave undefined anyway); alo_msda_backward is this
  * call with a NULL hint.
  */
@@ -189,8 +191,9 @@ int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, c
 /*
  * Which kernel alo_msda_backward_hinted takes for a launch of these dimensions (pointers assumed 16-byte aligned), without
  * enqueuing anything: ALO_MSDA_BWD_WIDE (16x16 query blocks sorted on chip, one atomic row per touched pixel per block: fp32 / bf16
- * values, D = 32, L = P = 4, Lq == S and a host copy of the shapes), ALO_MSDA_BWD_TILED (4x4 query tiles on the fp32 matrix cores:
- * fp32, D = 32, L = P = 4), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else); -1 for an unsupported dtype pair.
+ * values, D = 32 or 64, L = P = 4, Lq == S and a host copy of the shapes), ALO_MSDA_BWD_TILED (4x4 query tiles on the fp32 matrix cores:
+ * fp32, D = 32, L = P = 4), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else); -1 for a launch the library refuses
+ * (dtype pair, dimensions, sizes: alo_last_error says which).  The launch and this query read one plan, so they cannot disagree.
  */
 #define ALO_MSDA_BWD_GENERIC 0
 #define ALO_MSDA_BWD_TILED 1

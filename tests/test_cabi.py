@@ -92,7 +92,7 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 
 def test_resident_forward_plan_is_host_logic():
-    """alo_msda_resident_levels: which launches the LDS-resident forward serves (csrc/msda.hip resident_plan; 256 CUs assumed when no
+    """alo_msda_resident_levels: which launches the LDS-resident forward serves (csrc/msda.hip plan_forward / resident_plan; 256 CUs assumed when no
     device answers).  AUTO = at least one 16-query run per wave of the chip and levels 2-3 within the LDS image; ALWAYS = they fit."""
     lib = alo_hip.lib()
 
@@ -121,7 +121,7 @@ def test_resident_forward_plan_is_host_logic():
 
 
 def test_backward_dispatch_table_without_a_gpu():
-    """alo_msda_backward_path is pure host logic: which backward kernel a launch takes (csrc/msda.hip backward_impl)."""
+    """alo_msda_backward_path is pure host logic: which backward kernel a launch takes (csrc/msda.hip plan_backward)."""
     lib = alo_hip.lib()
     shapes = [(100, 167), (50, 84), (25, 42), (13, 21)]
     S = sum(h * w for h, w in shapes)
@@ -134,3 +134,58 @@ def test_backward_dispatch_table_without_a_gpu():
     assert path(32, S, f32, f64, hint) == -1     # not a supported dtype pair
     wrong = (ctypes.c_int32 * 8)(100, 167, 50, 84, 25, 42, 13, 20)   # does not add up to S: no block table
     assert path(32, S, f32, f32, wrong) == 1
+
+
+DETR_SHAPES = [(100, 167), (50, 84), (25, 42), (13, 21)]
+
+
+def _c_shapes(shapes):
+    return (ctypes.c_int32 * (2 * len(shapes)))(*[v for hw in shapes for v in hw])
+
+
+def test_host_shape_prefilter_agrees_with_the_backward_plan():
+    """alo_hip._wide_backward_wants_host_shapes decides whether msda_backward reads the shapes back for the hint; the library decides
+    the route from that hint (csrc/msda.hip plan_backward).  The two state one condition in two languages: wherever the pre-filter
+    says yes the hinted launch must be the wide one, wherever it says no the same hint must not make it wide."""
+    import torch
+
+    lib = alo_hip.lib()
+    dtypes = [(torch.float32, alo_hip.ALO_F32, alo_hip.ALO_F32), (torch.float64, alo_hip.ALO_F64, alo_hip.ALO_F64),
+              (torch.bfloat16, alo_hip.ALO_BF16, alo_hip.ALO_F32)]
+    checked = 0
+    for dtype, vdt, ldt in dtypes:
+        for D in (16, 32, 64, 128):
+            for L, P in ((4, 4), (4, 8), (3, 4)):
+                shapes = DETR_SHAPES[:L]
+                S = sum(h * w for h, w in shapes)
+                for Lq in (S, 300):
+                    dims = (4, S, 8, D, L, Lq, P)
+                    wants = alo_hip._wide_backward_wants_host_shapes(torch.empty(0, dtype=dtype), dims, ldt)
+                    path = lib.alo_msda_backward_path(*dims, vdt, ldt, _c_shapes(shapes))
+                    assert path in (0, 1, 2), (dtype, dims, path)
+                    assert (path == 2) == wants, (dtype, dims, path, wants)
+                    checked += 1
+    assert checked == 3 * 4 * 3 * 2
+
+
+def test_backward_env_knob_is_read_on_every_call(monkeypatch):
+    """ALO_MSDA_BWD=tiled keeps the wide kernel out: fp32 D = 32 goes to the tiled kernel, bf16 (no tiled kernel) to the generic one;
+    without the variable, in the same process, both are wide again."""
+    lib = alo_hip.lib()
+    S = sum(h * w for h, w in DETR_SHAPES)
+    hint = _c_shapes(DETR_SHAPES)
+    path = lambda vdt: lib.alo_msda_backward_path(4, S, 8, 32, 4, S, 4, vdt, alo_hip.ALO_F32, hint)  # noqa: E731
+    monkeypatch.setenv("ALO_MSDA_BWD", "tiled")
+    assert path(alo_hip.ALO_F32) == 1 and path(alo_hip.ALO_BF16) == 0
+    monkeypatch.delenv("ALO_MSDA_BWD")
+    assert path(alo_hip.ALO_F32) == 2 and path(alo_hip.ALO_BF16) == 2
+
+
+def test_backward_path_refuses_what_the_launch_refuses():
+    """The query validates like the launch: no kernel is named for a launch alo_msda_backward would turn down."""
+    lib = alo_hip.lib()
+    f32 = alo_hip.ALO_F32
+    assert lib.alo_msda_backward_path(1, 100, 8, 32, 33, 100, 4, f32, f32, None) == -1           # L > 32
+    assert b"levels" in lib.alo_last_error()
+    assert lib.alo_msda_backward_path(1, 1 << 22, 8, 32, 4, 300, 4, f32, f32, None) == -1       # a 4 GiB slab
+    assert lib.alo_msda_backward_path(1, 100, 8, 32, 4, 0, 4, f32, f32, None) == -1

@@ -26,7 +26,7 @@ PER_CORNER, TILED, WIDE = 0, 1, 2   # alo_msda_backward_path: msda_bwd_kernel, m
 
 def backward_path(c, dtype):
     """The kernel alo_hip.msda_backward takes for case ``c``: the wrapper hands the dispatcher a host copy of the shapes exactly for
-    the launches ``_tiled_backward_eligible`` admits, and ``alo_msda_backward_path`` answers the dispatch for that hint (and for the
+    the launches ``_wide_backward_wants_host_shapes`` admits, and ``alo_msda_backward_path`` answers the dispatch for that hint (and for the
     ALO_MSDA_BWD of the moment)."""
     import ctypes
 
@@ -34,7 +34,7 @@ def backward_path(c, dtype):
     _, Lq, _, L, P, _ = c["loc"].shape
     ldt = alo_hip.ALO_F64 if dtype == torch.float64 else alo_hip.ALO_F32
     hint = None
-    if alo_hip._tiled_backward_eligible(torch.empty(0, dtype=dtype), (N, S, M, D, L, Lq, P), ldt):
+    if alo_hip._wide_backward_wants_host_shapes(torch.empty(0, dtype=dtype), (N, S, M, D, L, Lq, P), ldt):
         hint = (ctypes.c_int32 * (2 * L))(*[int(v) for v in np.asarray(c["shapes"]).reshape(-1)])
     return alo_hip.lib().alo_msda_backward_path(N, S, M, D, L, Lq, P, alo_hip._DTYPE_CODE[dtype], ldt, hint)
 
