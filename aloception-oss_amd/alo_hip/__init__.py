@@ -1256,7 +1256,8 @@ def value_proj_head_major(x, weight, bias, padding_mask, heads):
 
 def panoptic_onehot(mask_logits, frame_size, threshold=0.5):
     """(B, Q, h, w) mask logits -> (B, Q, H, W) int64 one-hot instance masks: bilinear up-sampling, sigmoid, threshold and the
-    per-pixel arg-max over the queries in one pass (PanopticHead.inference)."""
+    per-pixel arg-max over the queries in one pass (PanopticHead.inference).  A NaN probability selects its query (the first one
+    if there are several), as ``F.threshold`` (which keeps NaN) followed by ``argmax`` (for which NaN is the maximum) does."""
     if not mask_logits.is_cuda or mask_logits.dim() != 4:
         raise RuntimeError("panoptic_onehot: needs CUDA (B, Q, h, w) logits")
     x = mask_logits.float().contiguous()

@@ -184,8 +184,9 @@ panoptic_onehot_kernel(const float* __restrict__ logits, long long* __restrict__
             const float* p = base + (size_t)q * dm.h * dm.w;
             const float v = ly0 * (lx0 * p[0] + lx1 * p[xp]) + ly1 * (lx0 * p[yp * dm.w] + lx1 * p[yp * dm.w + xp]);
             float s = 1.f / (1.f + expf(-v));
-            s = s > dm.thr ? s : 0.f;          // F.threshold(s, thr, 0)
-            if (s > best) { best = s; arg = q; }   // strict: ties keep the lowest query, as torch.argmax
+            s = s <= dm.thr ? 0.f : s;         // F.threshold(s, thr, 0): NaN is not <= thr and stays NaN
+            // strict: ties keep the lowest query, as torch.argmax; NaN is its maximum, and the first NaN stays
+            if (s > best || (s != s && best == best)) { best = s; arg = q; }
         }
         long long* o = out + (size_t)b * dm.Q * dm.H * dm.W + rem;
         for (int q = 0; q < dm.Q; ++q) o[(size_t)q * dm.H * dm.W] = q == arg ? 1 : 0;

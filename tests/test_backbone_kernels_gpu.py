@@ -23,14 +23,10 @@ import torch
 import torch.nn.functional as F
 
 import alo_hip
+from kernel_bounds import _finite_abs, c_acc, compare
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def c_acc(k):
-    """fp32-accumulation constant of a K-term dot product plus the bias (module docstring)."""
-    return (k + 1) * 2.0 ** -23
 
 
 # ---- launch arithmetic, mirrored from the kernels ----------------------------------------------------------------------------
@@ -77,36 +73,6 @@ def shortk_multi_tile(m, n):
     """gemm.hip launch_shortk: tiles = ceil(M / 64), gx = min(512 / ceil(N / 256), tiles): a 2nd tile iff tiles > gx."""
     tiles = -(-m // 64)
     return tiles > max(1, min(512 // -(-n // 256), tiles))
-
-
-# ---- comparison --------------------------------------------------------------------------------------------------------------
-def _finite_abs(t):
-    return torch.nan_to_num(t.double().abs(), nan=0.0, posinf=0.0)
-
-
-def compare(got, ref, bound, what):
-    """Same non-finite outputs as the fp64 op (NaN where it has NaN, the same infinity where it has one); every other element
-    within ``bound``.  Returns the worst error / bound ratio."""
-    got = got.double()
-    fin_g, fin_r = torch.isfinite(got), torch.isfinite(ref)
-    diff = fin_g != fin_r
-    if diff.any():
-        idx = diff.nonzero()[0].tolist()
-        raise AssertionError(f"{what}: {int(diff.sum())} outputs differ in finiteness from the fp64 op, first at {idx}: "
-                             f"got {got[tuple(idx)].item()} want {ref[tuple(idx)].item()}")
-    nf = ~fin_r
-    if nf.any():
-        assert torch.equal(torch.isnan(got[nf]), torch.isnan(ref[nf])), f"{what}: NaN where the fp64 op has an infinity (or back)"
-        inf = nf & ~torch.isnan(ref)
-        assert torch.equal(got[inf], ref[inf]), f"{what}: an infinity of the wrong sign"
-    err = torch.where(fin_r, (got - ref).abs(), torch.zeros_like(ref))
-    bound = torch.where(fin_r, bound, torch.ones_like(bound))
-    ratio = (err / bound.clamp_min(1e-300)).max().item() if err.numel() else 0.0
-    if ratio > 1.0:
-        idx = (err / bound).flatten().argmax().item()
-        raise AssertionError(f"{what}: |got - ref| / bound = {ratio:.3g} at flat index {idx}: got {got.flatten()[idx].item()} "
-                             f"want {ref.flatten()[idx].item()} bound {bound.flatten()[idx].item():.3g}")
-    return ratio
 
 
 def check_conv3x3(x, w, b, relu, stride, got, what="conv3x3"):
