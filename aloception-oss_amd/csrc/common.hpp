@@ -1,4 +1,4 @@
-// Shared helpers for the gfx950 kernels: error reporting, buffer-resource loads, element conversion.
+// Shared helpers for the gfx950 kernels: error reporting, the launch path, buffer-resource loads, element conversion, MFMA operands.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,24 +24,37 @@ inline int fail(alo_status_t code, const char* fmt, ...) {
         if (!(cond)) return ::alo::fail(code, __VA_ARGS__); \
     } while (0)
 
-inline int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return ALO_OK;
+// Whether every pointer is on a 16-byte boundary (a null pointer is).
+template <typename... P>
+inline bool aligned16(const P*... p) {
+    return ((... | (uintptr_t)p) & 15) == 0;
 }
 
-// Raise a kernel's dynamic-LDS limit once per (kernel, device): a function attribute is per device, so a process-wide flag
-// would leave the second GPU of a single-process multi-GPU job at the 48/64 KB default.  `done` is one atomic bit mask per
-// call site (up to 64 devices); the attribute call itself is idempotent, so a race only repeats it.
-inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, unsigned long long* done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (__atomic_load_n(done, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) __atomic_fetch_or(done, bit, __ATOMIC_RELEASE);
-    return e;
+// The one launch path of the library.  A launch that asks for more than 48 KiB of dynamic LDS raises the kernel's limit to the whole
+// LDS first, once per (kernel, device): a function attribute is per device, so a process-wide flag would leave the second GPU of a
+// single-process multi-GPU job at the 48/64 KB default.  `done` is one atomic bit mask per kernel (this instantiation's own; up to 64
+// devices); the attribute call itself is idempotent, so a race only repeats it.  The attribute call, the launch and hipGetLastError
+// all report through `what`.
+constexpr int kLdsLimit = 160 * 1024;
+template <auto kernel>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const char* what, void** args) {
+    ALO_REQUIRE(lds <= (size_t)kLdsLimit, ALO_ERR_UNSUPPORTED, "%s: %zu bytes of dynamic LDS, the limit is %d", what, lds, kLdsLimit);
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    hipError_t e = hipSuccess;
+    if (lds > 48 * 1024) {
+        static unsigned long long done = 0;
+        int dev = 0;
+        e = hipGetDevice(&dev);
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (e == hipSuccess && !(__atomic_load_n(&done, __ATOMIC_ACQUIRE) & bit)) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
+            if (e == hipSuccess) __atomic_fetch_or(&done, bit, __ATOMIC_RELEASE);
+        }
+    }
+    if (e == hipSuccess) e = hipLaunchKernel(fn, grid, block, args, lds, stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return ALO_OK;
 }
 
 constexpr int kNumXcd = 8;  // MI355X: 8 XCDs, block b is dispatched to XCD b % 8 (speed only, never correctness)
@@ -59,6 +72,22 @@ __device__ __forceinline__ unsigned xcd_contiguous_block(unsigned bid, unsigned 
 int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
                        const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, int N, int S, int M, int D, int Lq,
                        int value_dtype, const int32_t* host_shapes, hipStream_t stream, bool plan_only = false);
+
+// Strided 1x1 convolution over an NHWC map read as a GEMM: row r of X' = pixel (n, s * yo, s * xo) of X; s <= 1: X' = X.
+struct RowGather {
+    int s, Wo, HoWo, W, HW;
+};
+inline RowGather row_gather(int stride = 1, int Ho = 1, int Wo = 1, int H = 1, int W = 1) { return {stride, Wo, Ho * Wo, W, H * W}; }
+
+// gemm.hip: linear_shortk_kernel over gathered rows, the resident-weight flavour of alo_conv1x1_nhwc (gemm_packed.hip).
+int linear_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K,
+                         int relu, const RowGather& gather, hipStream_t stream);
+
+// relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
+// fn<first, relu != 0, residual != nullptr>(args...)
+#define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \
+    ((residual) ? ((relu) ? fn<first, true, true>(__VA_ARGS__) : fn<first, false, true>(__VA_ARGS__))                          \
+                : ((relu) ? fn<first, true, false>(__VA_ARGS__) : fn<first, false, false>(__VA_ARGS__)))
 
 // ---- device side ---------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -85,6 +114,38 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {  // lo in 
     typedef float f32x2_hw __attribute__((ext_vector_type(2)));
     const bf16x2_hw r = __builtin_convertvector(f32x2_hw{lo, hi}, bf16x2_hw);
     return __builtin_bit_cast(unsigned, r);
+}
+
+// the bf16 MFMA's operand type over the four registers a 16-byte load fills
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
+    union { u32x4 u; bf16x8_t b; } x;
+    x.u = v;
+    return x.b;
+}
+
+// GEMM epilogue on 8 bf16 outputs: + identity (same coordinates as y), then the activation, re-packed to bf16
+template <bool RELU>
+__device__ __forceinline__ u32x4 add_residual_bf16x8(const u32x4& v, const u32x4& rv) {
+    const unsigned a4[4] = {v.x, v.y, v.z, v.w}, r4[4] = {rv.x, rv.y, rv.z, rv.w};
+    unsigned o4[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
+        float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
+        if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
+        o4[i] = pack_bf16x2(lo, hi);
+    }
+    return u32x4{o4[0], o4[1], o4[2], o4[3]};
+}
+
+// row of the GEMM -> row of the NHWC input it reads (identity unless the 1x1 convolution is strided)
+__device__ __forceinline__ long gather_row(const RowGather& g, long row) {
+    if (g.s <= 1) return row;
+    const long n = row / g.HoWo;
+    const int rem = (int)(row - n * g.HoWo);
+    const int yo = rem / g.Wo, xo = rem - yo * g.Wo;
+    return n * g.HW + (long)(yo * g.s) * g.W + xo * g.s;
 }
 
 // A raw (stride-0) buffer resource over [base, base + bytes).  Loads whose byte offset falls outside return 0 and

@@ -20,13 +20,6 @@
 namespace alo {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
-
 constexpr int kPix = 64;                     // output pixels per tile
 constexpr int kThreads = 128;                // two waves
 constexpr int kOutStride = 64 * 2 + 16;      // LDS bytes per pixel of a wave's 64 x 64 output block
@@ -314,15 +307,14 @@ int conv_zsplit(int ntiles, int Cin, int Cout) {
 }
 
 template <int STRIDE, bool KSPLIT>
-hipError_t launch_conv(const void* x, const void* w, const void* bias, void* y, void* partial, const ConvDims& dm, hipStream_t stream) {
-    const void* kern = reinterpret_cast<const void*>(conv3x3_kernel<STRIDE, KSPLIT>);
+int launch_conv(const void* x, const void* w, const void* bias, void* y, void* partial, const ConvDims& dm, hipStream_t stream) {
     constexpr int lds = Geo<STRIDE>::kLds + kThreads * 4;
     void* args[] = {&x, &w, &bias, &y, &partial, const_cast<ConvDims*>(&dm)};
     const unsigned gy = KSPLIT ? dm.Cout / 64 : (dm.Cout + 127) / 128;
     const int ntiles = dm.tiles_per_image * dm.N;
     int per_xcd = (ntiles + 7) / 8;
     if (per_xcd > 128) per_xcd = 128;   // 32 CUs per XCD x up to 4 resident workgroups
-    return hipLaunchKernel(kern, dim3((unsigned)(8 * per_xcd), gy, (unsigned)dm.zsplit), dim3(kThreads), args, lds, stream);
+    return launch<conv3x3_kernel<STRIDE, KSPLIT>>(dim3((unsigned)(8 * per_xcd), gy, (unsigned)dm.zsplit), kThreads, lds, stream, "alo_conv3x3_nhwc", args);
 }
 
 }  // namespace
@@ -345,8 +337,7 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
     ALO_REQUIRE(Cin >= 64 && Cin % 64 == 0 && Cout >= 64 && Cout % 64 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_nhwc: Cin and Cout must be multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)workspace) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_conv3x3_nhwc: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, w_packed, y, workspace), ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: pointers must be 16-byte aligned");
     ALO_REQUIRE((long)H * W < (1L << 24) && (long)N * H * W * (long)(Cin > Cout ? Cin : Cout) < (1L << 40), ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_nhwc: image too large");
     ConvDims dm;
@@ -358,18 +349,14 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
     dm.cin_per_z = Cin / dm.zsplit;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool ksplit = Cout == 64;
-    hipError_t e = stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
+    const int rc = stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
                                : (ksplit ? launch_conv<2, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<2, false>(x, w_packed, bias, y, workspace, dm, s));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_conv3x3_nhwc: %s", hipGetErrorString(e));
-    if (dm.zsplit > 1) {
-        const long rows = (long)N * dm.Ho * dm.Wo;
-        const float* part = static_cast<const float*>(workspace);
-        int z = dm.zsplit;
-        long blocks = (rows * (Cout / 8) + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        void* args[] = {&part, &bias, &y, const_cast<long*>(&rows), &Cout, &z, &relu};
-        e = hipLaunchKernel(reinterpret_cast<const void*>(conv_splitk_finalize_kernel), dim3((unsigned)blocks), dim3(256), args, 0, s);
-        if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_conv3x3_nhwc (finalize): %s", hipGetErrorString(e));
-    }
-    return check_launch("alo_conv3x3_nhwc");
+    if (rc != ALO_OK || dm.zsplit == 1) return rc;
+    const long rows = (long)N * dm.Ho * dm.Wo;
+    const float* part = static_cast<const float*>(workspace);
+    int z = dm.zsplit;
+    long blocks = (rows * (Cout / 8) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    void* args[] = {&part, &bias, &y, const_cast<long*>(&rows), &Cout, &z, &relu};
+    return launch<conv_splitk_finalize_kernel>((unsigned)blocks, 256, 0, s, "alo_conv3x3_nhwc (finalize)", args);
 }

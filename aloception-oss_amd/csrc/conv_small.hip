@@ -13,15 +13,6 @@
 namespace alo {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ bf16x8_t as_frag(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
-
 constexpr int kTileH = 8, kTileW = 16;             // output pixels per workgroup: 4 waves x (2 rows x 16 pixels)
 constexpr int kHaloH = kTileH + 2, kHaloW = kTileW + 2;
 
@@ -69,7 +60,7 @@ conv3x3_small_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wf
         for (int cs = 0; cs < CIN / 16; ++cs) {
             const u32x4 a = wf[(tap * (CIN / 16) + cs) * 64];
             const u32x4 b = *reinterpret_cast<const u32x4*>(src + cs * 32);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(a), as_frag(b), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b), acc, 0, 0, 0);
         }
     }
     // ---- store: this lane's pixel, channels 8 j + 4 kg .. + 3 from registers 4 j .. 4 j + 3 ------------------------------------------
@@ -93,9 +84,7 @@ template <int CIN>
 int launch_small(const void* x, const void* wfrag, const void* bias32, void* y, SmallConvDims dm, hipStream_t stream) {
     void* args[] = {&x, &wfrag, &bias32, &y, &dm};
     const long blocks = (long)dm.N * dm.tiles_x * dm.tiles_y;
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(conv3x3_small_kernel<CIN>), dim3((unsigned)blocks), dim3(256), args, 0, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_conv3x3_small_nhwc: %s", hipGetErrorString(e));
-    return check_launch("alo_conv3x3_small_nhwc");
+    return launch<conv3x3_small_kernel<CIN>>((unsigned)blocks, 256, 0, stream, "alo_conv3x3_small_nhwc", args);
 }
 
 }  // namespace
@@ -111,7 +100,7 @@ extern "C" int alo_conv3x3_small_nhwc(const void* x, const void* w_frag, const v
     ALO_REQUIRE(Cout == 1 || (Cout > 0 && Cout <= 32 && Cout % 4 == 0), ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_small_nhwc: Cout must be 1 or a multiple of 4 up to 32 (got %d)", Cout);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_conv3x3_small_nhwc: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)w_frag | (uintptr_t)bias32) & 15) == 0 && ((uintptr_t)y & (Cout == 1 ? 1 : 7)) == 0,
+    ALO_REQUIRE(aligned16(x, w_frag, bias32) && ((uintptr_t)y & (Cout == 1 ? 1 : 7)) == 0,
                 ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_small_nhwc: x, w_frag, bias32 must be 16-byte aligned (y: 8-byte, 2 for Cout = 1)");
     SmallConvDims dm;
     dm.N = N; dm.H = H; dm.W = W; dm.Cout = Cout;

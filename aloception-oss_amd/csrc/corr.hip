@@ -147,12 +147,6 @@ corr_split_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, cons
 // ------------------------------------------------------------------------------------------------------------------
 // correlation GEMM on split operands
 // ------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
 typedef _Float16 __attribute__((ext_vector_type(8))) f16x8_t;
 __device__ __forceinline__ f16x8_t as_f16x8(const u32x4& v) {
     union { u32x4 u; f16x8_t h; } x;
@@ -803,21 +797,22 @@ corr_lookup_bwd_kernel(const LookupBwdArgs a) {
 }
 
 template <int R>
-int launch_lookup(const LookupArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(corr_lookup_kernel<R>, dim3(a.B * a.tiles_per_batch, a.num_levels), dim3(lookup_threads<R>()), 0, stream, a);
-    return check_launch("alo_corr_lookup");
+int launch_lookup(LookupArgs a, hipStream_t stream) {
+    void* args[] = {&a};
+    return launch<corr_lookup_kernel<R>>(dim3(a.B * a.tiles_per_batch, a.num_levels), lookup_threads<R>(), 0, stream, "alo_corr_lookup", args);
 }
 template <int R>
-int launch_lookup_coords_bwd(const LookupCoordsBwdArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(corr_lookup_coords_bwd_kernel<R>, dim3(a.fwd.B * a.fwd.tiles_per_batch, a.fwd.num_levels), dim3(lookup_threads<R>()), 0,
-                       stream, a);
-    return check_launch("alo_corr_lookup_backward_coords");
+int launch_lookup_coords_bwd(LookupCoordsBwdArgs a, hipStream_t stream) {
+    void* args[] = {&a};
+    return launch<corr_lookup_coords_bwd_kernel<R>>(dim3(a.fwd.B * a.fwd.tiles_per_batch, a.fwd.num_levels), lookup_threads<R>(), 0, stream,
+                                                    "alo_corr_lookup_backward_coords", args);
 }
 
 template <int R>
-int launch_lookup_bwd(const LookupBwdArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(corr_lookup_bwd_kernel<R>, dim3(a.B * a.tiles_per_batch, a.num_levels), dim3(lookup_threads<R>()), 0, stream, a);
-    return check_launch("alo_corr_lookup_backward");
+int launch_lookup_bwd(LookupBwdArgs a, hipStream_t stream) {
+    void* args[] = {&a};
+    return launch<corr_lookup_bwd_kernel<R>>(dim3(a.B * a.tiles_per_batch, a.num_levels), lookup_threads<R>(), 0, stream,
+                                             "alo_corr_lookup_backward", args);
 }
 
 int fill_lookup_args(LookupArgs& a, const float* const* levels, const float* coords, float* out, int B, int H, int W, int radius,
@@ -883,7 +878,7 @@ extern "C" int alo_corr_build(const float* fmap1, const float* fmap2, float* con
     ALO_REQUIRE(num_levels >= 1 && num_levels <= kMaxPyr, ALO_ERR_INVALID_ARGUMENT,
                 "alo_corr_build: num_levels must be in [1,%d], got %d", kMaxPyr, num_levels);
     const size_t need = alo_corr_build_workspace_bytes(B, C, H, W, num_levels);
-    ALO_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
+    ALO_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace), ALO_ERR_INVALID_ARGUMENT,
                 "alo_corr_build: a 16-byte aligned workspace of %zu bytes is required, %zu given", need, workspace_bytes);
     ALO_REQUIRE((double)H * W * H * W < 2.0e9 * 64, ALO_ERR_UNSUPPORTED, "alo_corr_build: feature grid too large");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -910,15 +905,15 @@ extern "C" int alo_corr_build(const float* fmap1, const float* fmap2, float* con
     hipError_t em = hipMemsetAsync(amax_b, 0, (size_t)B * sizeof(unsigned), stream);
     if (em != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_corr_build: memset: %s", hipGetErrorString(em));
     auto pixmax = [&](const float* in, int* kexp, unsigned* item_bits, long n) -> int {
-        hipLaunchKernelGGL(corr_pixmax_kernel, dim3((unsigned)((n + kPixPx - 1) / kPixPx), (unsigned)B), dim3(256), 0, stream, in, kexp, item_bits, C, n);
-        return check_launch("alo_corr_build(pixmax)");
+        void* args[] = {&in, &kexp, &item_bits, &C, &n};
+        return launch<corr_pixmax_kernel>(dim3((unsigned)((n + kPixPx - 1) / kPixPx), (unsigned)B), 256, 0, stream, "alo_corr_build(pixmax)", args);
     };
     if (int rc = pixmax(fmap1, ka, nullptr, HW)) return rc;
     if (int rc = pixmax(fmap2, kb, amax_b, HW)) return rc;
     auto split = [&](const float* in, uint16_t* out, const int* kexp, long n) -> int {
         const dim3 grid((unsigned)((n + kSplitPx - 1) / kSplitPx), (unsigned)KC, (unsigned)B);
-        hipLaunchKernelGGL(corr_split_kernel, grid, dim3(256), 0, stream, in, out, kexp, C, n, KC);
-        return check_launch("alo_corr_build(split)");
+        void* args[] = {&in, &out, &kexp, &C, &n, const_cast<int*>(&KC)};
+        return launch<corr_split_kernel>(grid, 256, 0, stream, "alo_corr_build(split)", args);
     };
     if (int rc = split(fmap1, f1s, ka, HW)) return rc;
     if (int rc = split(fmap2, f2s, kb, HW)) return rc;
@@ -940,14 +935,8 @@ extern "C" int alo_corr_build(const float* fmap1, const float* fmap2, float* con
     long nblocks = (long)((g.tiles_m + kRowGroup - 1) / kRowGroup) * kRowGroup * g.tiles_r * g.tiles_c * B;
     ALO_REQUIRE(nblocks < 0x7fffffffL, ALO_ERR_UNSUPPORTED, "alo_corr_build: grid too large");
     g.nblocks = (unsigned)nblocks;
-    static unsigned long long attr_done[2] = {0, 0};   // one bit per device
-    {
-        hipError_t e1 = ensure_dynamic_lds(reinterpret_cast<const void*>(corr_gemm3_kernel<true>), kGemmLds, &attr_done[0]);
-        hipError_t e2 = ensure_dynamic_lds(reinterpret_cast<const void*>(corr_gemm3_kernel<false>), kGemmLds, &attr_done[1]);
-        if (e1 != hipSuccess || e2 != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_corr_build: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    }
-    hipLaunchKernelGGL(corr_gemm3_kernel<true>, dim3(g.nblocks), dim3(kGemmThreads), kGemmLds, stream, g);
-    if (int rc = check_launch("alo_corr_build(gemm)")) return rc;
+    void* gemm_args[] = {&g};
+    if (int rc = launch<corr_gemm3_kernel<true>>(g.nblocks, kGemmThreads, kGemmLds, stream, "alo_corr_build(gemm)", gemm_args)) return rc;
 
     // levels >= 3: the same contraction against the 2x2-average chain of fmap2
     const float* prev = fmap2;
@@ -959,8 +948,8 @@ extern "C" int alo_corr_build(const float* fmap1, const float* fmap2, float* con
         ws += align256((size_t)B * C * h * w * sizeof(float));
         const long planes = (long)B * C, total = planes * h * w;
         const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-        hipLaunchKernelGGL(pool2_kernel, dim3(blocks), dim3(256), 0, stream, prev, pooled, planes, ph, pw);
-        if (int rc = check_launch("alo_corr_build(pool)")) return rc;
+        void* pool_args[] = {&prev, &pooled, const_cast<long*>(&planes), &ph, &pw};
+        if (int rc = launch<pool2_kernel>(blocks, 256, 0, stream, "alo_corr_build(pool)", pool_args)) return rc;
         prev = pooled; ph = h; pw = w;
         if (l < 3) continue;
         const long n = (long)h * w;
@@ -976,8 +965,8 @@ extern "C" int alo_corr_build(const float* fmap1, const float* fmap2, float* con
         e.tiles_r = 1;
         e.tiles_c = (int)((n + kTN - 1) / kTN);
         e.nblocks = (unsigned)((long)((e.tiles_m + kRowGroup - 1) / kRowGroup) * kRowGroup * e.tiles_c * B);
-        hipLaunchKernelGGL(corr_gemm3_kernel<false>, dim3(e.nblocks), dim3(kGemmThreads), kGemmLds, stream, e);
-        if (int rc = check_launch("alo_corr_build(gemm, coarse level)")) return rc;
+        void* coarse_args[] = {&e};
+        if (int rc = launch<corr_gemm3_kernel<false>>(e.nblocks, kGemmThreads, kGemmLds, stream, "alo_corr_build(gemm, coarse level)", coarse_args)) return rc;
     }
     return ALO_OK;
 }

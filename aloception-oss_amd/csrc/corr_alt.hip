@@ -225,9 +225,9 @@ corr_alt_lookup_kernel(const AltArgs a) {
 }
 
 template <int R>
-int launch_alt_lookup(const AltArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(corr_alt_lookup_kernel<R>, dim3(a.nblocks), dim3(kAltThreads), 0, stream, a);
-    return check_launch("alo_corr_alt_lookup");
+int launch_alt_lookup(AltArgs a, hipStream_t stream) {
+    void* args[] = {&a};
+    return launch<corr_alt_lookup_kernel<R>>(a.nblocks, kAltThreads, 0, stream, "alo_corr_alt_lookup", args);
 }
 
 inline size_t alt_align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -291,7 +291,7 @@ extern "C" int alo_corr_alt_prepare(const float* fmap1, const float* const* fmap
     if (int rc = alt_check_sizes(B, C, H, W, num_levels, what)) return rc;
     for (int l = 0; l < num_levels; ++l) ALO_REQUIRE(fmap2_levels[l], ALO_ERR_INVALID_ARGUMENT, "%s: fmap2_levels[%d] is null", what, l);
     const size_t need = alo_corr_alt_workspace_bytes(B, C, H, W, num_levels);
-    ALO_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
+    ALO_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace), ALO_ERR_INVALID_ARGUMENT,
                 "%s: a 16-byte aligned workspace of %zu bytes is required, %zu given", what, need, workspace_bytes);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     float* f1 = nullptr;
@@ -300,8 +300,8 @@ extern "C" int alo_corr_alt_prepare(const float* fmap1, const float* const* fmap
     const int Cp = alt_cpad(C);
     auto relayout = [&](const float* in, float* out, long n) -> int {
         const dim3 grid((unsigned)((n + 63) / 64), (unsigned)(Cp / kAltCS), (unsigned)B);
-        hipLaunchKernelGGL(corr_alt_relayout_kernel, grid, dim3(256), 0, stream, in, out, C, Cp, n);
-        return check_launch(what);
+        void* args[] = {&in, &out, &C, const_cast<int*>(&Cp), &n};
+        return launch<corr_alt_relayout_kernel>(grid, 256, 0, stream, what, args);
     };
     if (int rc = relayout(fmap1, f1, (long)H * W)) return rc;
     for (int l = 0; l < num_levels; ++l) {
@@ -319,7 +319,7 @@ extern "C" int alo_corr_alt_lookup(const void* workspace, size_t workspace_bytes
     if (int rc = alt_check_sizes(B, C, H, W, num_levels, what)) return rc;
     ALO_REQUIRE(radius >= 0 && radius <= 7, ALO_ERR_UNSUPPORTED, "%s: radius must be in [0,7], got %d", what, radius);
     const size_t need = alo_corr_alt_workspace_bytes(B, C, H, W, num_levels);
-    ALO_REQUIRE(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
+    ALO_REQUIRE(workspace_bytes >= need && aligned16(workspace), ALO_ERR_INVALID_ARGUMENT,
                 "%s: a 16-byte aligned workspace of %zu bytes is required, %zu given", what, need, workspace_bytes);
     AltArgs a;
     float* f1 = nullptr;

@@ -318,13 +318,6 @@ pos_generate_kernel(const float* __restrict__ emb, const float* __restrict__ dim
     }
 }
 
-template <typename K>
-int launch(K kernel, unsigned blocks, hipStream_t stream, const char* what, void** args) {
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(blocks), dim3(kThreads), args, 0, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return check_launch(what);
-}
-
 template <typename T>
 int add_layernorm_t(const void* x, const void* res, const void* gamma, const void* beta, void* out, const void* pos,
                     void* out_pos, long rows, int C, float eps, hipStream_t stream) {
@@ -335,10 +328,10 @@ int add_layernorm_t(const void* x, const void* res, const void* gamma, const voi
     const char* what = "alo_add_layernorm";
 #define ALO_LN_CASE(CH)                                                                                            \
     if (chunks == CH) {                                                                                            \
-        if (res && pos) return launch(add_layernorm_kernel<T, CH, true, true>, (unsigned)blocks, stream, what, args);   \
-        if (res) return launch(add_layernorm_kernel<T, CH, true, false>, (unsigned)blocks, stream, what, args);         \
-        if (pos) return launch(add_layernorm_kernel<T, CH, false, true>, (unsigned)blocks, stream, what, args);         \
-        return launch(add_layernorm_kernel<T, CH, false, false>, (unsigned)blocks, stream, what, args);                 \
+        if (res && pos) return launch<add_layernorm_kernel<T, CH, true, true>>((unsigned)blocks, kThreads, 0, stream, what, args);   \
+        if (res) return launch<add_layernorm_kernel<T, CH, true, false>>((unsigned)blocks, kThreads, 0, stream, what, args);         \
+        if (pos) return launch<add_layernorm_kernel<T, CH, false, true>>((unsigned)blocks, kThreads, 0, stream, what, args);         \
+        return launch<add_layernorm_kernel<T, CH, false, false>>((unsigned)blocks, kThreads, 0, stream, what, args);                 \
     }
     ALO_LN_CASE(1) ALO_LN_CASE(2) ALO_LN_CASE(3) ALO_LN_CASE(4)
 #undef ALO_LN_CASE
@@ -353,11 +346,11 @@ int bias_act_t(const void* x, const void* bias, const void* res, void* y, long r
     void* args[] = {&x, &bias, &res, &y, &n4, &C};
     const char* what = "alo_bias_act";
     if (res) {
-        if (relu) return launch(bias_act_kernel<T, true, true>, (unsigned)blocks, stream, what, args);
-        return launch(bias_act_kernel<T, true, false>, (unsigned)blocks, stream, what, args);
+        if (relu) return launch<bias_act_kernel<T, true, true>>((unsigned)blocks, kThreads, 0, stream, what, args);
+        return launch<bias_act_kernel<T, true, false>>((unsigned)blocks, kThreads, 0, stream, what, args);
     }
-    if (relu) return launch(bias_act_kernel<T, false, true>, (unsigned)blocks, stream, what, args);
-    return launch(bias_act_kernel<T, false, false>, (unsigned)blocks, stream, what, args);
+    if (relu) return launch<bias_act_kernel<T, false, true>>((unsigned)blocks, kThreads, 0, stream, what, args);
+    return launch<bias_act_kernel<T, false, false>>((unsigned)blocks, kThreads, 0, stream, what, args);
 }
 
 }  // namespace
@@ -372,9 +365,8 @@ extern "C" int alo_add_layernorm(const void* x, const void* residual, const void
                 "alo_add_layernorm: pos and out_pos go together");
     ALO_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_add_layernorm: rows must be positive and C a positive multiple of 4 (rows=%ld C=%d)", rows, C);
-    const uintptr_t all = (uintptr_t)x | (uintptr_t)residual | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out |
-                          (uintptr_t)pos | (uintptr_t)out_pos;
-    ALO_REQUIRE((all & 15) == 0, ALO_ERR_INVALID_ARGUMENT, "alo_add_layernorm: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, residual, gamma, beta, out, pos, out_pos), ALO_ERR_INVALID_ARGUMENT,
+                "alo_add_layernorm: pointers must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == ALO_F32) return add_layernorm_t<float>(x, residual, gamma, beta, out, pos, out_pos, rows, C, eps, s);
     if (dtype == ALO_BF16) return add_layernorm_t<bf16_t>(x, residual, gamma, beta, out, pos, out_pos, rows, C, eps, s);
@@ -386,8 +378,7 @@ extern "C" int alo_bias_act(const void* x, const void* bias, const void* residua
     ALO_REQUIRE(x && bias && y, ALO_ERR_INVALID_ARGUMENT, "alo_bias_act: null pointer argument");
     ALO_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_bias_act: rows must be positive and C a positive multiple of 4 (rows=%ld C=%d)", rows, C);
-    const uintptr_t all = (uintptr_t)x | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)y;
-    ALO_REQUIRE((all & 15) == 0, ALO_ERR_INVALID_ARGUMENT, "alo_bias_act: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, bias, residual, y), ALO_ERR_INVALID_ARGUMENT, "alo_bias_act: pointers must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == ALO_F32) return bias_act_t<float>(x, bias, residual, y, rows, C, relu, s);
     if (dtype == ALO_BF16) return bias_act_t<bf16_t>(x, bias, residual, y, rows, C, relu, s);
@@ -400,13 +391,9 @@ extern "C" int alo_value_head_major(const void* value, const void* padding_mask,
     ALO_REQUIRE(N > 0 && S > 0 && M > 0 && D > 0 && D % 8 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_value_head_major: dimensions must be positive and D a multiple of 8 (N=%d S=%d M=%d D=%d)", N, S, M, D);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_value_head_major: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)value | (uintptr_t)out) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_value_head_major: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(value, out), ALO_ERR_INVALID_ARGUMENT, "alo_value_head_major: pointers must be 16-byte aligned");
     void* args[] = {&value, &padding_mask, &out, &S, &M, &D};
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(value_head_major_kernel), dim3((S + 63) / 64, N),
-                                   dim3(kThreads), args, 0, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_value_head_major: %s", hipGetErrorString(e));
-    return check_launch("alo_value_head_major");
+    return launch<value_head_major_kernel>(dim3((S + 63) / 64, N), kThreads, 0, static_cast<hipStream_t>(stream), "alo_value_head_major", args);
 }
 
 static unsigned stream_blocks(long n4) {
@@ -418,14 +405,13 @@ extern "C" int alo_bias_act_nchw(const float* x, const float* bias, float* y, in
     ALO_REQUIRE(x && bias && y, ALO_ERR_INVALID_ARGUMENT, "alo_bias_act_nchw: null pointer argument");
     ALO_REQUIRE(B > 0 && C > 0 && HW > 0 && HW % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_bias_act_nchw: dimensions must be positive and H*W a multiple of 4 (B=%d C=%d HW=%d)", B, C, HW);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_bias_act_nchw: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, y), ALO_ERR_INVALID_ARGUMENT, "alo_bias_act_nchw: pointers must be 16-byte aligned");
     long n4 = (long)B * C * HW / 4;
     int hw4 = HW / 4;
     void* args[] = {&x, &bias, &y, &n4, &C, &hw4};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (relu) return launch(bias_act_nchw_kernel<true>, stream_blocks(n4), s, "alo_bias_act_nchw", args);
-    return launch(bias_act_nchw_kernel<false>, stream_blocks(n4), s, "alo_bias_act_nchw", args);
+    if (relu) return launch<bias_act_nchw_kernel<true>>(stream_blocks(n4), kThreads, 0, s, "alo_bias_act_nchw", args);
+    return launch<bias_act_nchw_kernel<false>>(stream_blocks(n4), kThreads, 0, s, "alo_bias_act_nchw", args);
 }
 
 extern "C" int alo_gru_gate(float* zr, const float* bias_zr, const float* h, float* rh, int B, int C, int HW,
@@ -434,12 +420,11 @@ extern "C" int alo_gru_gate(float* zr, const float* bias_zr, const float* h, flo
     ALO_REQUIRE(B > 0 && C > 0 && HW > 0 && HW % 4 == 0 && h_batch_stride % 4 == 0 && rh_batch_stride % 4 == 0,
                 ALO_ERR_INVALID_ARGUMENT, "alo_gru_gate: H*W and the batch strides must be multiples of 4 (B=%d C=%d HW=%d)",
                 B, C, HW);
-    ALO_REQUIRE((((uintptr_t)zr | (uintptr_t)h | (uintptr_t)rh) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_gru_gate: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(zr, h, rh), ALO_ERR_INVALID_ARGUMENT, "alo_gru_gate: pointers must be 16-byte aligned");
     long n4 = (long)B * C * HW / 4;
     int hw4 = HW / 4;
     void* args[] = {&zr, &bias_zr, &h, &rh, &n4, &C, &hw4, &h_batch_stride, &rh_batch_stride};
-    return launch(gru_gate_kernel, stream_blocks(n4), static_cast<hipStream_t>(stream), "alo_gru_gate", args);
+    return launch<gru_gate_kernel>(stream_blocks(n4), kThreads, 0, static_cast<hipStream_t>(stream), "alo_gru_gate", args);
 }
 
 extern "C" int alo_gru_update(const float* q, const float* bias_q, const float* zr, float* h, float* net, int B, int C,
@@ -447,12 +432,11 @@ extern "C" int alo_gru_update(const float* q, const float* bias_q, const float* 
     ALO_REQUIRE(q && bias_q && zr && h, ALO_ERR_INVALID_ARGUMENT, "alo_gru_update: null pointer argument");
     ALO_REQUIRE(B > 0 && C > 0 && HW > 0 && HW % 4 == 0 && h_batch_stride % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_gru_update: H*W and the batch stride must be multiples of 4 (B=%d C=%d HW=%d)", B, C, HW);
-    ALO_REQUIRE((((uintptr_t)q | (uintptr_t)zr | (uintptr_t)h | (uintptr_t)net) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_gru_update: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(q, zr, h, net), ALO_ERR_INVALID_ARGUMENT, "alo_gru_update: pointers must be 16-byte aligned");
     long n4 = (long)B * C * HW / 4;
     int hw4 = HW / 4;
     void* args[] = {&q, &bias_q, &zr, &h, &net, &n4, &C, &hw4, &h_batch_stride};
-    return launch(gru_update_kernel, stream_blocks(n4), static_cast<hipStream_t>(stream), "alo_gru_update", args);
+    return launch<gru_update_kernel>(stream_blocks(n4), kThreads, 0, static_cast<hipStream_t>(stream), "alo_gru_update", args);
 }
 
 extern "C" int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatial_shapes, const int32_t* level_start_index,
@@ -465,16 +449,14 @@ extern "C" int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatia
                 "alo_pos_sine_flat: sizes must be positive and num_pos_feats a multiple of 4 (B=%d S=%d L=%d F=%d)", B, S, L,
                 num_pos_feats);
     ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_pos_sine_flat: dtype %d", dtype);
-    ALO_REQUIRE((((uintptr_t)out | (uintptr_t)level_embed) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_pos_sine_flat: out / level_embed must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(out, level_embed), ALO_ERR_INVALID_ARGUMENT, "alo_pos_sine_flat: out / level_embed must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     {
         void* args[] = {&padding_mask, &spatial_shapes, &level_start_index, &workspace, &S, &normalize, &center, &scale, &eps};
-        hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(pos_prefix_kernel), dim3(32, L, B), dim3(kThreads), args, 0, st);
-        if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_pos_sine_flat: %s", hipGetErrorString(e));
+        if (int rc = launch<pos_prefix_kernel>(dim3(32, L, B), kThreads, 0, st, "alo_pos_sine_flat", args)) return rc;
     }
     long n4 = (long)B * S * (2 * num_pos_feats) / 4;
     void* args[] = {&workspace, &dim_t, &level_embed, &level_start_index, &out, &n4, &S, &L, &num_pos_feats};
-    if (dtype == ALO_F32) return launch(pos_generate_kernel<float>, stream_blocks(n4), st, "alo_pos_sine_flat", args);
-    return launch(pos_generate_kernel<bf16_t>, stream_blocks(n4), st, "alo_pos_sine_flat", args);
+    if (dtype == ALO_F32) return launch<pos_generate_kernel<float>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
+    return launch<pos_generate_kernel<bf16_t>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
 }

@@ -19,32 +19,13 @@ namespace {
 constexpr int kRows = 64;               // rows of X per tile
 constexpr int kOutStride = 64 * 2 + 16; // LDS row stride of a wave's 32 x 64 output block
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-
-__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
-
 struct GemmDims {
     long M;
     int N;
     int tiles;  // ceil(M / kRows)
     int S;      // head-major output only: rows per batch item
-    // strided 1x1 convolution: row r of X' = pixel (n, gs * yo, gs * xo) of the NHWC map X; gs <= 1: X' = X
-    int gs, gWo, gHoWo, gW, gHW;
+    RowGather g;
 };
-
-// row of the GEMM -> row of the NHWC input it reads (identity unless the 1x1 convolution is strided)
-template <typename D>
-__device__ __forceinline__ long gather_row(const D& dm, long row) {
-    if (dm.gs <= 1) return row;
-    const long n = row / dm.gHoWo;
-    const int rem = (int)(row - n * dm.gHoWo);
-    const int yo = rem / dm.gWo, xo = rem - yo * dm.gWo;
-    return n * dm.gHW + (long)(yo * dm.gs) * dm.gW + xo * dm.gs;
-}
 
 // HM = true (value_proj of MSDeformAttn): y is written HEAD-major, (batch, N / 32 heads, S, 32), and rows whose padding-mask
 // byte is set are written as zeros — `value.masked_fill(mask, 0)` and the re-layout the head-major attention kernel wants,
@@ -93,7 +74,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
         for (int j = 0; j < kLoads; ++j) {
             const int p = tid + 256 * j;  // piece index: row = p / kPieces, 16-byte column = p % kPieces
             long row = (long)tile * kRows + p / kPieces;
-            row = gather_row(dm, row < dm.M ? row : dm.M - 1);
+            row = gather_row(dm.g, row < dm.M ? row : dm.M - 1);
             r[j] = *reinterpret_cast<const u32x4*>(X + row * kK + (p % kPieces) * 8);
         }
     };
@@ -178,17 +159,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                 u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
                 if (grow < dm.M) {
                     if constexpr (HAS_RES) {  // + identity (same coordinates as y), then the activation
-                        const u32x4 rv = *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8);
-                        const unsigned a4[4] = {v.x, v.y, v.z, v.w}, r4[4] = {rv.x, rv.y, rv.z, rv.w};
-                        unsigned o4[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
-                            float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
-                            if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-                            o4[i] = pack_bf16x2(lo, hi);
-                        }
-                        v = u32x4{o4[0], o4[1], o4[2], o4[3]};
+                        v = add_residual_bf16x8<RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
                     }
                     *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
                 }
@@ -208,24 +179,16 @@ using namespace alo;
 namespace {
 template <int K, bool RELU, bool HAS_RES, bool HM = false>
 int launch_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N,
-                  hipStream_t stream, int S = 0, const int* gather = nullptr) {
+                  hipStream_t stream, int S = 0, const RowGather& gather = row_gather()) {
     GemmDims dm;
-    dm.M = M; dm.N = N; dm.tiles = (int)((M + kRows - 1) / kRows); dm.S = S;
-    dm.gs = gather ? gather[0] : 1;
-    dm.gWo = gather ? gather[2] : 1; dm.gHoWo = gather ? gather[1] * gather[2] : 1;
-    dm.gW = gather ? gather[4] : 1; dm.gHW = gather ? gather[3] * gather[4] : 1;
+    dm.M = M; dm.N = N; dm.tiles = (int)((M + kRows - 1) / kRows); dm.S = S; dm.g = gather;
     const size_t lds = kRows * (K * 2 + 16) + 4 * kRows * kOutStride + 4 * 64 * sizeof(float);
     const int cols = (N + 255) / 256;
     int gx = 512 / cols;  // persistent: about two workgroups per CU in total
     if (gx > dm.tiles) gx = dm.tiles;
     if (gx < 1) gx = 1;
     void* args[] = {&x, &weight, &bias, &residual, &y, &dm};
-    static unsigned long long attr_done = 0;  // per instantiation (lds depends on K only), one bit per device
-    (void)ensure_dynamic_lds(reinterpret_cast<const void*>(linear_shortk_kernel<K, RELU, HAS_RES, HM>), (int)lds, &attr_done);
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(linear_shortk_kernel<K, RELU, HAS_RES, HM>), dim3(gx, cols), dim3(256), args,
-                                   lds, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_linear_shortk: %s", hipGetErrorString(e));
-    return check_launch("alo_linear_shortk");
+    return launch<linear_shortk_kernel<K, RELU, HAS_RES, HM>>(dim3(gx, cols), 256, lds, stream, "alo_linear_shortk", args);
 }
 }  // namespace
 
@@ -236,35 +199,18 @@ extern "C" int alo_linear_shortk(const void* x, const void* weight, const void* 
                 "alo_linear_shortk: M must be positive and N a positive multiple of 64 (M=%ld N=%d)", M, N);
     ALO_REQUIRE(K == 64 || K == 128 || K == 256, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: K must be 64, 128 or 256, got %d", K);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_linear_shortk: pointers must be 16-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define ALO_GEMM_CASE(KK)                                                                                       \
-    if (K == KK) {                                                                                               \
-        if (residual) return relu ? launch_shortk<KK, true, true>(x, weight, bias, residual, y, M, N, st)       \
-                                  : launch_shortk<KK, false, true>(x, weight, bias, residual, y, M, N, st);     \
-        return relu ? launch_shortk<KK, true, false>(x, weight, bias, residual, y, M, N, st)                    \
-                    : launch_shortk<KK, false, false>(x, weight, bias, residual, y, M, N, st);                  \
-    }
-    ALO_GEMM_CASE(64) ALO_GEMM_CASE(128) ALO_GEMM_CASE(256)
-#undef ALO_GEMM_CASE
-    return ALO_ERR_UNSUPPORTED;
+    ALO_REQUIRE(aligned16(x, weight, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_shortk: pointers must be 16-byte aligned");
+    return linear_shortk_gather(x, weight, bias, residual, y, M, N, K, relu, row_gather(), static_cast<hipStream_t>(stream));
 }
 
 // 1x1 convolution with a spatial stride over an NHWC map, resident-weight flavour: the kept pixels are addressed by the tile
-// loader itself (no gathered copy of the input).  Declared in alo_hotpath.h as part of alo_conv1x1_nhwc (gemm_packed.hip).
-extern "C" int alo_internal_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y,
-                                          long M, int N, int K, int relu, const int* gather, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define ALO_GEMM_CASE(KK)                                                                                                  \
-    if (K == KK) {                                                                                                          \
-        if (residual) return relu ? launch_shortk<KK, true, true>(x, weight, bias, residual, y, M, N, st, 0, gather)       \
-                                  : launch_shortk<KK, false, true>(x, weight, bias, residual, y, M, N, st, 0, gather);     \
-        return relu ? launch_shortk<KK, true, false>(x, weight, bias, residual, y, M, N, st, 0, gather)                    \
-                    : launch_shortk<KK, false, false>(x, weight, bias, residual, y, M, N, st, 0, gather);                  \
-    }
-    ALO_GEMM_CASE(64) ALO_GEMM_CASE(128) ALO_GEMM_CASE(256)
-#undef ALO_GEMM_CASE
+// loader itself (no gathered copy of the input): alo_linear_shortk with the identity gather, alo_conv1x1_nhwc (gemm_packed.hip)
+// for unpacked weights.
+int alo::linear_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K,
+                              int relu, const RowGather& gather, hipStream_t stream) {
+    if (K == 64) return ALO_RELU_RES(launch_shortk, 64, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    if (K == 128) return ALO_RELU_RES(launch_shortk, 128, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    if (K == 256) return ALO_RELU_RES(launch_shortk, 256, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
     return fail(ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: the resident-weight kernel needs Cin in (64, 128, 256), got %d", K);
 }
 
@@ -474,10 +420,7 @@ extern "C" int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dt
     long total = (long)N * K / 8;
     unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     void* args[] = {&w, &packed, &N, &K};
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(pack_mfma_b_kernel), dim3(blocks), dim3(256), args, 0,
-                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_pack_mfma_b: %s", hipGetErrorString(e));
-    return check_launch("alo_pack_mfma_b");
+    return launch<pack_mfma_b_kernel>(blocks, 256, 0, static_cast<hipStream_t>(stream), "alo_pack_mfma_b", args);
 }
 
 extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y, long M,
@@ -486,27 +429,14 @@ extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const v
     ALO_REQUIRE(M > 0 && F > 0 && F % 256 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_ffn256: M must be positive and the hidden width a positive multiple of 256 (M=%ld F=%d)", M, F);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_ffn256: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)y) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_ffn256: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, w1, w2, y), ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: pointers must be 16-byte aligned");
     FfnDims dm;
     dm.M = M; dm.F = F; dm.tiles = (int)((M + kFfnRows - 1) / kFfnRows);
     const size_t lds = 2 * kFfnRows * kFfnStride + ((size_t)F + 256) * sizeof(float);
     int gx = dm.tiles < 512 ? dm.tiles : 512;
     void* args[] = {&x, &w1, &b1, &w2, &b2, &y, &dm};
-    if (lds > 160 * 1024) return fail(ALO_ERR_UNSUPPORTED, "alo_ffn256: hidden width %d needs %zu bytes of LDS", F, lds);
-    {   // lds grows with F: keep the largest limit set so far per device (a process-wide flag would miss a second device or a wider F)
-        static int limit_set[64] = {0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if ((int)lds > __atomic_load_n(&limit_set[dev & 63], __ATOMIC_ACQUIRE)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(ffn256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess)
-                __atomic_store_n(&limit_set[dev & 63], (int)lds, __ATOMIC_RELEASE);
-        }
-    }
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(ffn256_kernel), dim3(gx), dim3(256), args, lds,
-                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_ffn256: %s", hipGetErrorString(e));
-    return check_launch("alo_ffn256");
+    if (lds > (size_t)kLdsLimit) return fail(ALO_ERR_UNSUPPORTED, "alo_ffn256: hidden width %d needs %zu bytes of LDS", F, lds);
+    return launch<ffn256_kernel>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
 }
 
 extern "C" int alo_value_proj_head_major(const void* x, const void* weight, const void* bias, const void* padding_mask,
@@ -517,8 +447,7 @@ extern "C" int alo_value_proj_head_major(const void* x, const void* weight, cons
                 heads);
     ALO_REQUIRE(K == 64 || K == 128 || K == 256, ALO_ERR_UNSUPPORTED, "alo_value_proj_head_major: K must be 64, 128 or 256, got %d", K);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_value_proj_head_major: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)value_hm) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_value_proj_head_major: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, weight, value_hm), ALO_ERR_INVALID_ARGUMENT, "alo_value_proj_head_major: pointers must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long M = (long)batch * S;
     const int N = heads * 32;

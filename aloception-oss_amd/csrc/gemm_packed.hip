@@ -12,29 +12,13 @@
 namespace alo {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
-
 constexpr int kOutStride = 64 * 2 + 16;   // LDS row stride of a wave's 64 x 64 output block
 
 struct PackedDims {
     long M;
     int N, K;
-    // strided 1x1 convolution: row r of X' = pixel (n, gs * yo, gs * xo) of the NHWC map X; gs <= 1: X' = X
-    int gs, gWo, gHoWo, gW, gHW;
+    RowGather g;
 };
-
-__device__ __forceinline__ long gather_row(const PackedDims& dm, long row) {
-    if (dm.gs <= 1) return row;
-    const long n = row / dm.gHoWo;
-    const int rem = (int)(row - n * dm.gHoWo);
-    const int yo = rem / dm.gWo, xo = rem - yo * dm.gWo;
-    return n * dm.gHW + (long)(yo * dm.gs) * dm.gW + xo * dm.gs;
-}
 
 template <int WC, bool RELU, bool HAS_RES>
 __global__ void __launch_bounds__(256, 2)
@@ -65,7 +49,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
         for (int j = 0; j < kLoads; ++j) {
             const int p = tid + 256 * j;
             long row = row0 + p / kPieces;
-            row = gather_row(dm, row < dm.M ? row : dm.M - 1);   // rows past the end are read from the last row and never stored
+            row = gather_row(dm.g, row < dm.M ? row : dm.M - 1);   // rows past the end are read from the last row and never stored
             r[j] = *reinterpret_cast<const u32x4*>(X + row * dm.K + chunk * KC + (p % kPieces) * 8);
         }
     };
@@ -160,17 +144,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
         u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
         if (grow < dm.M) {
             if constexpr (HAS_RES) {   // + identity (same coordinates as y), then the activation
-                const u32x4 rv = *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8);
-                const unsigned a4[4] = {v.x, v.y, v.z, v.w}, r4[4] = {rv.x, rv.y, rv.z, rv.w};
-                unsigned o4[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
-                    float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
-                    if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-                    o4[i] = pack_bf16x2(lo, hi);
-                }
-                v = u32x4{o4[0], o4[1], o4[2], o4[3]};
+                v = add_residual_bf16x8<RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
             }
             *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
         }
@@ -182,24 +156,22 @@ int launch_packed(const void* x, const void* w, const void* bias, const void* re
     constexpr int WR = 4 / WC, kRows = 64 * WR, KC = 256 / WR;
     constexpr size_t xbytes = (size_t)kRows * (KC * 2 + 16), obytes = 4 * 64 * kOutStride;
     constexpr size_t lds = (xbytes > obytes ? xbytes : obytes) + 256 * sizeof(float);
-    static_assert(xbytes >= obytes || true, "");
-    const void* kern = reinterpret_cast<const void*>(linear_packed_kernel<WC, RELU, HAS_RES>);
     void* args[] = {&x, &w, &bias, &residual, &y, const_cast<PackedDims*>(&dm)};
-    hipError_t e = hipLaunchKernel(kern, dim3((unsigned)((dm.M + kRows - 1) / kRows), (unsigned)(dm.N / (64 * WC))), dim3(256), args,
-                                   lds, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_linear_packed: %s", hipGetErrorString(e));
-    return check_launch("alo_linear_packed");
+    const dim3 grid((unsigned)((dm.M + kRows - 1) / kRows), (unsigned)(dm.N / (64 * WC)));
+    return launch<linear_packed_kernel<WC, RELU, HAS_RES>>(grid, 256, lds, stream, "alo_linear_packed", args);
+}
+
+int dispatch_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, const PackedDims& dm,
+                    int relu, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dm.N % 256 == 0) return ALO_RELU_RES(launch_packed, 4, relu, residual, x, w_packed, bias, residual, y, dm, s);
+    return ALO_RELU_RES(launch_packed, 2, relu, residual, x, w_packed, bias, residual, y, dm, s);
 }
 
 }  // namespace
 }  // namespace alo
 
 using namespace alo;
-
-namespace {
-int dispatch_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, const PackedDims& dm,
-                    int relu, void* stream);
-}
 
 extern "C" int alo_linear_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, long M,
                                  int N, int K, int relu, int dtype, void* stream) {
@@ -208,52 +180,30 @@ extern "C" int alo_linear_packed(const void* x, const void* w_packed, const void
     ALO_REQUIRE(K % 256 == 0 && N % 128 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_linear_packed: K must be a multiple of 256 and N of 128 (K=%d N=%d)", K, N);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_linear_packed: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_linear_packed: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, w_packed, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: pointers must be 16-byte aligned");
     ALO_REQUIRE((M + 63) / 64 < (1L << 31), ALO_ERR_UNSUPPORTED, "alo_linear_packed: too many rows");
     PackedDims dm;
-    dm.M = M; dm.N = N; dm.K = K;
-    dm.gs = 1; dm.gWo = dm.gHoWo = dm.gW = dm.gHW = 1;
+    dm.M = M; dm.N = N; dm.K = K; dm.g = row_gather();
     return dispatch_packed(x, w_packed, bias, residual, y, dm, relu, stream);
 }
-
-extern "C" int alo_internal_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y,
-                                          long M, int N, int K, int relu, const int* gather, void* stream);
 
 extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual,
                                 void* y, int N, int H, int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream) {
     ALO_REQUIRE(x && weight && y, ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0 && stride >= 1, ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: N, H, W, stride must be positive");
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y | (uintptr_t)residual) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_conv1x1_nhwc: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, weight, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: pointers must be 16-byte aligned");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long M = (long)N * Ho * Wo;
     ALO_REQUIRE((long)H * W < (1L << 30), ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: map too large");
-    const int gather[5] = {stride, Ho, Wo, H, W};
+    const RowGather gather = row_gather(stride, Ho, Wo, H, W);
     if (!weight_is_packed) {
         ALO_REQUIRE(Cout % 64 == 0, ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: Cout must be a multiple of 64 (got %d)", Cout);
-        return alo_internal_shortk_gather(x, weight, bias, residual, y, M, Cout, Cin, relu, gather, stream);
+        return linear_shortk_gather(x, weight, bias, residual, y, M, Cout, Cin, relu, gather, static_cast<hipStream_t>(stream));
     }
     ALO_REQUIRE(Cin % 256 == 0 && Cout % 128 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_conv1x1_nhwc: packed weights need Cin %% 256 == 0 and Cout %% 128 == 0 (Cin=%d Cout=%d)", Cin, Cout);
     PackedDims dm;
-    dm.M = M; dm.N = Cout; dm.K = Cin;
-    dm.gs = stride; dm.gWo = Wo; dm.gHoWo = Ho * Wo; dm.gW = W; dm.gHW = H * W;
+    dm.M = M; dm.N = Cout; dm.K = Cin; dm.g = gather;
     return dispatch_packed(x, weight, bias, residual, y, dm, relu, stream);
 }
-
-namespace {
-int dispatch_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, const PackedDims& dm,
-                    int relu, void* stream) {
-    const int N = dm.N;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool r = relu != 0, res = residual != nullptr;
-    if (N % 256 == 0) {
-        if (res) return r ? launch_packed<4, true, true>(x, w_packed, bias, residual, y, dm, s) : launch_packed<4, false, true>(x, w_packed, bias, residual, y, dm, s);
-        return r ? launch_packed<4, true, false>(x, w_packed, bias, residual, y, dm, s) : launch_packed<4, false, false>(x, w_packed, bias, residual, y, dm, s);
-    }
-    if (res) return r ? launch_packed<2, true, true>(x, w_packed, bias, residual, y, dm, s) : launch_packed<2, false, true>(x, w_packed, bias, residual, y, dm, s);
-    return r ? launch_packed<2, true, false>(x, w_packed, bias, residual, y, dm, s) : launch_packed<2, false, false>(x, w_packed, bias, residual, y, dm, s);
-}
-}  // namespace

@@ -130,14 +130,12 @@ extern "C" int alo_mask_pyramid(const void* frame_mask, int mask_is_float, unsig
     if (int rc = fill_dims(dm, "alo_mask_pyramid", B, H, W, L, level_shapes_host, nearest_levels)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     void* args[] = {&frame_mask, &mask_flat, &dm};
-    const void* kern = mask_is_float ? reinterpret_cast<const void*>(mask_pyramid_kernel<float>)
-                                     : reinterpret_cast<const void*>(mask_pyramid_kernel<unsigned char>);
-    hipError_t e = hipLaunchKernel(kern, dim3(geo_blocks((long)B * dm.S)), dim3(256), args, 0, s);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_mask_pyramid: %s", hipGetErrorString(e));
+    const unsigned blocks = geo_blocks((long)B * dm.S);
+    if (int rc = mask_is_float ? launch<mask_pyramid_kernel<float>>(blocks, 256, 0, s, "alo_mask_pyramid", args)
+                               : launch<mask_pyramid_kernel<unsigned char>>(blocks, 256, 0, s, "alo_mask_pyramid", args))
+        return rc;
     void* args2[] = {&mask_flat, &valid_ratios, &dm};
-    e = hipLaunchKernel(reinterpret_cast<const void*>(valid_ratio_kernel), dim3((unsigned)(B * L)), dim3(64), args2, 0, s);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_mask_pyramid: %s", hipGetErrorString(e));
-    return check_launch("alo_mask_pyramid");
+    return launch<valid_ratio_kernel>((unsigned)(B * L), 64, 0, s, "alo_mask_pyramid", args2);
 }
 
 extern "C" int alo_encoder_reference_points(const float* valid_ratios, float* reference_points, int B, int L,
@@ -146,10 +144,8 @@ extern "C" int alo_encoder_reference_points(const float* valid_ratios, float* re
     GeoDims dm;
     if (int rc = fill_dims(dm, "alo_encoder_reference_points", B, 1, 1, L, level_shapes_host, 0u)) return rc;
     void* args[] = {&valid_ratios, &reference_points, &dm};
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(encoder_reference_points_kernel), dim3(geo_blocks((long)B * dm.S)),
-                                   dim3(256), args, 0, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_encoder_reference_points: %s", hipGetErrorString(e));
-    return check_launch("alo_encoder_reference_points");
+    return launch<encoder_reference_points_kernel>(geo_blocks((long)B * dm.S), 256, 0, static_cast<hipStream_t>(stream),
+                                                   "alo_encoder_reference_points", args);
 }
 
 // ---- panoptic post-processing: logits at mask resolution -> one-hot instance masks at frame resolution ----------------------------
@@ -203,8 +199,6 @@ extern "C" int alo_panoptic_onehot(const float* mask_logits, long long* onehot, 
     alo::OnehotDims dm;
     dm.B = B; dm.Q = Q; dm.h = h; dm.w = w; dm.H = H; dm.W = W; dm.thr = threshold;
     void* args[] = {&mask_logits, &onehot, &dm};
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(alo::panoptic_onehot_kernel), dim3(alo::geo_blocks((long)B * H * W) * 4), dim3(256),
-                                   args, 0, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_panoptic_onehot: %s", hipGetErrorString(e));
-    return check_launch("alo_panoptic_onehot");
+    return alo::launch<alo::panoptic_onehot_kernel>(alo::geo_blocks((long)B * H * W) * 4, 256, 0, static_cast<hipStream_t>(stream),
+                                                    "alo_panoptic_onehot", args);
 }

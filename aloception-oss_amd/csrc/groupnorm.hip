@@ -278,29 +278,22 @@ int groupnorm_rows_impl(const void* x, const void* weight, const void* bias, voi
                 C, groups);
     ALO_REQUIRE(y_batch_stride >= (long)HW * C && y_batch_stride % 8 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_groupnorm_rows: y_batch_stride must cover HW * C and keep rows 16-byte aligned");
-    ALO_REQUIRE((((uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)y | (uintptr_t)workspace) & 15) == 0,
-                ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x, weight, bias, y, workspace), ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: pointers must be 16-byte aligned");
     GnDims dm;
     dm.HW = HW; dm.C = C; dm.groups = groups; dm.nchunks = (HW + kGnRows - 1) / kGnRows;
     dm.y_batch_stride = y_batch_stride; dm.eps = eps; dm.relu = relu ? 1 : 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const void* stats = wide ? reinterpret_cast<const void*>(groupnorm_stats_kernel)
-                             : (cpg == 4 ? reinterpret_cast<const void*>(groupnorm_stats_small_kernel<4>)
-                                         : reinterpret_cast<const void*>(groupnorm_stats_small_kernel<2>));
-    const void* apply = wide ? reinterpret_cast<const void*>(groupnorm_apply_kernel)
-                             : (cpg == 4 ? reinterpret_cast<const void*>(groupnorm_apply_small_kernel<4>)
-                                         : reinterpret_cast<const void*>(groupnorm_apply_small_kernel<2>));
-    {
-        void* args[] = {&x, &workspace, &dm};
-        hipError_t e = hipLaunchKernel(stats, dim3(dm.nchunks, B), dim3(kGnThreads), args, 0, s);
-        if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_groupnorm_rows: %s", hipGetErrorString(e));
-    }
-    {
-        void* args[] = {&x, &workspace, &weight, &bias, &y, &dm};
-        hipError_t e = hipLaunchKernel(apply, dim3(dm.nchunks, B), dim3(kGnThreads), args, 0, s);
-        if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_groupnorm_rows: %s", hipGetErrorString(e));
-    }
-    return check_launch("alo_groupnorm_rows");
+    const dim3 grid(dm.nchunks, B);
+    const char* what = "alo_groupnorm_rows";
+    void* stats_args[] = {&x, &workspace, &dm};
+    if (int rc = wide       ? launch<groupnorm_stats_kernel>(grid, kGnThreads, 0, s, what, stats_args)
+                 : cpg == 4 ? launch<groupnorm_stats_small_kernel<4>>(grid, kGnThreads, 0, s, what, stats_args)
+                            : launch<groupnorm_stats_small_kernel<2>>(grid, kGnThreads, 0, s, what, stats_args))
+        return rc;
+    void* apply_args[] = {&x, &workspace, &weight, &bias, &y, &dm};
+    return wide       ? launch<groupnorm_apply_kernel>(grid, kGnThreads, 0, s, what, apply_args)
+           : cpg == 4 ? launch<groupnorm_apply_small_kernel<4>>(grid, kGnThreads, 0, s, what, apply_args)
+                      : launch<groupnorm_apply_small_kernel<2>>(grid, kGnThreads, 0, s, what, apply_args);
 }
 }  // namespace
 
@@ -320,8 +313,7 @@ extern "C" int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* o
     ALO_REQUIRE(BQ > 0 && Q > 0 && BQ % Q == 0 && C > 0 && C % 8 == 0 && h > 0 && w > 0 && H > 0 && W > 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_upsample_add_nhwc: BQ must be a positive multiple of Q and C a positive multiple of 8 (BQ=%d Q=%d C=%d)", BQ, Q, C);
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_upsample_add_nhwc: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)x_low | (uintptr_t)fpn | (uintptr_t)out) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_upsample_add_nhwc: pointers must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(x_low, fpn, out), ALO_ERR_INVALID_ARGUMENT, "alo_upsample_add_nhwc: pointers must be 16-byte aligned");
     UpAddDims dm;
     dm.Q = Q; dm.C8 = C / 8; dm.h = h; dm.w = w; dm.H = H; dm.W = W;
     dm.total = (long)BQ * H * W * dm.C8;
@@ -329,8 +321,5 @@ extern "C" int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* o
     long blocks = (dm.total + 255) / 256;
     if (blocks > 256L * 32) blocks = 256L * 32;
     void* args[] = {&x_low, &fpn, &out, &dm};
-    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(upsample_add_nhwc_kernel), dim3((unsigned)blocks), dim3(256), args, 0,
-                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_upsample_add_nhwc: %s", hipGetErrorString(e));
-    return check_launch("alo_upsample_add_nhwc");
+    return launch<upsample_add_nhwc_kernel>((unsigned)blocks, 256, 0, static_cast<hipStream_t>(stream), "alo_upsample_add_nhwc", args);
 }

@@ -1624,34 +1624,24 @@ Dims make_dims(const Shape& s, int G, long target_blocks = 4096) {
     return d;
 }
 
-// The one launch path of this file.  A launch that asks for more than 48 KiB of dynamic LDS raises the kernel's limit to the whole
-// LDS first, once per (kernel, device).
-constexpr int kLdsLimit = 160 * 1024;
+// The generic kernels' dynamic LDS grows with L * P: name that before the launch path (common.hpp) refuses the size in its own words.
 template <auto kernel>
-int launch(unsigned nblocks, int threads, size_t lds, hipStream_t stream, const char* what, void** args) {
-    if (lds > (size_t)kLdsLimit) return fail(ALO_ERR_UNSUPPORTED, "%s: L*P too large for LDS (%zu bytes)", what, lds);
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    if (lds > 48 * 1024) {
-        static unsigned long long attr_done = 0;   // one bit per device
-        hipError_t e = ensure_dynamic_lds(fn, kLdsLimit, &attr_done);
-        if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-    }
-    hipError_t e = hipLaunchKernel(fn, dim3(nblocks), dim3(threads), args, lds, stream);
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-    return check_launch(what);
+int launch_lp(unsigned nblocks, size_t lds, hipStream_t stream, const char* what, void** args) {
+    ALO_REQUIRE(lds <= (size_t)kLdsLimit, ALO_ERR_UNSUPPORTED, "%s: L*P too large for LDS (%zu bytes)", what, lds);
+    return launch<kernel>(nblocks, kThreads, lds, stream, what, args);
 }
 
 #define ALO_FWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
     if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
         const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(FwdDesc<CT>) + 16); \
         if (fused)                                                                                                 \
-            return launch<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), true>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_forward_fused", args); \
-        return launch<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), false>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_forward", args);     \
+            return launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), true>>(lp.dm.nblocks, lds, stream, "alo_msda_forward_fused", args); \
+        return launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), false>>(lp.dm.nblocks, lds, stream, "alo_msda_forward", args);     \
     }
 #define ALO_BWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
     if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
         const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(BwdDesc<CT>) + 16); \
-        return launch<msda_bwd_kernel<T, LT, CT, VEC, G, LPCT>>(lp.dm.nblocks, kThreads, lds, stream, "alo_msda_backward", args); \
+        return launch_lp<msda_bwd_kernel<T, LT, CT, VEC, G, LPCT>>(lp.dm.nblocks, lds, stream, "alo_msda_backward", args); \
     }
 // every (vector width, group) pair a plan can produce for one dtype
 #define ALO_ALL_CASES(CASE, T, LT, CT, VECW)                                                       \
@@ -1778,8 +1768,8 @@ int forward_impl(const void* value, const int32_t* spatial_shapes, const int32_t
     ALO_REQUIRE(out, ALO_ERR_INVALID_ARGUMENT, "alo_msda_forward: out is null");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const bool fused = a.fused = ref != nullptr;
-    a.aligned = (((uintptr_t)value | (uintptr_t)out) & 15) == 0;
-    a.in_aligned = (((uintptr_t)loc | (uintptr_t)attn | (uintptr_t)ref) & 15) == 0;
+    a.aligned = aligned16(value, out);
+    a.in_aligned = aligned16(loc, attn, ref);
     LaunchPlan lp = plan_forward(s, a);
     const unsigned nblocks = lp.dm.nblocks;
     void* args[] = {&value, &spatial_shapes, &level_start_index, &loc, &attn, &ref, &out, &lp.dm, &lp.rd};   // rd: resident kernel only
@@ -1950,9 +1940,8 @@ extern "C" int alo_msda_backward_hinted(const void* value, const int32_t* spatia
     if (int rc = validate(s, loc_dtype)) return rc;
     ALO_REQUIRE(grad_out && grad_value && grad_sampling_loc && grad_attn_weight, ALO_ERR_INVALID_ARGUMENT, "alo_msda_backward: null gradient pointer");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const bool aligned = (((uintptr_t)value | (uintptr_t)grad_out) & 15) == 0;
-    const bool all_aligned = aligned && (((uintptr_t)sampling_loc | (uintptr_t)attn_weight | (uintptr_t)grad_value |
-                                          (uintptr_t)grad_sampling_loc | (uintptr_t)grad_attn_weight) & 15) == 0;
+    const bool aligned = aligned16(value, grad_out);
+    const bool all_aligned = aligned && aligned16(sampling_loc, attn_weight, grad_value, grad_sampling_loc, grad_attn_weight);
     LaunchPlan lp = plan_backward(s, host_spatial_shapes, aligned, all_aligned);
     ALO_REQUIRE(lp.route >= 0, ALO_ERR_UNSUPPORTED, "alo_msda_backward: grid too large");
     hipError_t e = hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * (value_dtype == ALO_F64 ? 8 : 4), stream);

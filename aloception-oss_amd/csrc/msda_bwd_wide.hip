@@ -634,15 +634,13 @@ int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* 
     if (plan_only) return ALO_OK;
     wd.dbg = getenv("ALO_WIDE_DBG") ? atoi(getenv("ALO_WIDE_DBG")) : 0;
     void* args[] = {&value, &shapes, &lstart, &loc, &attn, &grad_out, &grad_value, &grad_loc, &grad_attn, &wd};
-    const int which = (value_dtype == ALO_F32 ? 0 : 1) + (D == 32 ? 0 : 2);
-    const void* fns[4] = {reinterpret_cast<const void*>(msda_bwd_wide_kernel<float, 32>), reinterpret_cast<const void*>(msda_bwd_wide_kernel<bf16_t, 32>),
-                          reinterpret_cast<const void*>(msda_bwd_wide_kernel<float, 64>), reinterpret_cast<const void*>(msda_bwd_wide_kernel<bf16_t, 64>)};
-    static unsigned long long attr_done[4] = {0, 0, 0, 0};   // one bit per device
-    hipError_t ea = ensure_dynamic_lds(fns[which], wide_lds(D), &attr_done[which]);
-    if (ea != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward (wide): %s", hipGetErrorString(ea));
-    hipError_t el = hipLaunchKernel(fns[which], dim3(wd.nblocks), dim3(kWThreads), args, wide_lds(D), stream);
-    if (el != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward (wide): %s", hipGetErrorString(el));
-    return check_launch("alo_msda_backward (wide)");
+    const char* what = "alo_msda_backward (wide)";
+    if (D == 32) {
+        if (value_dtype == ALO_F32) return launch<msda_bwd_wide_kernel<float, 32>>(wd.nblocks, kWThreads, wide_lds(32), stream, what, args);
+        return launch<msda_bwd_wide_kernel<bf16_t, 32>>(wd.nblocks, kWThreads, wide_lds(32), stream, what, args);
+    }
+    if (value_dtype == ALO_F32) return launch<msda_bwd_wide_kernel<float, 64>>(wd.nblocks, kWThreads, wide_lds(64), stream, what, args);
+    return launch<msda_bwd_wide_kernel<bf16_t, 64>>(wd.nblocks, kWThreads, wide_lds(64), stream, what, args);
 }
 
 }  // namespace alo

@@ -12,13 +12,6 @@
 namespace alo {
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-__device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
-    union { u32x4 u; bf16x8_t b; } x;
-    x.u = v;
-    return x.b;
-}
-
 constexpr int kPoolRows = 8, kPoolCols = 7;                          // pooled pixels per tile
 constexpr int kConvRows = 2 * kPoolRows + 1, kConvCols = 2 * kPoolCols + 1;   // 17 x 15 convolution outputs
 constexpr int kConvPix = kConvRows * kConvCols;                      // 255
@@ -206,8 +199,7 @@ extern "C" int alo_stem_conv_pool(const void* x, const void* w_packed, const voi
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0, ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: N, H, W must be positive");
     ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_stem_conv_pool: bf16 only (dtype %d)", dtype);
-    ALO_REQUIRE((((uintptr_t)w_packed | (uintptr_t)y) & 15) == 0, ALO_ERR_INVALID_ARGUMENT,
-                "alo_stem_conv_pool: w_packed and y must be 16-byte aligned");
+    ALO_REQUIRE(aligned16(w_packed, y), ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: w_packed and y must be 16-byte aligned");
     StemDims dm;
     dm.N = N; dm.H = H; dm.W = W;
     dm.Hc = (H - 1) / 2 + 1; dm.Wc = (W - 1) / 2 + 1;        // (H + 6 - 7) / 2 + 1
@@ -217,10 +209,7 @@ extern "C" int alo_stem_conv_pool(const void* x, const void* w_packed, const voi
     dm.tiles_x = (dm.Wp + kPoolCols - 1) / kPoolCols;
     const long ntiles = (long)dm.tiles_y * dm.tiles_x * N;
     ALO_REQUIRE(ntiles < (1L << 30), ALO_ERR_UNSUPPORTED, "alo_stem_conv_pool: image batch too large");
-    const void* kern = reinterpret_cast<const void*>(stem_conv_pool_kernel);
     void* args[] = {&x, &w_packed, &bias, &y, &dm};
     const unsigned grid = (unsigned)(ntiles < 768 ? ntiles : 768);   // 256 CUs x 3 resident workgroups
-    hipError_t e = hipLaunchKernel(kern, dim3(grid), dim3(kStemThreads), args, kStemLds, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_stem_conv_pool: %s", hipGetErrorString(e));
-    return check_launch("alo_stem_conv_pool");
+    return launch<stem_conv_pool_kernel>(grid, kStemThreads, kStemLds, static_cast<hipStream_t>(stream), "alo_stem_conv_pool", args);
 }

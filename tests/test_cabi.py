@@ -11,8 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "alo_hotpath.h")
 
 
-def declared_functions():
-    text = open(HEADER).read()
+def declared_functions(header=HEADER):
+    text = open(header).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(alo_[a-z0-9_]+)\s*\(", text)))
 
@@ -30,6 +30,21 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} missing from {alo_hip.LIB_PATH}"
     assert lib.alo_abi_version() == 2
     assert lib.alo_last_error() is not None
+
+
+def test_library_exports_nothing_but_the_declared_symbols():
+    """Every alo_* function in the dynamic symbol table is declared in a public header: helpers shared between the library's
+    own sources have C++ linkage (namespace alo) and never look like entry points."""
+    import subprocess
+
+    out = subprocess.run(["readelf", "--dyn-syms", "-W", alo_hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set()
+    for line in out.splitlines():
+        cols = line.split()   # Num: Value Size Type Bind Vis Ndx Name
+        if len(cols) == 8 and cols[3] == "FUNC" and cols[6] != "UND" and cols[7].startswith("alo_"):
+            exported.add(cols[7].split("@")[0])
+    declared = set(declared_functions()) | set(declared_functions(os.path.join(ROOT, "include", "alo_corr_alt.h")))
+    assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
 
 
 def test_no_torch_symbols_in_the_abi():
