@@ -1,4 +1,5 @@
-"""ctypes binding of ``libalo_hotpath.so`` (the C ABI declared in ``include/alo_hotpath.h`` and ``include/alo_corr_alt.h``).
+"""ctypes binding of ``libalo_hotpath.so`` (the C ABI declared in ``include/alo_hotpath.h`` and ``include/alo_corr_alt.h``) and of
+``libalo_two_stage.so`` (``include/alo_two_stage.h``).
 
 This is the only place the host code touches the native library.  PyTorch is used for what it is good at here —
 device memory, streams, dtypes — and nothing else: every function below takes torch tensors, validates them the way
@@ -1268,3 +1269,141 @@ def panoptic_onehot(mask_logits, frame_size, threshold=0.5):
         with torch.cuda.device(x.device), _timed("panoptic_onehot", 8.0 * out.numel()):
             _check(lib().alo_panoptic_onehot(_ptr(x), _ptr(out), b_, q, h, w_, H, W, float(threshold), _stream(x.device)))
     return out
+
+
+# ---- two-stage Deformable-DETR: proposals, row masking, decoder queries (libalo_two_stage.so, include/alo_two_stage.h) ------------
+TWO_STAGE_LIB_PATH = os.path.join(_PKG_ROOT, "libalo_two_stage.so")
+_two_stage_lib = None
+
+
+def two_stage_lib():
+    """The loaded libalo_two_stage.so (it reports errors through libalo_hotpath.so's ``alo_last_error``); raises
+    :class:`HotpathUnavailable` when it is missing or has another ABI."""
+    global _two_stage_lib
+    if _two_stage_lib is None:
+        lib()   # first: the two-stage library links against it
+        if not os.path.exists(TWO_STAGE_LIB_PATH):
+            raise HotpathUnavailable(f"{TWO_STAGE_LIB_PATH} is missing: build it with `make -C {CSRC_DIR}` (hipcc, --offload-arch=gfx950)")
+        try:
+            handle = ctypes.CDLL(TWO_STAGE_LIB_PATH)
+        except OSError as e:  # pragma: no cover - depends on the box
+            raise HotpathUnavailable(f"cannot load {TWO_STAGE_LIB_PATH}: {e}") from e
+        c = ctypes
+        vp, ip = c.c_void_p, c.c_int
+        handle.alo_two_stage_abi_version.restype = ip
+        handle.alo_two_stage_abi_version.argtypes = []
+        handle.alo_encoder_proposals.restype = ip
+        handle.alo_encoder_proposals.argtypes = [vp, vp, vp, ip, ip, c.POINTER(c.c_int), vp]
+        handle.alo_encoder_proposals_masked.restype = ip
+        handle.alo_encoder_proposals_masked.argtypes = [vp, vp, vp, vp, vp, ip, ip, c.POINTER(c.c_int), ip, ip, vp]
+        handle.alo_mask_rows.restype = ip
+        handle.alo_mask_rows.argtypes = [vp, vp, vp, c.c_long, ip, ip, vp]
+        handle.alo_proposal_queries.restype = ip
+        handle.alo_proposal_queries.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, vp]
+        if handle.alo_two_stage_abi_version() != 1:
+            raise HotpathUnavailable(f"{TWO_STAGE_LIB_PATH} has ABI version {handle.alo_two_stage_abi_version()}, expected 1")
+        _two_stage_lib = handle
+    return _two_stage_lib
+
+
+def encoder_proposals_supported(mask_flatten, shapes):
+    """CUDA, contiguous (B, S) bool / uint8 mask of fewer than 2^31 tokens over at most 8 non-empty levels.  (The mask carries no
+    gradient; whether the caller's other tensors do is the caller's question: :func:`fusable`.)"""
+    return (mask_flatten.is_cuda and mask_flatten.dim() == 2 and mask_flatten.dtype in (torch.bool, torch.uint8)
+            and mask_flatten.is_contiguous() and 0 < len(shapes) <= 8 and mask_flatten.shape[0] > 0 and mask_flatten.numel() < 2 ** 31
+            and all(int(h) > 0 and int(w) > 0 for h, w in shapes)
+            and sum(int(h) * int(w) for h, w in shapes) == mask_flatten.shape[1])
+
+
+def encoder_proposals(mask_flatten, shapes):
+    """Box proposal of every encoder token in one kernel -> (proposals (B, S, 4) float32: inverse sigmoid of (cx, cy, w, h),
+    +inf where the token is dropped; keep (B, S) bool).  Equals ``encoder_output_proposals`` of
+    alonet.deformable_detr.deformable_transformer in float32: same ``keep``, same +inf pattern."""
+    if not encoder_proposals_supported(mask_flatten, shapes):
+        raise RuntimeError("encoder_proposals: needs a contiguous CUDA (B, S) bool / uint8 mask and 1..8 non-empty levels whose sizes sum to S")
+    B, S = mask_flatten.shape
+    arr, L = _host_shapes(shapes)
+    proposals = torch.empty((B, S, 4), dtype=torch.float32, device=mask_flatten.device)
+    keep = torch.empty((B, S), dtype=torch.uint8, device=mask_flatten.device)
+    with torch.cuda.device(mask_flatten.device), _timed(f"encoder_proposals/S={S}", 18.0 * B * S):
+        _check(two_stage_lib().alo_encoder_proposals(_ptr(mask_flatten), _ptr(proposals), _ptr(keep), B, L, arr,
+                                                     _stream(mask_flatten.device)))
+    return proposals, keep.view(torch.bool)
+
+
+def encoder_proposals_masked_supported(mask_flatten, shapes, memory):
+    """What :func:`encoder_proposals` needs of the mask and :func:`mask_rows` of the rows, for memory (B, S, C) on the mask's device."""
+    return (encoder_proposals_supported(mask_flatten, shapes) and memory.dim() == 3 and memory.device == mask_flatten.device
+            and tuple(memory.shape[:2]) == tuple(mask_flatten.shape) and mask_rows_supported(memory, mask_flatten))
+
+
+def encoder_proposals_masked(mask_flatten, shapes, memory):
+    """:func:`encoder_proposals` and :func:`mask_rows` in one launch -> (proposals, keep, memory with the dropped rows zeroed):
+    0.026 against 0.029 ms for the two launches at the headline size (docs/experiments.md)."""
+    if not encoder_proposals_masked_supported(mask_flatten, shapes, memory):
+        raise RuntimeError("encoder_proposals_masked: needs what encoder_proposals and mask_rows need, memory (B, S, C) on the mask's device")
+    B, S = mask_flatten.shape
+    arr, L = _host_shapes(shapes)
+    proposals = torch.empty((B, S, 4), dtype=torch.float32, device=mask_flatten.device)
+    keep = torch.empty((B, S), dtype=torch.uint8, device=mask_flatten.device)
+    out = torch.empty_like(memory)
+    with torch.cuda.device(memory.device), _timed(f"encoder_proposals_masked/S={S}", 2.0 * memory.element_size() * memory.numel() + 18.0 * B * S):
+        _check(two_stage_lib().alo_encoder_proposals_masked(_ptr(mask_flatten), _ptr(proposals), _ptr(keep), _ptr(memory), _ptr(out), B, L,
+                                                            arr, memory.shape[-1], _DTYPE_CODE[memory.dtype], _stream(memory.device)))
+    return proposals, keep.view(torch.bool), out
+
+
+def mask_rows_supported(memory, keep):
+    """CUDA, contiguous fp32 / bf16 rows of a multiple of 8 channels, one bool / uint8 per row, 16-byte aligned."""
+    return (memory.is_cuda and memory.dtype in (torch.float32, torch.bfloat16) and memory.is_contiguous() and memory.dim() >= 2
+            and memory.shape[-1] % 8 == 0 and memory.numel() > 0 and memory.data_ptr() % 16 == 0
+            and keep.is_cuda and keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous()
+            and tuple(keep.shape) == tuple(memory.shape[:-1]))
+
+
+def mask_rows(memory, keep):
+    """``memory.masked_fill(~keep[..., None], 0)`` in one pass of 16-byte vectors; dropped rows are written, not read."""
+    if not mask_rows_supported(memory, keep):
+        raise RuntimeError("mask_rows: needs contiguous CUDA fp32 / bf16 rows with C % 8 == 0 and one bool / uint8 `keep` per row")
+    C = memory.shape[-1]
+    rows = memory.numel() // C
+    out = torch.empty_like(memory)
+    with torch.cuda.device(memory.device), _timed(f"mask_rows/rows={rows}", 2.0 * memory.element_size() * memory.numel() + rows):
+        _check(two_stage_lib().alo_mask_rows(_ptr(memory), _ptr(keep), _ptr(out), rows, C, _DTYPE_CODE[memory.dtype],
+                                             _stream(memory.device)))
+    return out
+
+
+def proposal_queries_supported(coords_unact, topk, dtype):
+    return (coords_unact.is_cuda and coords_unact.dtype == torch.float32 and coords_unact.dim() == 3 and coords_unact.shape[2] == 4
+            and coords_unact.is_contiguous() and coords_unact.numel() > 0 and coords_unact.data_ptr() % 16 == 0
+            and topk.is_cuda and topk.dtype == torch.int64 and topk.dim() == 2 and topk.shape[0] == coords_unact.shape[0]
+            and topk.is_contiguous() and topk.numel() > 0 and dtype in (torch.float32, torch.bfloat16))
+
+
+def proposal_dim_t(device, owner=None):
+    """(64,) float32 frequencies of the proposal embedding, ``10000 ** (k / 64)``, by the torch ops the torch formulation uses, on
+    ``device``.  With ``owner`` (a weight on that device) they are kept on it with the other derived tensors (:func:`derived`)."""
+    def build():
+        return 10000 ** (torch.arange(64, dtype=torch.float32, device=device) / 64)
+    if owner is None or owner.device != torch.device(device):
+        return build()
+    return derived(owner, "proposal_dim_t", (owner,), build)
+
+
+def proposal_queries(coords_unact, topk, dtype, owner=None):
+    """Decoder queries of the selected proposals in one kernel: coords_unact (B, S, 4) float32, topk (B, K) int64 ->
+    (reference_points (B, K, 4) float32 = sigmoid of the gathered rows, embed (B, K, 512) ``dtype`` = their sine embedding,
+    ``get_proposal_pos_embed``).  ``owner``: the weight the embedding feeds (``pos_trans.weight``), which keeps the 64 frequencies
+    (:func:`proposal_dim_t`); without one they are computed per call."""
+    if not proposal_queries_supported(coords_unact, topk, dtype):
+        raise RuntimeError("proposal_queries: needs contiguous CUDA (B, S, 4) float32 coordinates, (B, K) int64 indices, fp32 / bf16 output")
+    B, S, _ = coords_unact.shape
+    K = topk.shape[1]
+    ref = torch.empty((B, K, 4), dtype=torch.float32, device=coords_unact.device)
+    embed = torch.empty((B, K, 512), dtype=dtype, device=coords_unact.device)
+    dim_t = proposal_dim_t(coords_unact.device, owner)
+    with torch.cuda.device(coords_unact.device), _timed(f"proposal_queries/K={K}", B * K * (8.0 + 32.0 + 512.0 * embed.element_size())):
+        _check(two_stage_lib().alo_proposal_queries(_ptr(coords_unact), _ptr(topk), _ptr(dim_t), _ptr(ref), _ptr(embed), B, S, K,
+                                                    _DTYPE_CODE[dtype], _stream(coords_unact.device)))
+    return ref, embed

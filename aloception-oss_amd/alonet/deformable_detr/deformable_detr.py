@@ -47,6 +47,10 @@ class DeformableDETR(nn.Module):
     num_feature_levels : int        pyramid levels sampled by the attention (4)
     aux_loss : bool                 also return the predictions of the intermediate decoder layers
     with_box_refine : bool          iterative bounding-box refinement
+                                    (a ``transformer`` built with ``two_stage=True`` requires it: its queries are the encoder's
+                                    best ``num_queries`` box proposals, scored by one extra pair of detection heads, and no
+                                    ``query_embed`` exists; the forward then also returns ``enc_outputs_class`` (B, S, C) and
+                                    ``enc_outputs_coord`` (B, S, 4), the proposals of every encoder token)
     weights : str                   checkpoint path or registered name
     device : torch.device           defaults to cuda (the deformable attention op has no CPU implementation)
     activation_fn : "sigmoid" | "softmax"   (softmax adds a background class)
@@ -88,7 +92,11 @@ class DeformableDETR(nn.Module):
             self.input_proj = nn.ModuleList(projs)
         else:
             self.input_proj = nn.ModuleList([proj(backbone.num_channels[0], kernel_size=1)])
-        self.query_embed = nn.Embedding(num_queries, hidden * 2)
+        self.two_stage = bool(getattr(transformer, "two_stage", False))
+        if self.two_stage and not with_box_refine:
+            raise ValueError("a two-stage transformer needs with_box_refine=True: the proposals are scored by per-layer detection heads")
+        if not self.two_stage:
+            self.query_embed = nn.Embedding(num_queries, hidden * 2)
         self.transformer = transformer
         self.class_embed = nn.Linear(hidden, num_classes)
         self.bbox_embed = MLP(hidden, hidden, 4, 3)
@@ -104,11 +112,17 @@ class DeformableDETR(nn.Module):
             nn.init.constant_(p[0].bias, 0)
 
         self.num_decoder_layers = num_pred = transformer.decoder.num_layers
+        if self.two_stage:
+            num_pred += 1   # the last pair of heads scores the encoder's proposals
         if with_box_refine:
             self.class_embed = _get_clones(self.class_embed, num_pred)
             self.bbox_embed = _get_clones(self.bbox_embed, num_pred)
             nn.init.constant_(self.bbox_embed[0].layers[-1].bias.data[2:], -2.0)
             self.transformer.decoder.bbox_embed = self.bbox_embed
+            if self.two_stage:
+                self.transformer.decoder.class_embed = self.class_embed
+                for box_embed in self.bbox_embed:   # as the published two-stage model: every head starts from the proposal itself
+                    nn.init.constant_(box_embed.layers[-1].bias.data[2:], 0.0)
         else:
             nn.init.constant_(self.bbox_embed.layers[-1].bias.data[2:], -2.0)
             self.class_embed = nn.ModuleList([self.class_embed for _ in range(num_pred)])  # one shared head
@@ -179,7 +193,8 @@ class DeformableDETR(nn.Module):
         if lazy_pos:
             kwargs = dict(kwargs, pos_encoder=self.backbone[1])
 
-        transformer_out = self.transformer(srcs, masks, pos[1:], self.query_embed.weight, **kwargs)
+        query_embed = None if self.two_stage else self.query_embed.weight
+        transformer_out = self.transformer(srcs, masks, pos[1:], query_embed, **kwargs)
         if self.return_bb_outputs:
             features[-1] = (srcs[-2], masks[-2])
         return self.forward_heads(transformer_out, bb_outputs=(features, pos[:-1]))
@@ -280,6 +295,9 @@ class DeformableDETR(nn.Module):
             out["dec_outputs"] = transformer_outputs["hs"]
         if self.return_enc_outputs:
             out["enc_outputs"] = transformer_outputs["memory"][-2]
+        if transformer_outputs.get("enc_outputs_class") is not None:   # two-stage: the encoder's proposal of every token
+            out["enc_outputs_class"] = transformer_outputs["enc_outputs_class"]
+            out["enc_outputs_coord"] = transformer_outputs["enc_outputs_coord_unact"].sigmoid()
         if self.return_bb_outputs:
             features, pos = bb_outputs
             for lvl, (src, mask) in enumerate(features):
@@ -416,11 +434,13 @@ class DeformableDETR(nn.Module):
         return DeformableTransformerDecoder(layer, dec_layers, return_intermediate_dec)
 
     def build_transformer(self, hidden_dim=256, dropout=0.1, nheads=8, dim_feedforward=1024, enc_layers=6, dec_layers=6,
-                          num_feature_levels=4, dec_n_points=4, enc_n_points=4, return_intermediate_dec=True):
+                          num_feature_levels=4, dec_n_points=4, enc_n_points=4, return_intermediate_dec=True, two_stage=False,
+                          num_queries=300):
         decoder = self.build_decoder(dec_layers=dec_layers, return_intermediate_dec=return_intermediate_dec,
                                      hidden_dim=hidden_dim, num_feature_levels=num_feature_levels)
         return DeformableTransformer(decoder=decoder, d_model=hidden_dim, dropout=dropout, nhead=nheads,
                                      dim_feedforward=dim_feedforward, num_encoder_layers=enc_layers,
                                      num_decoder_layers=dec_layers, num_feature_levels=num_feature_levels,
                                      dec_n_points=dec_n_points, enc_n_points=enc_n_points,
-                                     return_intermediate_dec=return_intermediate_dec)
+                                     return_intermediate_dec=return_intermediate_dec, two_stage=two_stage,
+                                     two_stage_num_proposals=num_queries)

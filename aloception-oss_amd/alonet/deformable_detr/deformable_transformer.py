@@ -2,10 +2,12 @@
 
 Module tree, parameter names and arithmetic follow alonet/deformable_detr/deformable_transformer.py:22-633 so that a
 reference checkpoint's ``transformer.*`` keys load unchanged; every attention gather goes through
-``MSDeformAttn`` -> ``MSDeformAttnFunction`` -> HIP.  The two-stage variant (never built by the reference's R50
-constructors) is not provided.
+``MSDeformAttn`` -> ``MSDeformAttnFunction`` -> HIP.  The two-stage variant (``two_stage=True``: the encoder's tokens propose
+the decoder's queries, reference :108-112, :130-177, :248-263) is restated at the end of this file's helpers; at inference its
+element-wise passes run on the kernels of csrc/two_stage.hip.
 """
 import copy
+import math
 
 import torch
 import torch.nn.functional as F
@@ -78,6 +80,55 @@ def _ffn(linear1, activation, linear2, x):
         h = alo_hip.linear_auto(x, linear1.weight, linear1.bias, relu=True)
         return alo_hip.linear_auto(h, linear2.weight, linear2.bias)
     return linear2(activation(linear1(x)))
+
+
+PROPOSAL_EMBED_DIM = 512   # 4 box components x 128 sine features: fixed by the reference (:131), hence d_model = 256 for two-stage
+
+
+def encoder_output_proposals(mask_flatten, shapes, dtype=torch.float32):
+    """One box proposal per encoder token, from the padding mask alone (reference :145-171).
+
+    mask_flatten (B, S) bool, True on padding; shapes [(h_l, w_l)] as Python ints.  Returns ``(proposals, keep)``:
+    ``proposals`` (B, S, 4) ``dtype`` holds ``log(p / (1 - p))`` of ``p = ((x + 0.5) / valid_W, (y + 0.5) / valid_H, wh, wh)``
+    with ``wh = 0.05 * 2^level``, where ``valid_W`` / ``valid_H`` count the un-padded tokens of the level's first row / first
+    column per image; ``keep`` (B, S) bool is True where the token is not padding and ``0.01 < p < 0.99`` holds in all four
+    components.  Tokens outside ``keep`` get ``+inf`` in all four components.
+
+    The model calls it in float32 whatever its own dtype, as the reference does (its grid is float32 and its counts are
+    integers): nothing here depends on a parameter, so there is nothing to differentiate.  ``dtype=torch.float64`` is the
+    yardstick the float32 kernel (``alo_hip.encoder_proposals``) is measured against.
+
+    Two properties of the reference are kept on purpose:
+      * a dropped token is only marked by ``+inf`` coordinates and a zeroed memory row.  Its class logit, computed from the
+        zeroed row, is finite (the heads' biases), so ``topk`` can still select it;
+      * a level whose first row (or column) is entirely padding has ``valid_W = 0``: ``p = inf`` fails the window test, so the
+        whole level is dropped for that image — no NaN appears.
+    """
+    device = mask_flatten.device
+    B = mask_flatten.shape[0]
+    per_level, start = [], 0
+    for lvl, (h, w) in enumerate(shapes):
+        free = ~mask_flatten[:, start:start + h * w].view(B, h, w)
+        valid_h = free[:, :, 0].sum(1).to(dtype).view(B, 1, 1)
+        valid_w = free[:, 0, :].sum(1).to(dtype).view(B, 1, 1)
+        cy = ((torch.arange(h, dtype=dtype, device=device) + 0.5).view(1, h, 1) / valid_h).expand(B, h, w)
+        cx = ((torch.arange(w, dtype=dtype, device=device) + 0.5).view(1, 1, w) / valid_w).expand(B, h, w)
+        side = torch.full((B, h, w), 0.05 * 2.0 ** lvl, dtype=dtype, device=device)
+        per_level.append(torch.stack((cx, cy, side, side), -1).view(B, h * w, 4))
+        start += h * w
+    p = torch.cat(per_level, 1)
+    keep = ((p > 0.01) & (p < 0.99)).all(-1) & ~mask_flatten
+    proposals = torch.log(p / (1 - p)).masked_fill(~keep.unsqueeze(-1), float("inf"))
+    return proposals, keep
+
+
+def proposal_pos_embed(coords_unact):
+    """Sine embedding of un-activated boxes (reference :130-143): (..., 4) -> (..., 512) in the input's dtype, component-major;
+    within a component ``sin(a_i)`` at even and ``cos(a_i)`` at odd positions, ``a_i = sigmoid(c) * 2 pi / 10000^(2 floor(i / 2) / 128)``.
+    The frequencies are float32 whatever the input's dtype, as in the reference.  ``+-inf`` gives sigmoid 1 / 0: finite output."""
+    dim_t = 10000 ** (torch.arange(64, dtype=torch.float32, device=coords_unact.device) / 64)   # one per (sin, cos) pair; 2 k / 128 = k / 64 exactly
+    angle = (coords_unact.sigmoid() * (2 * math.pi)).unsqueeze(-1) / dim_t     # (..., 4, 64)
+    return torch.stack((angle.sin(), angle.cos()), -1).flatten(-3)
 
 
 def _get_clones(module, n):
@@ -303,8 +354,9 @@ class DeformableTransformer(nn.Module):
                  return_intermediate_dec=False, num_feature_levels=4, dec_n_points=4, enc_n_points=4,
                  two_stage=False, two_stage_num_proposals=300):
         super().__init__()
-        if two_stage:
-            raise NotImplementedError("two-stage Deformable-DETR is not part of this build (unused by the R50 models)")
+        if two_stage and 2 * d_model != PROPOSAL_EMBED_DIM:
+            raise ValueError(f"two-stage Deformable-DETR needs d_model = {PROPOSAL_EMBED_DIM // 2}: the proposals' sine embedding is "
+                             f"fixed at 4 x 128 = {PROPOSAL_EMBED_DIM} = 2 * d_model channels (got d_model = {d_model})")
         self.d_model, self.nhead = d_model, nhead
         self.two_stage, self.two_stage_num_proposals = two_stage, two_stage_num_proposals
         if encoder is None:
@@ -318,7 +370,13 @@ class DeformableTransformer(nn.Module):
             decoder = DeformableTransformerDecoder(decoder_layer, num_decoder_layers, return_intermediate_dec)
         self.decoder = decoder
         self.level_embed = nn.Parameter(torch.Tensor(num_feature_levels, d_model))
-        self.reference_points = nn.Linear(d_model, 2)
+        if two_stage:   # the queries come from the encoder's proposals: no learned reference points (reference :108-114)
+            self.enc_output = nn.Linear(d_model, d_model)
+            self.enc_output_norm = nn.LayerNorm(d_model)
+            self.pos_trans = nn.Linear(d_model * 2, d_model * 2)
+            self.pos_trans_norm = nn.LayerNorm(d_model * 2)
+        else:
+            self.reference_points = nn.Linear(d_model, 2)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -328,9 +386,74 @@ class DeformableTransformer(nn.Module):
         for m in self.modules():
             if isinstance(m, MSDeformAttn):
                 m._reset_parameters()
-        xavier_uniform_(self.reference_points.weight.data, gain=1.0)
-        constant_(self.reference_points.bias.data, 0.0)
+        if not self.two_stage:
+            xavier_uniform_(self.reference_points.weight.data, gain=1.0)
+            constant_(self.reference_points.bias.data, 0.0)
         normal_(self.level_embed)
+
+    def get_proposal_pos_embed(self, proposals):
+        return proposal_pos_embed(proposals)
+
+    def gen_encoder_output_proposals(self, memory, memory_padding_mask, shapes, fused=False):
+        """(``enc_output_norm(enc_output(memory with dropped rows zeroed))``, proposals (B, S, 4) float32): see
+        :func:`encoder_output_proposals` for the semantics.  ``shapes``: [(h, w)] as Python ints.  ``fused``: inference, the
+        element-wise part on alo_encoder_proposals_masked (or, where that does not apply, alo_encoder_proposals / alo_mask_rows)."""
+        if fused and alo_hip.encoder_proposals_masked_supported(memory_padding_mask, shapes, memory):
+            proposals, keep, output_memory = alo_hip.encoder_proposals_masked(memory_padding_mask, shapes, memory)   # both in one launch
+        else:
+            if fused and alo_hip.encoder_proposals_supported(memory_padding_mask, shapes):
+                proposals, keep = alo_hip.encoder_proposals(memory_padding_mask, shapes)
+            else:
+                proposals, keep = encoder_output_proposals(memory_padding_mask, shapes)
+            if fused and alo_hip.mask_rows_supported(memory, keep):
+                output_memory = alo_hip.mask_rows(memory, keep)
+            else:
+                output_memory = memory.masked_fill(~keep.unsqueeze(-1), 0.0)
+        if fused and alo_hip.add_layernorm_supported(output_memory):
+            output_memory = _add_norm(self.enc_output_norm,
+                                      alo_hip.linear_auto(output_memory, self.enc_output.weight, self.enc_output.bias), None)
+        else:
+            output_memory = self.enc_output_norm(self.enc_output(output_memory))
+        return output_memory, proposals
+
+    def _proposal_heads(self):
+        """The detection heads the proposals are scored with: entry ``decoder.num_layers`` of ``decoder.class_embed`` /
+        ``decoder.bbox_embed`` (the model attaches them; reference :252-254)."""
+        n = self.decoder.num_layers
+        for name in ("class_embed", "bbox_embed"):
+            heads = getattr(self.decoder, name, None)
+            if heads is None:
+                raise RuntimeError(f"two-stage DeformableTransformer: decoder.{name} is missing — attach the detection heads "
+                                   f"({n + 1} of them: one per decoder layer and one for the encoder's proposals) before the forward")
+            if len(heads) <= n:
+                raise RuntimeError(f"two-stage DeformableTransformer: decoder.{name} holds {len(heads)} heads, the proposals "
+                                   f"are scored by entry {n} (one per decoder layer and one more)")
+        return self.decoder.class_embed[n], self.decoder.bbox_embed[n]
+
+    def _two_stage_queries(self, memory, mask_flatten, shapes, kwargs):
+        """Reference :248-263: score every encoder token as a box proposal, keep the ``two_stage_num_proposals`` best by class
+        channel 0 and derive the decoder's inputs from their (detached) boxes.
+        -> (query_pos, tgt, reference_points (B, K, 4), enc_outputs_class, enc_outputs_coord_unact)"""
+        class_head, box_head = self._proposal_heads()
+        fused = _fused_ok(self, kwargs, memory, self.enc_output.weight, self.pos_trans.weight)
+        output_memory, output_proposals = self.gen_encoder_output_proposals(memory, mask_flatten, shapes, fused=fused)
+        enc_outputs_class = class_head(output_memory)
+        enc_outputs_coord_unact = box_head(output_memory) + output_proposals
+        topk = torch.topk(enc_outputs_class[..., 0], self.two_stage_num_proposals, dim=1)[1]
+        if fused and alo_hip.proposal_queries_supported(enc_outputs_coord_unact, topk, memory.dtype):
+            reference_points, embed = alo_hip.proposal_queries(enc_outputs_coord_unact, topk, memory.dtype, owner=self.pos_trans.weight)
+        else:
+            coords = torch.gather(enc_outputs_coord_unact, 1, topk.unsqueeze(-1).expand(-1, -1, 4)).detach()
+            reference_points = coords.sigmoid()
+            embed = proposal_pos_embed(coords).to(memory.dtype)
+        if fused and alo_hip.add_layernorm_supported(embed):
+            pos_trans_out = _add_norm(self.pos_trans_norm, alo_hip.linear_auto(embed, self.pos_trans.weight, self.pos_trans.bias), None)
+        else:
+            pos_trans_out = self.pos_trans_norm(self.pos_trans(embed))
+        query_pos, tgt = torch.split(pos_trans_out, memory.shape[-1], dim=2)
+        if fused:   # the decoder layers' one-pass kernels want dense operands
+            query_pos, tgt = query_pos.contiguous(), tgt.contiguous()
+        return query_pos, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact
 
     @staticmethod
     def get_valid_ratio(mask):
@@ -341,7 +464,7 @@ class DeformableTransformer(nn.Module):
         return torch.cat([valid_w / W, valid_h / H], 1)
 
     def forward(self, srcs, masks, pos_embeds, query_embed=None, **kwargs):
-        assert query_embed is not None
+        assert self.two_stage or query_embed is not None
         device = srcs[0].device
         src_flatten, mask_flatten, pos_flatten, shapes = [], [], [], []
         pos_encoder = kwargs.pop("pos_encoder", None)  # set by DeformableDETR when it left the encodings to this module
@@ -374,14 +497,19 @@ class DeformableTransformer(nn.Module):
                               **kwargs)
 
         bs, _, c = memory.shape
-        query_pos, tgt = torch.split(query_embed, c, dim=1)
-        query_pos = query_pos.unsqueeze(0).expand(bs, -1, -1)
-        tgt = tgt.unsqueeze(0).expand(bs, -1, -1)
-        if _fused_ok(self, kwargs, memory, query_embed):
-            # the one-pass kernels of the decoder layers want dense operands: materialise the two broadcasts once per forward
-            # instead of once per layer
-            query_pos, tgt = query_pos.contiguous(), tgt.contiguous()
-        reference_points = self.reference_points(query_pos).sigmoid()
+        enc_outputs_class = enc_outputs_coord_unact = None
+        if self.two_stage:
+            query_pos, tgt, reference_points, enc_outputs_class, enc_outputs_coord_unact = self._two_stage_queries(
+                memory, mask_flatten, shapes, kwargs)
+        else:
+            query_pos, tgt = torch.split(query_embed, c, dim=1)
+            query_pos = query_pos.unsqueeze(0).expand(bs, -1, -1)
+            tgt = tgt.unsqueeze(0).expand(bs, -1, -1)
+            if _fused_ok(self, kwargs, memory, query_embed):
+                # the one-pass kernels of the decoder layers want dense operands: materialise the two broadcasts once per forward
+                # instead of once per layer
+                query_pos, tgt = query_pos.contiguous(), tgt.contiguous()
+            reference_points = self.reference_points(query_pos).sigmoid()
 
         out = {}
         out.update(self.decoder(tgt, reference_points, memory, spatial_shapes, level_start_index, valid_ratios,
@@ -392,6 +520,6 @@ class DeformableTransformer(nn.Module):
             splits.append(memory_t[..., start:start + n].reshape(bs, c, h, w))
             start += n
         out["memory"] = splits
-        out["enc_outputs_class"] = None
-        out["enc_outputs_coord_unact"] = None
+        out["enc_outputs_class"] = enc_outputs_class
+        out["enc_outputs_coord_unact"] = enc_outputs_coord_unact
         return out
