@@ -1254,6 +1254,109 @@ def value_proj_head_major(x, weight, bias, padding_mask, heads):
     return out
 
 
+# ---- the encoder layer's row-local chain in one kernel (libalo_encoder_block.so, include/alo_encoder_block.h) ---------------------
+ENCODER_BLOCK_LIB_PATH = os.path.join(_PKG_ROOT, "libalo_encoder_block.so")
+_encoder_block_lib = None
+
+
+def encoder_block_lib():
+    """The loaded libalo_encoder_block.so (it reports errors through libalo_hotpath.so's ``alo_last_error``); raises
+    :class:`HotpathUnavailable` when it is missing or has another ABI."""
+    global _encoder_block_lib
+    if _encoder_block_lib is None:
+        lib()   # first: the library links against it
+        if not os.path.exists(ENCODER_BLOCK_LIB_PATH):
+            raise HotpathUnavailable(f"{ENCODER_BLOCK_LIB_PATH} is missing: build it with `make -C {CSRC_DIR}` (hipcc, --offload-arch=gfx950)")
+        try:
+            handle = ctypes.CDLL(ENCODER_BLOCK_LIB_PATH)
+        except OSError as e:  # pragma: no cover - depends on the box
+            raise HotpathUnavailable(f"cannot load {ENCODER_BLOCK_LIB_PATH}: {e}") from e
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        handle.alo_encoder_block_abi_version.restype = ip
+        handle.alo_encoder_block_abi_version.argtypes = []
+        handle.alo_encoder_block.restype = ip
+        handle.alo_encoder_block.argtypes = [vp] * 21 + [ip] * 3 + [ctypes.c_float] * 2 + [ip, vp]
+        if handle.alo_encoder_block_abi_version() != 1:
+            raise HotpathUnavailable(f"{ENCODER_BLOCK_LIB_PATH} has ABI version {handle.alo_encoder_block_abi_version()}, expected 1")
+        _encoder_block_lib = handle
+    return _encoder_block_lib
+
+
+def encoder_block_enabled():
+    """``ALO_ENC_BLOCK=off`` (read per call) keeps the encoder on its separate launches: for tests and profiling."""
+    return os.environ.get("ALO_ENC_BLOCK", "on").lower() not in ("off", "0")
+
+
+def encoder_block_supported(src, w1, w2, *vectors, heads=8, levels=4, points=4, value_weight=None):
+    """What :func:`encoder_block` takes: a bf16 CUDA (N, S, 256) ``src`` outside autograd (:func:`fusable`), FFN weights
+    :func:`ffn256` takes, 8 heads and L = P = 4, a value projection :func:`value_proj_head_major` takes (when the next layer's
+    projections are asked for) and every bias / LayerNorm vector in ``vectors`` present."""
+    if not (fusable(src, w1, w2, value_weight, *vectors) and src.dtype == torch.bfloat16 and src.dim() == 3 and src.shape[-1] == 256
+            and src.numel() > 0 and ffn256_supported(src, w1, w2) and heads == 8 and levels == 4 and points == 4
+            and all(v is not None for v in vectors)):
+        return False
+    return value_weight is None or value_proj_head_major_supported(src, value_weight, heads)
+
+
+def _vec(t, dtype):
+    return t.to(dtype).contiguous()
+
+
+def encoder_block(src, w1, b1, w2, b2, norm2, tail=None, nxt=None):
+    """The row-local part of an encoder layer in one kernel, bit for bit the chain of launches it stands in for.
+
+    ``src`` (N, S, 256) bf16; ``norm2 = (weight, bias, eps)``: ``src' = LayerNorm2(ffn256(x) + x)`` with ``x = src``, or with
+    ``tail = (attn_out, wo, bo, norm1_weight, norm1_bias, eps1)``, ``x = LayerNorm1(linear(attn_out, wo, bo) + src)``.
+    With ``nxt = (pos, padding_mask | None, wv, bv, wq, bq)`` also the next layer's ``value_proj_head_major(src', wv, bv,
+    padding_mask, 8)`` and ``linear(src' + pos, wq, bq)`` for the merged (384, 256) offsets + logits weight.
+    -> (src', value_hm | None, offsets_logits | None)"""
+    if not encoder_block_supported(src, w1, w2, b1, b2, norm2[0], norm2[1]):
+        raise RuntimeError("encoder_block: needs a bf16 CUDA (N, S, 256) src outside autograd, bf16 FFN weights with a hidden width "
+                           "that is a multiple of 256, and every bias")
+    N, S, C = src.shape
+    dt, dev = src.dtype, src.device
+    src = src.contiguous()
+    Fh = w1.shape[0]
+    out = torch.empty_like(src)
+    named = [("w1", w1, (Fh, 256)), ("w2", w2, (256, Fh))]
+    t_args = [None] * 5
+    eps1 = 0.0
+    if tail is not None:
+        attn_out, wo, bo, g1, e1, eps1 = tail
+        if attn_out.shape != src.shape or attn_out.dtype != dt or attn_out.device != dev:
+            raise RuntimeError("encoder_block: attn_out must have the shape, dtype and device of src")
+        named.append(("wo", wo, (256, 256)))
+        attn_out = attn_out.contiguous()
+        t_args = [attn_out, pack_mfma_b(wo), _vec(bo, dt), _vec(g1, dt), _vec(e1, dt)]
+    n_args = [None] * 8
+    value = both = None
+    if nxt is not None:
+        pos, padding_mask, wv, bv, wq, bq = nxt
+        if pos.shape != src.shape or pos.dtype != dt or pos.device != dev:
+            raise RuntimeError("encoder_block: pos must have the shape, dtype and device of src")
+        if padding_mask is not None:
+            if padding_mask.dtype != torch.bool or tuple(padding_mask.shape) != (N, S) or padding_mask.device != dev:
+                raise RuntimeError("padding_mask must be a (N, S) bool tensor on src's device")
+            padding_mask = padding_mask.contiguous()
+        named += [("wv", wv, (256, 256)), ("wq", wq, (384, 256))]
+        value = torch.empty((N, 8, S, 32), dtype=dt, device=dev)
+        both = torch.empty((N, S, 384), dtype=dt, device=dev)
+        n_args = [pos.contiguous(), padding_mask, pack_mfma_b(wv), _vec(bv, dt), pack_mfma_b(wq), _vec(bq, dt), value, both]
+    for name, w, shape in named:
+        if tuple(w.shape) != shape or w.dtype != dt or w.device != dev:
+            raise RuntimeError(f"encoder_block: {name} must be a {shape} tensor of src's dtype on its device")
+    f_args = [src, pack_mfma_b(w1), _vec(b1, dt), pack_mfma_b(w2), _vec(b2, dt), _vec(norm2[0], dt), _vec(norm2[1], dt), out]
+    ptr = lambda t: None if t is None else _ptr(t)
+    rows = N * S
+    # what the result needs: src, src' (+ attn_out) (+ pos, value, offsets + logits, mask bytes)
+    nbytes = 2.0 * rows * (256 * (2 + (tail is not None) + 2 * (nxt is not None)) + 384 * (nxt is not None)) + rows * (nxt is not None)
+    flops = 2.0 * rows * 256 * (2 * Fh + 256 * (tail is not None) + (256 + 384) * (nxt is not None))
+    tag = f"encoder_block/{'tail+' if tail is not None else ''}ffn{'+proj' if nxt is not None else ''}/rows={rows}"
+    with torch.cuda.device(dev), _timed(tag, nbytes, flops):
+        _check(encoder_block_lib().alo_encoder_block(*[ptr(t) for t in t_args + f_args + n_args], N, S, Fh, float(eps1), float(norm2[2]),
+                                                     ALO_BF16, _stream(dev)))
+    return out, value, both
+
 
 def panoptic_onehot(mask_logits, frame_size, threshold=0.5):
     """(B, Q, h, w) mask logits -> (B, Q, H, W) int64 one-hot instance masks: bilinear up-sampling, sigmoid, threshold and the

@@ -180,6 +180,34 @@ class DeformableTransformerEncoderLayer(nn.Module):
             return _add_norm(self.norm2, src2, src, pos=pos)
         return _add_norm(self.norm2, src2, src), None
 
+    def block_supported(self, src, query):
+        """Whether this layer's row-local chain fits the fused kernel (alo_hip.encoder_block): the conjunction of what the
+        separate launches of ``forward_fused`` and of the head-major attention path ask for."""
+        attn = self.self_attn
+        return (self.activation is F.relu and attn.head_major_supported(query, src)
+                and alo_hip.encoder_block_supported(
+                    src, self.linear1.weight, self.linear2.weight, self.linear1.bias, self.linear2.bias, self.norm1.weight,
+                    self.norm1.bias, self.norm2.weight, self.norm2.bias, attn.output_proj.bias, heads=attn.n_heads,
+                    levels=attn.n_levels, points=attn.n_points, value_weight=attn.value_proj.weight))
+
+    def forward_block(self, src, value, both, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None,
+                      next_layer=None):
+        """``forward_fused`` in two launches: the attention kernel on ready-made inputs (value, offsets + logits), then everything
+        up to the next attention kernel in one (alo_hip.encoder_block): output projection, both residual + LayerNorm pairs, the
+        FFN and ``next_layer``'s three projections.  -> (src', next value | None, next offsets + logits | None)"""
+        attn = self.self_attn
+        out = attn.forward_head_major(value, both, reference_points, spatial_shapes, level_start_index, project=False)
+        tail = (out, attn.output_proj.weight, attn.output_proj.bias, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        nxt = None
+        if next_layer is not None:
+            n_attn = next_layer.self_attn
+            w_cat, b_cat = n_attn._merged_query_projection()
+            nxt = (pos, padding_mask, n_attn.value_proj.weight, n_attn.value_proj.bias, w_cat, b_cat)
+        return alo_hip.encoder_block(
+            src, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias,
+            (self.norm2.weight, self.norm2.bias, self.norm2.eps),
+            tail=tail, nxt=nxt)
+
 
 class DeformableTransformerEncoder(nn.Module):
     def __init__(self, encoder_layer, num_layers):
@@ -211,6 +239,16 @@ class DeformableTransformerEncoder(nn.Module):
         reference_points = self.get_reference_points(spatial_shapes, valid_ratios, device=src.device, **kwargs)
         if _fused_ok(self, kwargs, output, pos) and all(hasattr(layer, "forward_fused") for layer in self.layers):
             query = output if pos is None else output + pos
+            if (pos is not None and alo_hip.encoder_block_enabled()
+                    and all(hasattr(layer, "forward_block") and layer.block_supported(output, query) for layer in self.layers)):
+                # between two attention kernels ONE launch: layer 0's projections with the separate kernels, then per layer the
+                # attention kernel and the block, which also makes the next layer's projections
+                value, both = self.layers[0].self_attn.head_major_inputs(query, output, padding_mask)
+                for i, layer in enumerate(self.layers):
+                    nxt = self.layers[i + 1] if i + 1 < len(self.layers) else None
+                    output, value, both = layer.forward_block(output, value, both, pos, reference_points, spatial_shapes,
+                                                              level_start_index, padding_mask, next_layer=nxt)
+                return output
             for i, layer in enumerate(self.layers):
                 output, query = layer.forward_fused(output, query, pos, reference_points, spatial_shapes, level_start_index,
                                                     padding_mask, next_query=i + 1 < len(self.layers), **kwargs)

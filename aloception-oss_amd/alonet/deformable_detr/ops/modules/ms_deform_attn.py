@@ -80,6 +80,36 @@ class MSDeformAttn(nn.Module):
                                lambda: (torch.cat([so.weight, aw.weight], 0).contiguous(),
                                         torch.cat([so.bias, aw.bias], 0).contiguous()))
 
+    def head_major_supported(self, query, input_flatten):
+        """Whether the inference path of the DETR-family shape applies (:meth:`head_major_inputs`, :meth:`forward_head_major`):
+        bf16, head dimension 32, L = P = 4, every projection with its bias."""
+        return (self.fused_prologue and query.is_cuda and self.d_model // self.n_heads == 32 and self.n_levels == 4
+                and self.n_points == 4 and self.value_proj.bias is not None and self.sampling_offsets.bias is not None
+                and self.attention_weights.bias is not None
+                and alo_hip.linear_shortk_supported(query, self.sampling_offsets.weight)
+                and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, self.n_heads))
+
+    def head_major_inputs(self, query, input_flatten, input_padding_mask=None):
+        """What the attention kernel reads, in two launches -> (value (N, M, S, 32) head-major with the padded rows zeroed,
+        offsets + logits (N, Lq, 3 M L P): both projections of the query in ONE GEMM, the query read once)."""
+        w_cat, b_cat = self._merged_query_projection()
+        both = alo_hip.linear_auto(query, w_cat, b_cat)
+        value = alo_hip.value_proj_head_major(input_flatten, self.value_proj.weight, self.value_proj.bias, input_padding_mask,
+                                              self.n_heads)
+        return value, both
+
+    def forward_head_major(self, value, both, reference_points, input_spatial_shapes, input_level_start_index, project=True):
+        """The layer from ready-made inputs (:meth:`head_major_inputs`, or a fused kernel that made them for this layer); the
+        attention kernel takes its offsets and logits as column slices of ``both``.  ``project=False`` returns the attention
+        output before ``output_proj``."""
+        N, Lq, _ = both.shape
+        M, L, P = self.n_heads, self.n_levels, self.n_points
+        offsets = both[..., :M * L * P * 2].view(N, Lq, M, L, P, 2)
+        logits = both[..., M * L * P * 2:].view(N, Lq, M, L * P)
+        output = alo_hip.msda_forward_fused_hm(value, input_spatial_shapes, input_level_start_index, offsets, logits,
+                                               reference_points)
+        return alo_hip.linear_auto(output, self.output_proj.weight, self.output_proj.bias) if project else output
+
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                 input_padding_mask=None, **kwargs):
         """
@@ -115,15 +145,11 @@ class MSDeformAttn(nn.Module):
         hm = (fused and D == 32 and L == 4 and P == 4 and self.value_proj.bias is not None
               and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, M))
         if hm and self.sampling_offsets.bias is not None and self.attention_weights.bias is not None:
-            # both projections of the query in ONE GEMM (query read once); the attention kernel takes its offsets and logits as
-            # column slices of the merged result
-            w_cat, b_cat = self._merged_query_projection()
-            both = alo_hip.linear_auto(query, w_cat, b_cat)
-            offsets = both[..., :M * L * P * 2].view(N, Lq, M, L, P, 2)
-            logits = both[..., M * L * P * 2:].view(N, Lq, M, L * P)
-        else:
-            offsets = proj(self.sampling_offsets, query).view(N, Lq, M, L, P, 2)
-            logits = proj(self.attention_weights, query).view(N, Lq, M, L * P)
+            # inference, DETR-family shape: three launches (head_major_inputs), the attention kernel, the output projection
+            value, both = self.head_major_inputs(query, input_flatten, input_padding_mask)
+            return self.forward_head_major(value, both, reference_points, input_spatial_shapes, input_level_start_index)
+        offsets = proj(self.sampling_offsets, query).view(N, Lq, M, L, P, 2)
+        logits = proj(self.attention_weights, query).view(N, Lq, M, L * P)
         if hm:
             # inference, DETR-family shape: value_proj, the padding mask and the head-major layout are ONE kernel
             value = alo_hip.value_proj_head_major(input_flatten, self.value_proj.weight, self.value_proj.bias,

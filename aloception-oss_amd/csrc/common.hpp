@@ -251,4 +251,105 @@ __device__ __forceinline__ void store_vec(T* p, const CT (&v)[VEC]) {
     }
 }
 
+// Sum over the 64 lanes of a wave, every lane gets it (the LayerNorm kernels: one wave per row).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ---- 64 x 256 bf16 row tiles in LDS against weights streamed in MFMA fragment order (ffn256_kernel, encoder_block_kernel) ----------
+// A workgroup of 4 waves owns 64 rows; wave w computes 64 output columns of them as [2 row tiles][2 column tiles] of 32 x 32.  The
+// products are computed transposed (weights = the MFMA's row operand), so a lane owns ONE row of the tile and four consecutive
+// columns per accumulator quad.
+constexpr int kTileRows = 64;
+constexpr int kTileStride = 256 * 2 + 16;  // LDS row stride: +16 B keeps the 16-byte fragment reads conflict-free
+constexpr int kTileKB = 2;                 // k-steps per weight batch
+constexpr int kTileBatches = 16 / kTileKB; // batches per 256-deep contraction
+
+// Weight fragments arrive in batches of kTileKB k-steps (2 column tiles x kTileKB x 16 B per lane) through two register buffers:
+// batch i+1 is requested before batch i is consumed (L2 latency ~ the MFMA time of one batch).  frag0 = this lane's 16 bytes of the
+// first fragment of column tile 0 (alo_pack_mfma_b order: a fragment is 64 lanes x 16 B contiguous), tile_stride = elements between
+// the two column tiles.  sched_barrier keeps the compiler from sinking the requests next to their first use.
+__device__ __forceinline__ void load_batch(u32x4 (&buf)[2][kTileKB], const bf16_t* frag0, size_t tile_stride, int batch) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < kTileKB; ++j)
+            buf[t][j] = *reinterpret_cast<const u32x4*>(frag0 + t * tile_stride + (size_t)(kTileKB * batch + j) * 512);
+    __builtin_amdgcn_sched_barrier(0);
+}
+// acc[row tile][column tile] += A (the LDS tile, k-steps kTileKB * batch ..) x the batch's weight fragments; nl = lane & 31, kg = lane >> 5
+__device__ __forceinline__ void mma_batch(f32x16 (&acc)[2][2], const unsigned char* a_lds, const u32x4 (&buf)[2][kTileKB], int batch,
+                                          int nl, int kg) {
+    u32x4 af[2][kTileKB];  // A fragments of the whole batch first: their LDS latency overlaps instead of preceding each MFMA group
+#pragma unroll
+    for (int j = 0; j < kTileKB; ++j) {
+        const int s = kTileKB * batch + j;
+        af[0][j] = *reinterpret_cast<const u32x4*>(a_lds + nl * kTileStride + (16 * s + 8 * kg) * 2);
+        af[1][j] = *reinterpret_cast<const u32x4*>(a_lds + (32 + nl) * kTileStride + (16 * s + 8 * kg) * 2);
+    }
+#pragma unroll
+    for (int j = 0; j < kTileKB; ++j) {
+        const u32x4 a0 = af[0][j], a1 = af[1][j];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a0), acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a0), acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a1), acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a1), acc[1][1], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// One whole 256-deep contraction of the LDS tile against weights w (fragment pointer of k-step 0), through bufa / bufb.  bufa already
+// holds batch 0; on return it holds batch 0 of `next` (same tile stride) when next != nullptr.
+__device__ __forceinline__ void mma_tile256(f32x16 (&acc)[2][2], const unsigned char* a_lds, u32x4 (&bufa)[2][kTileKB],
+                                            u32x4 (&bufb)[2][kTileKB], const bf16_t* w, size_t tile_stride, const bf16_t* next,
+                                            size_t next_stride, int nl, int kg) {
+#pragma unroll
+    for (int bt = 0; bt < kTileBatches; bt += 2) {
+        load_batch(bufb, w, tile_stride, bt + 1);
+        mma_batch(acc, a_lds, bufa, bt, nl, kg);
+        if (bt + 2 < kTileBatches) load_batch(bufa, w, tile_stride, bt + 2);
+        else if (next != nullptr) load_batch(bufa, next, next_stride, 0);
+        mma_batch(acc, a_lds, bufb, bt + 1, nl, kg);
+    }
+}
+
+// The tile loader: rows [row0, row0 + 64) of a (M, 256) bf16 matrix, 8 pieces of 16 B per thread, rows contiguous across lanes.  Rows
+// past the end are read from the last row (never stored) so that all eight requests go out back to back, unpredicated.
+__device__ __forceinline__ void fetch_tile256(u32x4 (&v)[8], const bf16_t* X, long row0, long M, int tid) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int p = tid + 256 * j;
+        long row = row0 + (p >> 5);
+        row = row < M ? row : M - 1;
+        v[j] = *reinterpret_cast<const u32x4*>(X + row * 256 + (p & 31) * 8);
+    }
+}
+__device__ __forceinline__ void park_tile256(unsigned char* lds, const u32x4 (&v)[8], int tid) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int p = tid + 256 * j;
+        *reinterpret_cast<u32x4*>(lds + (p >> 5) * kTileStride + (p & 31) * 16) = v[j];
+    }
+}
+// this wave's accumulators (+ bias[column] when ADD_BIAS) -> bf16 -> the LDS tile, [row][column], as 8-byte writes
+template <bool ADD_BIAS, bool RELU>
+__device__ __forceinline__ void stage_tile256(unsigned char* lds, const f32x16 (&acc)[2][2], const float* bias, int wave, int nl, int kg) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int col = 64 * wave + 32 * t + 8 * q + 4 * kg;  // registers 4 q .. 4 q + 3 = columns col .. col + 3
+            f32x4 bb = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (ADD_BIAS) bb = *reinterpret_cast<const f32x4*>(bias + col);
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                float v0 = acc[a][t][4 * q], v1 = acc[a][t][4 * q + 1], v2 = acc[a][t][4 * q + 2], v3 = acc[a][t][4 * q + 3];
+                if constexpr (ADD_BIAS) { v0 += bb[0]; v1 += bb[1]; v2 += bb[2]; v3 += bb[3]; }
+                if constexpr (RELU) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
+                *reinterpret_cast<u32x2*>(lds + (32 * a + nl) * kTileStride + col * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+            }
+        }
+}
+
 }  // namespace alo

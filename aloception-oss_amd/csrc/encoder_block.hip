@@ -1,0 +1,374 @@
+// The row-local part of a Deformable-DETR encoder layer in one kernel (include/alo_encoder_block.h):
+//
+//   [ src  = LayerNorm1(attn_out Wo^T + bo + src) ]                    attention tail        (TAIL)
+//     src' = LayerNorm2(relu(src W1^T + b1) W2^T + b2 + src)           feed-forward block
+//   [ value = mask(src' Wv^T + bv) head-major,  offsets_logits = (src' + pos) Wq^T + bq ]    next layer's projections (PROJ)
+//
+// Run as separate launches (alo_linear_shortk, alo_add_layernorm, alo_ffn256, alo_add_layernorm, alo_value_proj_head_major,
+// alo_linear_shortk) every arrow of that chain is a (rows, 256) bf16 tensor written by one streaming kernel and read back by the next:
+// at 177784 rows about 900 MB of the 1500 MB a layer moves between two attention launches (counted from the shapes, not measured).  Here a workgroup owns 64 rows for the whole
+// chain.  It is ffn256_kernel's frame (gemm.hip): 256 threads, two 64 x 256 bf16 LDS tiles A and B, persistent over the tiles, weights
+// pre-packed in MFMA fragment order and streamed through two register buffers.  Each product reads A and stages its bf16 result in B;
+// each LayerNorm reads B (+ its residual) one wave per row, a lane owning 4 consecutive columns as in add_layernorm_kernel, and leaves
+// the normalised rows in A for the next product.  Rounding points, operand roles and summation orders are those of the kernels this
+// stands in for, so the three outputs equal theirs bit for bit.
+#include "common.hpp"
+
+#include "../../include/alo_encoder_block.h"
+
+namespace alo {
+namespace {
+
+constexpr int kHeads = 8;          // value_hm is (batch, 8, S, 32)
+constexpr int kQueryCols = 384;    // merged [sampling_offsets (256); attention_weights (128)]
+constexpr int kRowsPerWave = kTileRows / 4;
+constexpr int kTables = 256 * 7 + kQueryCols;   // fp32 tables next to b1: b2, bo, bv, bq, and the two LayerNorms' gamma / beta
+
+struct EncBlockArgs {
+    const bf16_t *attn, *wo, *bo, *g1, *be1;
+    const bf16_t *src, *w1, *b1, *w2, *b2, *g2, *be2;
+    bf16_t* out;
+    const bf16_t* pos;
+    const unsigned char* mask;
+    const bf16_t *wv, *bv, *wq, *bq;
+    bf16_t *value, *both;
+    long M;
+    int S, F, tiles;
+    float eps1, eps2;
+};
+
+__device__ __forceinline__ void unpack4(const u32x2& x, float (&v)[4]) {
+    v[0] = __uint_as_float(x.x << 16); v[1] = __uint_as_float(x.x & 0xffff0000u);
+    v[2] = __uint_as_float(x.y << 16); v[3] = __uint_as_float(x.y & 0xffff0000u);
+}
+__device__ __forceinline__ u32x2 pack4(const float (&v)[4]) { return u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}; }
+
+// LayerNorm of one 256-wide row spread over the wave, 4 consecutive columns per lane: add_layernorm_kernel's arithmetic
+__device__ __forceinline__ void layernorm_row(const float (&v)[4], const f32x4& g, const f32x4& b, float eps, float (&y)[4]) {
+    const float inv_c = 1.0f / 256.f;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s += v[i];
+    const float mean = wave_sum(s) * inv_c;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const float d = v[i] - mean; q += d * d; }
+    const float rstd = rsqrtf(wave_sum(q) * inv_c + eps);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = (v[i] - mean) * rstd * g[i] + b[i];
+}
+
+// accumulators start from the bias (linear_shortk_kernel): registers 4 q .. 4 q + 3 of column tile t = columns 32 t + 8 q + 4 kg ..
+__device__ __forceinline__ void init_acc_bias(f32x16 (&acc)[2][2], const float* bias64, int kg) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(bias64 + 32 * t + 8 * q + 4 * kg);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { acc[0][t][4 * q + i] = bb[i]; acc[1][t][4 * q + i] = bb[i]; }
+        }
+}
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a][t][i] = 0.f;
+}
+// a wave reads back what it staged itself
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// An opaque copy of a weight pointer, taken once per tile: without it the address of every weight load of the three short products (a
+// register pair each, the same for all tiles) is computed ahead of the tile loop and the pairs are spilled.
+__device__ __forceinline__ const bf16_t* per_tile(const bf16_t* w) {
+    asm volatile("" : "+v"(w));
+    return w;
+}
+
+// The residual and pos rows a LayerNorm adds are wanted AFTER a product, in the one-wave-per-row layout; held in registers across the
+// product (32 VGPRs next to 64 accumulators and 32 of weights) they pushed the kernel into scratch.  So they are loaded after the
+// product, and only warmed before it: one dword per 128-byte line of this wave's 16 rows brings the lines into the L2 and costs one
+// register; retire() is where that register is given up.
+__device__ __forceinline__ unsigned warm_rows(const bf16_t* X, long first_row, long M, int lane) {
+    long row = first_row + (lane >> 2);
+    row = row < M ? row : M - 1;
+    return *reinterpret_cast<const unsigned*>(X + row * 256 + (lane & 3) * 64);
+}
+__device__ __forceinline__ void retire(unsigned v) { asm volatile("" ::"v"(v)); }
+// this wave's 16 rows, 4 consecutive columns per lane; rows past the end are read from the last row
+__device__ __forceinline__ void load_rows(u32x2 (&v)[kRowsPerWave], const bf16_t* X, long first_row, long M, int lane) {
+#pragma unroll
+    for (int r = 0; r < kRowsPerWave; ++r) {
+        long row = first_row + r;
+        row = row < M ? row : M - 1;
+        v[r] = *reinterpret_cast<const u32x2*>(X + row * 256 + 4 * lane);
+    }
+}
+
+template <bool TAIL, bool PROJ>
+__global__ void __launch_bounds__(256, 2)
+encoder_block_kernel(const EncBlockArgs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const A = smem;                             // the tile every product reads
+    unsigned char* const B = smem + kTileRows * kTileStride;   // hidden chunk / every product's bf16 result
+    const int tid = threadIdx.x, lane = tid & 63;
+    // the wave index as a scalar: row and weight-tile addresses then split into a scalar base and one per-lane offset, instead of a
+    // register pair per row and per fragment
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nl = lane & 31, kg = lane >> 5;
+    const int F = p.F;
+
+    float* const b1s = reinterpret_cast<float*>(smem + 2 * kTileRows * kTileStride);
+    float* const b2s = b1s + F;
+    float* const bos = b2s + 256;
+    float* const bvs = bos + 256;
+    float* const bqs = bvs + 256;
+    float* const g1s = bqs + kQueryCols;
+    float* const e1s = g1s + 256;
+    float* const g2s = e1s + 256;
+    float* const e2s = g2s + 256;
+    for (int i = tid; i < F; i += 256) b1s[i] = bf16_to_f32(p.b1[i].bits);
+    b2s[tid] = bf16_to_f32(p.b2[tid].bits);
+    g2s[tid] = bf16_to_f32(p.g2[tid].bits);
+    e2s[tid] = bf16_to_f32(p.be2[tid].bits);
+    if constexpr (TAIL) {
+        bos[tid] = bf16_to_f32(p.bo[tid].bits);
+        g1s[tid] = bf16_to_f32(p.g1[tid].bits);
+        e1s[tid] = bf16_to_f32(p.be1[tid].bits);
+    }
+    if constexpr (PROJ) {
+        bvs[tid] = bf16_to_f32(p.bv[tid].bits);
+        for (int i = tid; i < kQueryCols; i += 256) bqs[i] = bf16_to_f32(p.bq[i].bits);
+    }
+
+    const int fs = F / 16;  // k steps per output-column tile of the packed W2
+    // this lane's 16 bytes of the first fragment of this wave's first column tile (packed fragment = 64 lanes x 16 B contiguous)
+    auto k256_frag = [&](const bf16_t* W, int col0) { return W + ((size_t)((col0 + 64 * wave) / 32) * 16 * 64 + lane) * 8; };  // tile stride 16 * 512
+    auto w2_frag = [&](int r0) { return p.w2 + (((size_t)(2 * wave) * fs + r0 / 16) * 64 + lane) * 8; };                        // tile stride fs * 512
+    constexpr size_t kStride256 = (size_t)16 * 512;
+
+    for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+        const long row0 = (long)tile * kTileRows;
+        const int wrow = kRowsPerWave * wave;  // the 16 rows this wave normalises
+        const bf16_t* const wo_f = TAIL ? per_tile(k256_frag(p.wo, 0)) : nullptr;
+        const bf16_t* const wv_f = PROJ ? per_tile(k256_frag(p.wv, 0)) : nullptr;
+        const bf16_t* const wq_f = PROJ ? per_tile(k256_frag(p.wq, 0)) : nullptr;  // columns 256 .. : 8 column tiles on
+        u32x4 bufa[2][kTileKB], bufb[2][kTileKB];
+        {
+            u32x4 xv[8];
+            fetch_tile256(xv, TAIL ? p.attn : p.src, row0, p.M, tid);
+            park_tile256(A, xv, tid);
+        }
+
+        if constexpr (TAIL) {
+            // ---- attention tail: A = LayerNorm1(attn_out Wo^T + bo + src); the residual rows are warmed before the product ----------
+            const unsigned warm = warm_rows(p.src, row0 + wrow, p.M, lane);
+            load_batch(bufa, wo_f, kStride256, 0);
+            __syncthreads();
+            f32x16 acc[2][2];
+            init_acc_bias(acc, bos + 64 * wave, kg);
+            mma_tile256(acc, A, bufa, bufb, wo_f, kStride256, k256_frag(p.w1, 0), kStride256, nl, kg);
+            stage_tile256<false, false>(B, acc, nullptr, wave, nl, kg);
+            __syncthreads();  // the projected rows are in B and nobody reads A any more
+            retire(warm);
+            u32x2 res[kRowsPerWave];
+            load_rows(res, p.src, row0 + wrow, p.M, lane);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(g1s + 4 * lane), b = *reinterpret_cast<const f32x4*>(e1s + 4 * lane);
+#pragma unroll
+            for (int r = 0; r < kRowsPerWave; ++r) {
+                float v[4], t[4], y[4];
+                unpack4(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                unpack4(res[r], t);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] += t[i];
+                layernorm_row(v, g, b, p.eps1, y);
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4(y);
+            }
+        } else {
+            load_batch(bufa, k256_frag(p.w1, 0), kStride256, 0);
+        }
+        __syncthreads();  // the FFN's x tile is in A
+
+        // ---- feed-forward block: ffn256_kernel's arithmetic, the hidden activation 256 units at a time through B -------------------
+        {
+            f32x16 acc2[2][2];
+            zero_acc(acc2);
+            for (int r0 = 0; r0 < F; r0 += 256) {
+                f32x16 acc1[2][2];
+                zero_acc(acc1);
+                const bf16_t* w2p = w2_frag(r0);
+                mma_tile256(acc1, A, bufa, bufb, k256_frag(p.w1, r0), kStride256, w2p, (size_t)fs * 512, nl, kg);
+                stage_tile256<true, true>(B, acc1, b1s + r0, wave, nl, kg);
+                __syncthreads();  // the whole 64 x 256 hidden chunk is in B
+                const bf16_t* next = r0 + 256 < F ? k256_frag(p.w1, r0 + 256) : wv_f;
+                mma_tile256(acc2, B, bufa, bufb, w2p, (size_t)fs * 512, next, kStride256, nl, kg);
+                __syncthreads();  // everyone is done reading the chunk before it is overwritten
+            }
+            stage_tile256<true, false>(B, acc2, b2s, wave, nl, kg);
+        }
+        __syncthreads();
+
+        // ---- src' = LayerNorm2(B + A) -> A and, in whole rows, to memory --------------------------------------------------------------
+        {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(g2s + 4 * lane), b = *reinterpret_cast<const f32x4*>(e2s + 4 * lane);
+#pragma unroll
+            for (int r = 0; r < kRowsPerWave; ++r) {
+                float v[4], t[4], y[4];
+                unpack4(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                unpack4(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), t);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] += t[i];
+                layernorm_row(v, g, b, p.eps2, y);
+                const u32x2 o = pack4(y);
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = o;
+                const long row = row0 + wrow + r;
+                if (row < p.M) *reinterpret_cast<u32x2*>(p.out + row * 256 + 4 * lane) = o;
+            }
+        }
+        __syncthreads();  // src' is in A; B is free
+
+        if constexpr (PROJ) {
+            // ---- the next layer's value: mask(A Wv^T + bv), head-major; the pos rows are warmed before the product ------------------------
+            const unsigned warm = warm_rows(p.pos, row0 + wrow, p.M, lane);
+            f32x16 acc[2][2];
+            init_acc_bias(acc, bvs + 64 * wave, kg);
+            mma_tile256(acc, A, bufa, bufb, wv_f, kStride256, wq_f, kStride256, nl, kg);
+            stage_tile256<false, false>(B, acc, nullptr, wave, nl, kg);
+            __syncthreads();  // the value rows are in B and nobody reads A any more
+            retire(warm);
+            unsigned char masked[kTileRows / 16];  // first, so that the stores below wait for these bytes alone
+#pragma unroll
+            for (int pass = 0; pass < kTileRows / 16; ++pass) {
+                long row = row0 + pass * 16 + (lane >> 2);
+                row = row < p.M ? row : p.M - 1;
+                masked[pass] = p.mask != nullptr ? p.mask[row] : (unsigned char)0;
+            }
+            u32x2 posr[kRowsPerWave];
+            load_rows(posr, p.pos, row0 + wrow, p.M, lane);
+            // the tile starts at token sp0 of batch item nb0: a 32-bit division per row instead of a 64-bit one
+            const long nb0 = row0 / p.S;
+            const int sp0 = (int)(row0 - nb0 * p.S);
+            // per head (32 columns = 64 B per row): 4 lanes x 16 B per row, 16 consecutive rows = 1 KB per store instruction
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+#pragma unroll
+                for (int pass = 0; pass < kTileRows / 16; ++pass) {
+                    const int row = pass * 16 + (lane >> 2);
+                    const long grow = row0 + row;
+                    if (grow < p.M) {
+                        u32x4 v = *reinterpret_cast<const u32x4*>(B + row * kTileStride + (64 * wave + 32 * hh) * 2 + (lane & 3) * 16);
+                        if (masked[pass]) v = u32x4{0u, 0u, 0u, 0u};
+                        const unsigned over = (unsigned)(sp0 + row) / (unsigned)p.S;
+                        const long nb = nb0 + over, sp = sp0 + row - (long)over * p.S;
+                        const int head = 2 * wave + hh;
+                        *reinterpret_cast<u32x4*>(p.value + ((nb * kHeads + head) * p.S + sp) * 32 + (lane & 3) * 8) = v;
+                    }
+                }
+            }
+            // ---- the next layer's query, in place: A = bf16(A + pos), the sum taken on the rounded src' ---------------------------------
+#pragma unroll
+            for (int r = 0; r < kRowsPerWave; ++r) {
+                float y[4], t[4];
+                unpack4(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), y);
+                unpack4(posr[r], t);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) y[i] += t[i];
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4(y);
+            }
+            __syncthreads();  // the query is in A; the value rows have left B
+
+            // ---- offsets + logits: A Wq^T + bq over the merged 384 columns, 64 per wave: columns 0-255, then 256-383 (two waves) ------
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                if (pass == 1 && wave >= 2) break;  // wave-uniform; no workgroup barrier below
+                const int col0 = 256 * pass;
+                init_acc_bias(acc, bqs + col0 + 64 * wave, kg);
+                const bf16_t* const wq_p = wq_f + (size_t)pass * 8 * kStride256;
+                const bf16_t* next = (pass == 0 && wave < 2) ? wq_f + 8 * kStride256 : nullptr;
+                mma_tile256(acc, A, bufa, bufb, wq_p, kStride256, next, kStride256, nl, kg);
+                wave_lds_fence();  // pass 1: the read-back of pass 0 is done
+                stage_tile256<false, false>(B, acc, nullptr, wave, nl, kg);
+                wave_lds_fence();
+                // rows leave as whole 128-byte lines: 8 lanes x 16 B per row, 8 rows per store instruction
+#pragma unroll
+                for (int k = 0; k < kTileRows / 8; ++k) {
+                    const int row = k * 8 + (lane >> 3);
+                    const long grow = row0 + row;
+                    const u32x4 v = *reinterpret_cast<const u32x4*>(B + row * kTileStride + (64 * wave) * 2 + (lane & 7) * 16);
+                    if (grow < p.M) *reinterpret_cast<u32x4*>(p.both + grow * kQueryCols + col0 + 64 * wave + (lane & 7) * 8) = v;
+                }
+            }
+            __syncthreads();  // A and B are rewritten by the next tile
+        }
+    }
+}
+
+template <bool TAIL, bool PROJ>
+int launch_block(const EncBlockArgs& a, size_t lds, hipStream_t stream) {
+    int dev = 0, cus = 0;  // persistent: two workgroups per CU
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        return fail(ALO_ERR_LAUNCH, "alo_encoder_block: cannot read the device's compute unit count");
+    const int gx = a.tiles < 2 * cus ? a.tiles : 2 * cus;
+    void* args[] = {const_cast<EncBlockArgs*>(&a)};
+    return launch<encoder_block_kernel<TAIL, PROJ>>(gx, 256, lds, stream, "alo_encoder_block", args);
+}
+
+}  // namespace
+}  // namespace alo
+
+using namespace alo;
+
+extern "C" int alo_encoder_block_abi_version(void) { return ALO_ENCODER_BLOCK_ABI_VERSION; }
+
+extern "C" int alo_encoder_block(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b,
+                                 const void* src, const void* w1_packed, const void* b1, const void* w2_packed, const void* b2,
+                                 const void* norm2_w, const void* norm2_b, void* src_out, const void* pos, const void* padding_mask,
+                                 const void* wv_packed, const void* bv, const void* wq_packed, const void* bq, void* value_hm,
+                                 void* offsets_logits, int batch, int S, int F, float eps1, float eps2, int dtype, void* stream) {
+    const char* what = "alo_encoder_block";
+    ALO_REQUIRE(src && w1_packed && b1 && w2_packed && b2 && norm2_w && norm2_b && src_out, ALO_ERR_INVALID_ARGUMENT,
+                "%s: null pointer argument", what);
+    const bool tail = attn_out || wo_packed || bo || norm1_w || norm1_b;
+    ALO_REQUIRE(!tail || (attn_out && wo_packed && bo && norm1_w && norm1_b), ALO_ERR_INVALID_ARGUMENT,
+                "%s: null pointer argument (attn_out, wo_packed, bo, norm1_w and norm1_b go together)", what);
+    const bool proj = pos || wv_packed || bv || wq_packed || bq || value_hm || offsets_logits;
+    ALO_REQUIRE(!proj || (pos && wv_packed && bv && wq_packed && bq && value_hm && offsets_logits), ALO_ERR_INVALID_ARGUMENT,
+                "%s: null pointer argument (pos, wv_packed, bv, wq_packed, bq, value_hm and offsets_logits go together)", what);
+    ALO_REQUIRE(proj || !padding_mask, ALO_ERR_INVALID_ARGUMENT, "%s: padding_mask without the projections it applies to", what);
+    ALO_REQUIRE(batch > 0 && S > 0 && F > 0 && F % 256 == 0, ALO_ERR_INVALID_ARGUMENT,
+                "%s: batch, S must be positive and the hidden width a positive multiple of 256 (batch=%d S=%d F=%d)", what, batch, S, F);
+    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "%s: bf16 only (dtype %d)", what, dtype);
+    ALO_REQUIRE(aligned16(attn_out, wo_packed, src, w1_packed, w2_packed, src_out, pos, wv_packed, wq_packed, value_hm, offsets_logits),
+                ALO_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+    // a tile's outputs are written while other tiles' inputs are still to be read: no output may overlap an input or another output
+    const size_t rows = (size_t)batch * S;
+    const struct { const void* p; size_t bytes; bool out; } spans[] = {
+        {attn_out, rows * 512, false}, {src, rows * 512, false}, {pos, rows * 512, false}, {padding_mask, rows, false},
+        {src_out, rows * 512, true}, {value_hm, rows * 512, true}, {offsets_logits, rows * 768, true}};
+    for (const auto& o : spans)
+        for (const auto& i : spans)
+            ALO_REQUIRE(!o.out || &o == &i || !o.p || !i.p || (const char*)o.p + o.bytes <= (const char*)i.p ||
+                            (const char*)i.p + i.bytes <= (const char*)o.p,
+                        ALO_ERR_INVALID_ARGUMENT, "%s: an output overlaps an input or another output", what);
+    EncBlockArgs a;
+    a.attn = (const bf16_t*)attn_out; a.wo = (const bf16_t*)wo_packed; a.bo = (const bf16_t*)bo;
+    a.g1 = (const bf16_t*)norm1_w; a.be1 = (const bf16_t*)norm1_b;
+    a.src = (const bf16_t*)src; a.w1 = (const bf16_t*)w1_packed; a.b1 = (const bf16_t*)b1; a.w2 = (const bf16_t*)w2_packed;
+    a.b2 = (const bf16_t*)b2; a.g2 = (const bf16_t*)norm2_w; a.be2 = (const bf16_t*)norm2_b;
+    a.out = (bf16_t*)src_out; a.pos = (const bf16_t*)pos; a.mask = (const unsigned char*)padding_mask;
+    a.wv = (const bf16_t*)wv_packed; a.bv = (const bf16_t*)bv; a.wq = (const bf16_t*)wq_packed; a.bq = (const bf16_t*)bq;
+    a.value = (bf16_t*)value_hm; a.both = (bf16_t*)offsets_logits;
+    a.M = (long)batch * S; a.S = S; a.F = F; a.tiles = (int)((a.M + kTileRows - 1) / kTileRows);
+    a.eps1 = eps1; a.eps2 = eps2;
+    const size_t lds = 2 * kTileRows * kTileStride + ((size_t)F + kTables) * sizeof(float);
+    ALO_REQUIRE(lds <= (size_t)kLdsLimit, ALO_ERR_UNSUPPORTED, "%s: hidden width %d needs %zu bytes of LDS", what, F, lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (tail) return proj ? launch_block<true, true>(a, lds, st) : launch_block<true, false>(a, lds, st);
+    return proj ? launch_block<false, true>(a, lds, st) : launch_block<false, false>(a, lds, st);
+}

@@ -12,12 +12,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxChunks = 4;  // C <= 64 lanes * 4 elements * 4 chunks = 1024
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ void load4(const float* p, float (&v)[4]) {
     const f32x4 x = *reinterpret_cast<const f32x4*>(p);
     v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];

@@ -227,8 +227,8 @@ int alo::linear_shortk_gather(const void* x, const void* weight, const void* bia
 namespace alo {
 namespace {
 
-constexpr int kFfnRows = 64;
-constexpr int kFfnStride = 256 * 2 + 16;  // LDS row stride of the 64 x 256 bf16 tiles (x, hidden chunk, output staging)
+constexpr int kFfnRows = kTileRows;
+constexpr int kFfnStride = kTileStride;  // LDS row stride of the 64 x 256 bf16 tiles (x, hidden chunk, output staging)
 
 struct FfnDims {
     long M;
@@ -254,61 +254,20 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
     for (int i = tid; i < F; i += 256) b1s[i] = B1 ? bf16_to_f32(B1[i].bits) : 0.f;
     b2s[tid] = B2 ? bf16_to_f32(B2[tid].bits) : 0.f;
 
-    // Weight fragments arrive in batches of KB k-steps (2 column tiles x KB x 16 B per lane) through two register buffers:
-    // batch i+1 is requested before batch i is consumed, across phase and round boundaries too (L2 latency ~ the MFMA time
-    // of one batch).  sched_barrier keeps the compiler from sinking the requests next to their first use.
-    constexpr int KB = 2;            // k-steps per batch
-    constexpr int NBATCH = 16 / KB;  // batches per phase
-    auto load_batch = [&](u32x4 (&buf)[2][KB], const bf16_t* frag0, size_t tile_stride, int batch) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < KB; ++j)
-                buf[t][j] = *reinterpret_cast<const u32x4*>(frag0 + t * tile_stride + (size_t)(KB * batch + j) * 512);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mma_batch = [&](f32x16 (&acc)[2][2], const unsigned char* a_lds, const u32x4 (&buf)[2][KB], int batch) {
-        u32x4 af[2][KB];  // A fragments of the whole batch first: their LDS latency overlaps instead of preceding each MFMA group
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            const int s = KB * batch + j;
-            af[0][j] = *reinterpret_cast<const u32x4*>(a_lds + nl * kFfnStride + (16 * s + 8 * kg) * 2);
-            af[1][j] = *reinterpret_cast<const u32x4*>(a_lds + (32 + nl) * kFfnStride + (16 * s + 8 * kg) * 2);
-        }
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            const u32x4 a0 = af[0][j], a1 = af[1][j];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a0), acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a0), acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a1), acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a1), acc[1][1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    // the weights stream through two register buffers, a batch ahead of their use (load_batch / mma_batch of common.hpp)
     const int fs = F / 16;  // k steps per output-column tile of the packed W2
     // packed fragment (row tile, k step) = 64 lanes x 16 B contiguous: a load instruction reads 8 whole lines
     auto w1_frag = [&](int r0) { return W1 + ((size_t)((r0 + 64 * wave) / 32) * 16 * 64 + lane) * 8; };  // tile stride 16 * 512
     auto w2_frag = [&](int r0) { return W2 + (((size_t)(2 * wave) * fs + r0 / 16) * 64 + lane) * 8; };     // tile stride fs * 512
 
     for (int tile = blockIdx.x; tile < dm.tiles; tile += gridDim.x) {
-        // ---- x tile -> LDS (64 rows x 512 B, 8 pieces of 16 B per thread, rows contiguous across lanes); rows past the end are
-        // read from the last row (never stored) so that all eight requests go out back to back -----------------------------
+        // ---- x tile -> LDS ------------------------------------------------------------------------------------------------
         {
             u32x4 xv[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int p = tid + 256 * j;
-                long row = (long)tile * kFfnRows + (p >> 5);
-                row = row < dm.M ? row : dm.M - 1;
-                xv[j] = *reinterpret_cast<const u32x4*>(X + row * 256 + (p & 31) * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int p = tid + 256 * j;
-                *reinterpret_cast<u32x4*>(xs + (p >> 5) * kFfnStride + (p & 31) * 16) = xv[j];
-            }
+            fetch_tile256(xv, X, (long)tile * kFfnRows, dm.M, tid);
+            park_tile256(xs, xv, tid);
         }
-        u32x4 bufa[2][KB], bufb[2][KB];
+        u32x4 bufa[2][kTileKB], bufb[2][kTileKB];
         load_batch(bufa, w1_frag(0), (size_t)16 * 512, 0);
         __syncthreads();
 
@@ -331,54 +290,17 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
                     for (int i = 0; i < 16; ++i) acc1[a][t][i] = 0.f;
             const bf16_t* w1p = w1_frag(r0);
             const bf16_t* w2p = w2_frag(r0);
-#pragma unroll
-            for (int bt = 0; bt < NBATCH; bt += 2) {
-                load_batch(bufb, w1p, (size_t)16 * 512, bt + 1);
-                mma_batch(acc1, xs, bufa, bt);
-                if (bt + 2 < NBATCH) load_batch(bufa, w1p, (size_t)16 * 512, bt + 2);
-                else load_batch(bufa, w2p, (size_t)fs * 512, 0);
-                mma_batch(acc1, xs, bufb, bt + 1);
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int col = 64 * wave + 32 * t + 8 * q + 4 * kg;  // registers 4 q .. 4 q + 3 = hidden units col .. col + 3
-                    const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + r0 + col);
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        const float v0 = relu_keep_nan(acc1[a][t][4 * q] + bb[0]), v1 = relu_keep_nan(acc1[a][t][4 * q + 1] + bb[1]);
-                        const float v2 = relu_keep_nan(acc1[a][t][4 * q + 2] + bb[2]), v3 = relu_keep_nan(acc1[a][t][4 * q + 3] + bb[3]);
-                        *reinterpret_cast<u32x2*>(hs + (32 * a + nl) * kFfnStride + col * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
-                    }
-                }
+            mma_tile256(acc1, xs, bufa, bufb, w1p, (size_t)16 * 512, w2p, (size_t)fs * 512, nl, kg);
+            stage_tile256<true, true>(hs, acc1, b1s + r0, wave, nl, kg);
             __syncthreads();  // the whole 64 x 256 hidden chunk is in LDS
 
             // ---- phase 2: out[:, 64 wave ..] += h_chunk (64 x 256) W2[64 wave + ..][r0 .. r0 + 256)^T ------------------------
-#pragma unroll
-            for (int bt = 0; bt < NBATCH; bt += 2) {
-                load_batch(bufb, w2p, (size_t)fs * 512, bt + 1);
-                mma_batch(acc2, hs, bufa, bt);
-                if (bt + 2 < NBATCH) load_batch(bufa, w2p, (size_t)fs * 512, bt + 2);
-                else if (r0 + 256 < F) load_batch(bufa, w1_frag(r0 + 256), (size_t)16 * 512, 0);
-                mma_batch(acc2, hs, bufb, bt + 1);
-            }
+            mma_tile256(acc2, hs, bufa, bufb, w2p, (size_t)fs * 512, r0 + 256 < F ? w1_frag(r0 + 256) : nullptr, (size_t)16 * 512, nl, kg);
             __syncthreads();  // everyone is done reading the chunk before it is overwritten
         }
 
         // ---- epilogue: + b2 -> bf16 -> staging (the hidden-chunk buffer) -> whole-line stores ---------------------------------
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int col = 64 * wave + 32 * t + 8 * q + 4 * kg;
-                const f32x4 bb = *reinterpret_cast<const f32x4*>(b2s + col);
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-                    *reinterpret_cast<u32x2*>(hs + (32 * a + nl) * kFfnStride + col * 2) =
-                        u32x2{pack_bf16x2(acc2[a][t][4 * q] + bb[0], acc2[a][t][4 * q + 1] + bb[1]),
-                              pack_bf16x2(acc2[a][t][4 * q + 2] + bb[2], acc2[a][t][4 * q + 3] + bb[3])};
-            }
+        stage_tile256<true, false>(hs, acc2, b2s, wave, nl, kg);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
