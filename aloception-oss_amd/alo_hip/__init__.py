@@ -1,5 +1,5 @@
-"""ctypes binding of ``libalo_hotpath.so`` (the C ABI declared in ``include/alo_hotpath.h`` and ``include/alo_corr_alt.h``) and of
-``libalo_two_stage.so`` (``include/alo_two_stage.h``).
+"""ctypes binding of ``libalo_hotpath.so``: one library, one ABI number, declared by the four headers under ``include/``
+(``alo_hotpath.h``, ``alo_corr_alt.h``, ``alo_two_stage.h``, ``alo_encoder_block.h``).
 
 This is the only place the host code touches the native library.  PyTorch is used for what it is good at here —
 device memory, streams, dtypes — and nothing else: every function below takes torch tensors, validates them the way
@@ -77,101 +77,69 @@ def build(force=False):
     return LIB_PATH
 
 
-def _declare(lib):
-    c = ctypes
-    vp, ip, sz = c.c_void_p, c.c_int, c.c_size_t
-    lib.alo_abi_version.restype = ip
-    lib.alo_abi_version.argtypes = []
-    lib.alo_last_error.restype = c.c_char_p
-    lib.alo_last_error.argtypes = []
-    lib.alo_msda_forward.restype = ip
-    lib.alo_msda_forward.argtypes = [vp] * 6 + [ip] * 9 + [vp]
-    lib.alo_msda_forward_fused.restype = ip
-    lib.alo_msda_forward_fused.argtypes = [vp] * 7 + [ip] * 9 + [vp]
-    lib.alo_msda_backward.restype = ip
-    lib.alo_msda_backward.argtypes = [vp] * 9 + [ip] * 9 + [vp]
-    lib.alo_msda_backward_hinted.restype = ip
-    lib.alo_msda_backward_hinted.argtypes = [vp] * 9 + [ip] * 9 + [c.POINTER(c.c_int32), vp]
-    lib.alo_msda_backward_path.restype = ip
-    lib.alo_msda_backward_path.argtypes = [ip] * 9 + [c.POINTER(c.c_int32)]
-    lib.alo_corr_level_shape.restype = None
-    lib.alo_corr_level_shape.argtypes = [ip, ip, ip, c.POINTER(ip), c.POINTER(ip)]
-    lib.alo_corr_build_workspace_bytes.restype = sz
-    lib.alo_corr_build_workspace_bytes.argtypes = [ip] * 5
-    lib.alo_corr_build.restype = ip
-    lib.alo_corr_build.argtypes = [vp, vp, c.POINTER(vp), vp, sz] + [ip] * 5 + [vp]
-    lib.alo_corr_lookup.restype = ip
-    lib.alo_corr_lookup.argtypes = [c.POINTER(vp), vp, vp] + [ip] * 5 + [vp]
-    lib.alo_corr_lookup_backward.restype = ip
-    lib.alo_corr_lookup_backward.argtypes = [c.POINTER(vp), vp, vp] + [ip] * 5 + [vp]
-    lib.alo_corr_lookup_backward_coords.restype = ip
-    lib.alo_corr_lookup_backward_coords.argtypes = [c.POINTER(vp), vp, vp, vp] + [ip] * 5 + [vp]
-    lib.alo_corr_alt_workspace_bytes.restype = sz
-    lib.alo_corr_alt_workspace_bytes.argtypes = [ip] * 5
-    lib.alo_corr_alt_prepare.restype = ip
-    lib.alo_corr_alt_prepare.argtypes = [vp, c.POINTER(vp), vp, sz] + [ip] * 5 + [vp]
-    lib.alo_corr_alt_lookup.restype = ip
-    lib.alo_corr_alt_lookup.argtypes = [vp, sz, vp, vp] + [ip] * 6 + [vp]
-    lib.alo_msda_forward_fused_hm.restype = ip
-    lib.alo_msda_forward_fused_hm_rows.restype = ip
-    lib.alo_msda_forward_fused_hm_rows.argtypes = [vp] * 5 + [c.c_long, c.c_long, vp, vp] + [ip] * 9 + [vp]
-    lib.alo_msda_forward_fused_hm.argtypes = [vp] * 7 + [ip] * 9 + [vp]
-    lib.alo_msda_forward_fused_hm_resident.restype = ip
-    lib.alo_msda_forward_fused_hm_resident.argtypes = [vp] * 5 + [c.c_long, c.c_long, vp, vp] + [ip] * 9 + [c.POINTER(c.c_int32), ip, vp]
-    lib.alo_msda_resident_levels.restype = ip
-    lib.alo_msda_resident_levels.argtypes = [c.POINTER(c.c_int32)] + [ip] * 6
-    lib.alo_value_head_major.restype = ip
-    lib.alo_value_head_major.argtypes = [vp] * 3 + [ip] * 5 + [vp]
-    lib.alo_bias_act_nchw.restype = ip
-    lib.alo_bias_act_nchw.argtypes = [vp] * 3 + [ip] * 4 + [vp]
-    lib.alo_gru_gate.restype = ip
-    lib.alo_gru_gate.argtypes = [vp] * 4 + [ip] * 3 + [c.c_long, c.c_long, vp]
-    lib.alo_gru_update.restype = ip
-    lib.alo_gru_update.argtypes = [vp] * 5 + [ip] * 3 + [c.c_long, vp]
-    lib.alo_pack_mfma_b.restype = ip
-    lib.alo_pack_mfma_b.argtypes = [vp, vp, ip, ip, ip, vp]
-    lib.alo_value_proj_head_major.restype = ip
-    lib.alo_value_proj_head_major.argtypes = [vp] * 5 + [ip] * 5 + [vp]
-    lib.alo_conv3x3_nhwc.restype = ip
-    lib.alo_conv3x3_nhwc.argtypes = [vp] * 5 + [ip] * 8 + [vp]
-    lib.alo_conv3x3_workspace_bytes.restype = c.c_size_t
-    lib.alo_conv3x3_workspace_bytes.argtypes = [ip] * 6
-    lib.alo_stem_conv_pool.restype = ip
-    lib.alo_stem_conv_pool.argtypes = [vp] * 4 + [ip] * 3 + [c.c_long] * 4 + [ip, vp]
-    lib.alo_groupnorm_rows_workspace_bytes.restype = c.c_size_t
-    lib.alo_groupnorm_rows_workspace_bytes.argtypes = [ip, ip, ip]
-    lib.alo_groupnorm_rows.restype = ip
-    lib.alo_groupnorm_rows.argtypes = [vp] * 5 + [ip] * 4 + [c.c_float, c.c_long, ip, vp]
-    lib.alo_groupnorm_rows_act.restype = ip
-    lib.alo_groupnorm_rows_act.argtypes = [vp] * 5 + [ip] * 4 + [c.c_float, c.c_long, ip, ip, vp]
-    lib.alo_conv3x3_small_nhwc.restype = ip
-    lib.alo_conv3x3_small_nhwc.argtypes = [vp] * 4 + [ip] * 6 + [vp]
-    lib.alo_upsample_add_nhwc.restype = ip
-    lib.alo_upsample_add_nhwc.argtypes = [vp] * 3 + [ip] * 8 + [vp]
-    lib.alo_linear_packed.restype = ip
-    lib.alo_linear_packed.argtypes = [vp] * 5 + [c.c_long, ip, ip, ip, ip, vp]
-    lib.alo_mask_pyramid.restype = ip
-    lib.alo_mask_pyramid.argtypes = [vp, ip, vp, vp, ip, ip, ip, ip, c.POINTER(c.c_int), c.c_uint, vp]
-    lib.alo_encoder_reference_points.restype = ip
-    lib.alo_encoder_reference_points.argtypes = [vp, vp, ip, ip, c.POINTER(c.c_int), vp]
-    lib.alo_conv1x1_nhwc.restype = ip
-    lib.alo_conv1x1_nhwc.argtypes = [vp, vp, ip, vp, vp, vp] + [ip] * 8 + [vp]
-    lib.alo_panoptic_onehot.restype = ip
-    lib.alo_panoptic_onehot.argtypes = [vp, vp] + [ip] * 6 + [c.c_float, vp]
-    lib.alo_ffn256.restype = ip
-    lib.alo_ffn256.argtypes = [vp] * 6 + [c.c_long, ip, ip, vp]
-    lib.alo_linear_shortk.restype = ip
-    lib.alo_linear_shortk.argtypes = [vp] * 5 + [c.c_long, ip, ip, ip, ip, vp]
-    lib.alo_pos_sine_flat.restype = ip
-    lib.alo_pos_sine_flat.argtypes = [vp] * 7 + [ip] * 6 + [c.c_float, c.c_float, ip, vp]
-    lib.alo_add_layernorm.restype = ip
-    lib.alo_add_layernorm.argtypes = [vp] * 7 + [c.c_long, ip, c.c_float, ip, vp]
-    lib.alo_bias_act.restype = ip
-    lib.alo_bias_act.argtypes = [vp] * 4 + [c.c_long, ip, ip, ip, vp]
+_vp, _ip, _i32p, _long, _f32, _size = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_long, ctypes.c_float, ctypes.c_size_t
+_vpp, _ipp = ctypes.POINTER(_vp), ctypes.POINTER(_ip)
+# name -> (restype, argtypes) of every function the four headers declare; an entry point that enqueues work ends in the stream
+_SIGNATURES = {
+    # include/alo_hotpath.h
+    "alo_abi_version": (_ip, []),
+    "alo_last_error": (ctypes.c_char_p, []),
+    "alo_msda_forward": (_ip, [_vp] * 6 + [_ip] * 9 + [_vp]),
+    "alo_msda_forward_fused": (_ip, [_vp] * 7 + [_ip] * 9 + [_vp]),
+    "alo_msda_forward_fused_hm": (_ip, [_vp] * 7 + [_ip] * 9 + [_vp]),
+    "alo_msda_forward_fused_hm_rows": (_ip, [_vp] * 5 + [_long, _long, _vp, _vp] + [_ip] * 9 + [_vp]),
+    "alo_msda_forward_fused_hm_resident": (_ip, [_vp] * 5 + [_long, _long, _vp, _vp] + [_ip] * 9 + [_i32p, _ip, _vp]),
+    "alo_msda_resident_levels": (_ip, [_i32p] + [_ip] * 6),
+    "alo_msda_backward": (_ip, [_vp] * 9 + [_ip] * 9 + [_vp]),
+    "alo_msda_backward_hinted": (_ip, [_vp] * 9 + [_ip] * 9 + [_i32p, _vp]),
+    "alo_msda_backward_path": (_ip, [_ip] * 9 + [_i32p]),
+    "alo_corr_level_shape": (None, [_ip, _ip, _ip, _ipp, _ipp]),
+    "alo_corr_build_workspace_bytes": (_size, [_ip] * 5),
+    "alo_corr_build": (_ip, [_vp, _vp, _vpp, _vp, _size] + [_ip] * 5 + [_vp]),
+    "alo_corr_lookup": (_ip, [_vpp, _vp, _vp] + [_ip] * 5 + [_vp]),
+    "alo_corr_lookup_backward": (_ip, [_vpp, _vp, _vp] + [_ip] * 5 + [_vp]),
+    "alo_corr_lookup_backward_coords": (_ip, [_vpp, _vp, _vp, _vp] + [_ip] * 5 + [_vp]),
+    "alo_value_head_major": (_ip, [_vp] * 3 + [_ip] * 5 + [_vp]),
+    "alo_value_proj_head_major": (_ip, [_vp] * 5 + [_ip] * 5 + [_vp]),
+    "alo_bias_act_nchw": (_ip, [_vp] * 3 + [_ip] * 4 + [_vp]),
+    "alo_gru_gate": (_ip, [_vp] * 4 + [_ip] * 3 + [_long, _long, _vp]),
+    "alo_gru_update": (_ip, [_vp] * 5 + [_ip] * 3 + [_long, _vp]),
+    "alo_pack_mfma_b": (_ip, [_vp, _vp, _ip, _ip, _ip, _vp]),
+    "alo_linear_shortk": (_ip, [_vp] * 5 + [_long, _ip, _ip, _ip, _ip, _vp]),
+    "alo_linear_packed": (_ip, [_vp] * 5 + [_long, _ip, _ip, _ip, _ip, _vp]),
+    "alo_ffn256": (_ip, [_vp] * 6 + [_long, _ip, _ip, _vp]),
+    "alo_conv1x1_nhwc": (_ip, [_vp, _vp, _ip, _vp, _vp, _vp] + [_ip] * 8 + [_vp]),
+    "alo_conv3x3_workspace_bytes": (_size, [_ip] * 6),
+    "alo_conv3x3_nhwc": (_ip, [_vp] * 5 + [_ip] * 8 + [_vp]),
+    "alo_conv3x3_small_nhwc": (_ip, [_vp] * 4 + [_ip] * 6 + [_vp]),
+    "alo_stem_conv_pool": (_ip, [_vp] * 4 + [_ip] * 3 + [_long] * 4 + [_ip, _vp]),
+    "alo_groupnorm_rows_workspace_bytes": (_size, [_ip, _ip, _ip]),
+    "alo_groupnorm_rows": (_ip, [_vp] * 5 + [_ip] * 4 + [_f32, _long, _ip, _vp]),
+    "alo_groupnorm_rows_act": (_ip, [_vp] * 5 + [_ip] * 4 + [_f32, _long, _ip, _ip, _vp]),
+    "alo_upsample_add_nhwc": (_ip, [_vp] * 3 + [_ip] * 8 + [_vp]),
+    "alo_mask_pyramid": (_ip, [_vp, _ip, _vp, _vp, _ip, _ip, _ip, _ip, _ipp, ctypes.c_uint, _vp]),
+    "alo_encoder_reference_points": (_ip, [_vp, _vp, _ip, _ip, _ipp, _vp]),
+    "alo_panoptic_onehot": (_ip, [_vp, _vp] + [_ip] * 6 + [_f32, _vp]),
+    "alo_pos_sine_flat": (_ip, [_vp] * 7 + [_ip] * 6 + [_f32, _f32, _ip, _vp]),
+    "alo_add_layernorm": (_ip, [_vp] * 7 + [_long, _ip, _f32, _ip, _vp]),
+    "alo_bias_act": (_ip, [_vp] * 4 + [_long, _ip, _ip, _ip, _vp]),
+    # include/alo_corr_alt.h
+    "alo_corr_alt_workspace_bytes": (_size, [_ip] * 5),
+    "alo_corr_alt_prepare": (_ip, [_vp, _vpp, _vp, _size] + [_ip] * 5 + [_vp]),
+    "alo_corr_alt_lookup": (_ip, [_vp, _size, _vp, _vp] + [_ip] * 6 + [_vp]),
+    # include/alo_two_stage.h
+    "alo_encoder_proposals": (_ip, [_vp, _vp, _vp, _ip, _ip, _ipp, _vp]),
+    "alo_encoder_proposals_masked": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _ip, _ipp, _ip, _ip, _vp]),
+    "alo_mask_rows": (_ip, [_vp, _vp, _vp, _long, _ip, _ip, _vp]),
+    "alo_proposal_queries": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _ip, _ip, _ip, _vp]),
+    # include/alo_encoder_block.h
+    "alo_encoder_block": (_ip, [_vp] * 21 + [_ip] * 3 + [_f32] * 2 + [_ip, _vp]),
+}
 
 
 def lib():
-    """The loaded library; raises :class:`HotpathUnavailable` (never falls back) when it cannot be loaded."""
+    """The loaded library; raises :class:`HotpathUnavailable` (never falls back) when it cannot be loaded, lacks an entry of
+    ``_SIGNATURES`` (built from an older tree) or has another ABI number."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -183,9 +151,15 @@ def lib():
             handle = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise HotpathUnavailable(f"cannot load {LIB_PATH}: {e}") from e
-        _declare(handle)
-        if handle.alo_abi_version() != 2:
-            raise HotpathUnavailable(f"{LIB_PATH} has ABI version {handle.alo_abi_version()}, expected 2")
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:
+                raise HotpathUnavailable(f"{LIB_PATH} does not export {name}: it was built from an older tree; "
+                                         f"rebuild it with `make -C {CSRC_DIR}`") from None
+            fn.restype, fn.argtypes = restype, argtypes
+        if handle.alo_abi_version() != 3:
+            raise HotpathUnavailable(f"{LIB_PATH} has ABI version {handle.alo_abi_version()}, expected 3")
         _lib = handle
     return _lib
 
@@ -297,7 +271,7 @@ class _timed:
         self.tag, self.nbytes, self.flops, self.relaunch = tag, nbytes, flops, relaunch
 
     def __enter__(self):
-        self.on = _timer is not None and (_timer.only is None or self.tag.startswith(_timer.only))
+        self.on = _timer is not None and self.tag is not None and (_timer.only is None or self.tag.startswith(_timer.only))
         if self.on:
             self.start = torch.cuda.Event(enable_timing=True)
             self.stop = torch.cuda.Event(enable_timing=True)
@@ -310,6 +284,20 @@ class _timed:
             _timer.records.append((self.tag, self.start, self.stop, self.nbytes, self.flops))
             if self.relaunch is not None:
                 _timer.relaunch[self.tag] = self.relaunch
+
+
+def _launch(symbol, device, tag, nbytes, flops, *args, relaunch=False):
+    """Enqueue entry point ``symbol`` on ``device``'s current torch stream: what ``alo::launch`` is to csrc.  A tensor in ``args``
+    stands for its device pointer (it is alive for the call), ``None`` for a null pointer, everything else is passed as it is; the
+    stream goes last.  The call is timed under ``tag`` (``None``: untimed) with its algorithmic ``nbytes`` / ``flops``; with
+    ``relaunch`` a running :class:`LaunchTimer` also gets a closure that repeats the call and keeps ``args`` alive for that."""
+    fn = getattr(lib(), symbol)
+
+    def call():
+        _check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], _stream(device)))
+
+    with torch.cuda.device(device), _timed(tag, nbytes, flops, relaunch=call if relaunch and _timer else None):
+        call()
 
 
 def msda_forward_bytes(N, S, M, D, L, Lq, P, elem, loc_elem=4):
@@ -360,9 +348,8 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
     N, S, M, D, L, Lq, P = dims
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     nbytes = msda_forward_bytes(N, S, M, D, L, Lq, P, value.element_size(), loc.element_size())
-    with torch.cuda.device(value.device), _timed(f"msda_fwd/Lq={Lq}", nbytes):
-        _check(lib().alo_msda_forward(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(loc), _ptr(attn),
-                                      _ptr(out), N, S, M, D, L, Lq, P, vdt, ldt, _stream(value.device)))
+    _launch("alo_msda_forward", value.device, f"msda_fwd/Lq={Lq}", nbytes, 0.0, value, spatial_shapes, level_start_index, loc, attn,
+            out, N, S, M, D, L, Lq, P, vdt, ldt)
     return out
 
 
@@ -400,10 +387,8 @@ def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offset
     # bytes actually streamed by the fused launch: value + out + raw offsets/logits (value dtype) + reference points
     e = value.element_size()
     nbytes = e * (N * S * M * D + N * Lq * M * D + N * Lq * M * L * P * 3) + reference_points.element_size() * reference_points.numel()
-    with torch.cuda.device(value.device), _timed(f"msda_fwd_fused/Lq={Lq}", nbytes):
-        _check(lib().alo_msda_forward_fused(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index),
-                                            _ptr(sampling_offsets), _ptr(attn_logits), _ptr(reference_points), _ptr(out),
-                                            N, S, M, D, L, Lq, P, ref_dim, vdt, _stream(value.device)))
+    _launch("alo_msda_forward_fused", value.device, f"msda_fwd_fused/Lq={Lq}", nbytes, 0.0, value, spatial_shapes, level_start_index,
+            sampling_offsets, attn_logits, reference_points, out, N, S, M, D, L, Lq, P, ref_dim, vdt)
     return out
 
 
@@ -423,9 +408,8 @@ def value_head_major(value, padding_mask=None):
             raise RuntimeError("padding_mask must be a (N, S) bool CUDA tensor")
         padding_mask = padding_mask.contiguous()
     out = torch.empty((N, M, S, D), dtype=value.dtype, device=value.device)
-    with torch.cuda.device(value.device), _timed(f"value_head_major/S={S}", 2 * value.element_size() * value.numel()):
-        _check(lib().alo_value_head_major(_ptr(value), None if padding_mask is None else _ptr(padding_mask), _ptr(out),
-                                          N, S, M, D, _DTYPE_CODE[value.dtype], _stream(value.device)))
+    _launch("alo_value_head_major", value.device, f"value_head_major/S={S}", 2 * value.element_size() * value.numel(), 0.0,
+            value, padding_mask, out, N, S, M, D, _DTYPE_CODE[value.dtype])
     return out
 
 
@@ -481,22 +465,11 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
         starts = (ctypes.c_int32 * (2 * L))(*[int(v) for hw in host for v in hw])
 
     policy = RESIDENT_ALWAYS if resident == "always" else RESIDENT_AUTO
-
-    def launch():
-        if starts is not None:
-            _check(lib().alo_msda_forward_fused_hm_resident(_ptr(value_hm), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                            _ptr(sampling_offsets), _ptr(attn_logits), off_rs, log_rs,
-                                                            _ptr(reference_points), _ptr(out), N, S, M, D, L, Lq, P, ref_dim,
-                                                            _DTYPE_CODE[value_hm.dtype], starts, policy, _stream(value_hm.device)))
-            return
-        _check(lib().alo_msda_forward_fused_hm_rows(_ptr(value_hm), _ptr(spatial_shapes), _ptr(level_start_index),
-                                                    _ptr(sampling_offsets), _ptr(attn_logits), off_rs, log_rs,
-                                                    _ptr(reference_points), _ptr(out), N, S, M, D, L, Lq, P, ref_dim,
-                                                    _DTYPE_CODE[value_hm.dtype], _stream(value_hm.device)))
-
     tag = "msda_fwd_fused_resident" if starts is not None and lib().alo_msda_resident_levels(starts, N, S, M, L, Lq, policy) else "msda_fwd_fused"
-    with torch.cuda.device(value_hm.device), _timed(f"{tag}/Lq={Lq}", nbytes, relaunch=launch if _timer else None):
-        launch()
+    symbol, hint = ("alo_msda_forward_fused_hm_rows", ()) if starts is None else ("alo_msda_forward_fused_hm_resident", (starts, policy))
+    _launch(symbol, value_hm.device, f"{tag}/Lq={Lq}", nbytes, 0.0, value_hm, spatial_shapes, level_start_index, sampling_offsets,
+            attn_logits, off_rs, log_rs, reference_points, out, N, S, M, D, L, Lq, P, ref_dim, _DTYPE_CODE[value_hm.dtype], *hint,
+            relaunch=True)
     return out
 
 
@@ -527,9 +500,6 @@ def _wide_backward_wants_host_shapes(value, dims, ldt):
     return value.dtype in (torch.float32, torch.bfloat16) and ldt == ALO_F32 and D in (32, 64) and L == 4 and P == 4 and Lq == S
 
 
-_tiled_backward_eligible = _wide_backward_wants_host_shapes   # the helper's earlier name (it never described the tiled kernel): kept for callers
-
-
 def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step=64):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight].  Replaces ``alonet_custom::ms_deform_attn_backward``."""
     dims, vdt, ldt, loc, attn = _msda_prepare(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
@@ -545,14 +515,8 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     # only the encoder's self-attention on the DETR-family shape can use the hint (it sizes the grid of query blocks)
     host = _host_spatial_shapes(spatial_shapes) if _wide_backward_wants_host_shapes(value, dims, ldt) else None
     hint = None if host is None else (ctypes.c_int32 * (2 * L))(*[int(v) for hw in host for v in hw])
-
-    def launch():
-        _check(lib().alo_msda_backward_hinted(_ptr(value), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(loc), _ptr(attn),
-                                              _ptr(grad_output), _ptr(grad_value), _ptr(grad_loc), _ptr(grad_attn),
-                                              N, S, M, D, L, Lq, P, vdt, ldt, hint, _stream(value.device)))
-
-    with torch.cuda.device(value.device), _timed(f"msda_bwd/Lq={Lq}", nbytes, relaunch=launch if _timer else None):
-        launch()
+    _launch("alo_msda_backward_hinted", value.device, f"msda_bwd/Lq={Lq}", nbytes, 0.0, value, spatial_shapes, level_start_index, loc,
+            attn, grad_output, grad_value, grad_loc, grad_attn, N, S, M, D, L, Lq, P, vdt, ldt, hint, relaunch=True)
     return [grad_value.to(value.dtype), grad_loc.to(sampling_loc.dtype), grad_attn.to(attn_weight.dtype)]
 
 
@@ -586,13 +550,9 @@ def corr_build(fmap1, fmap2, num_levels=4):
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=fmap1.device)
     ptrs = (ctypes.c_void_p * num_levels)(*[t.data_ptr() for t in levels])
     ncols = sum(h * w for h, w in shapes)
-    def launch():   # keeps fmaps, levels and workspace alive for LaunchTimer.replay_samples
-        _check(lib().alo_corr_build(_ptr(fmap1), _ptr(fmap2), ptrs, _ptr(ws), nbytes, B, C, H, W, num_levels,
-                                    _stream(fmap1.device)))
-
-    with torch.cuda.device(fmap1.device), _timed("corr_build", 4.0 * (2 * B * C * H * W + B * H * W * ncols),
-                                                 2.0 * B * (H * W) * (H * W) * C, relaunch=launch if _timer else None):
-        launch()
+    # relaunch: the closure keeps the feature maps and the workspace alive for LaunchTimer.replay_samples
+    _launch("alo_corr_build", fmap1.device, "corr_build", 4.0 * (2 * B * C * H * W + B * H * W * ncols), 2.0 * B * (H * W) * (H * W) * C,
+            fmap1, fmap2, ptrs, ws, nbytes, B, C, H, W, num_levels, relaunch=True)
     # ws may be released now: the caching allocator keeps the block bound to this stream until the kernels retire
     return levels
 
@@ -625,8 +585,7 @@ def corr_lookup(levels, coords, radius=4):
     out = torch.empty((B, L * (2 * radius + 1) ** 2, H, W), dtype=torch.float32, device=coords.device)
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2)
-    with torch.cuda.device(coords.device), _timed("corr_lookup", nbytes):
-        _check(lib().alo_corr_lookup(ptrs, _ptr(coords), _ptr(out), B, H, W, radius, L, _stream(coords.device)))
+    _launch("alo_corr_lookup", coords.device, "corr_lookup", nbytes, 0.0, ptrs, coords, out, B, H, W, radius, L)
     return out
 
 
@@ -638,8 +597,7 @@ def corr_lookup_backward(grad_levels, coords, grad_out, radius=4):
                                                              "corr_lookup_backward")
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + 2 * L * taps + 2)
-    with torch.cuda.device(coords.device), _timed("corr_lookup_backward", nbytes):
-        _check(lib().alo_corr_lookup_backward(ptrs, _ptr(coords), _ptr(grad_out), B, H, W, radius, L, _stream(coords.device)))
+    _launch("alo_corr_lookup_backward", coords.device, "corr_lookup_backward", nbytes, 0.0, ptrs, coords, grad_out, B, H, W, radius, L)
     return grad_levels
 
 
@@ -651,9 +609,8 @@ def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
     per_level = torch.empty((B, L, 2, H, W), dtype=torch.float32, device=coords.device)
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2 + 2 * L)
-    with torch.cuda.device(coords.device), _timed("corr_lookup_backward_coords", nbytes):
-        _check(lib().alo_corr_lookup_backward_coords(ptrs, _ptr(coords), _ptr(grad_out), _ptr(per_level), B, H, W, radius, L,
-                                                     _stream(coords.device)))
+    _launch("alo_corr_lookup_backward_coords", coords.device, "corr_lookup_backward_coords", nbytes, 0.0, ptrs, coords, grad_out,
+            per_level, B, H, W, radius, L)
     return per_level.sum(1)
 
 
@@ -674,8 +631,7 @@ def corr_alt_prepare(fmap1, fmap2_levels):
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=fmap1.device)
     ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels])
     moved = 4.0 * 2 * (fmap1.numel() + sum(t.numel() for t in levels))
-    with torch.cuda.device(fmap1.device), _timed("corr_alt_prepare", moved):
-        _check(lib().alo_corr_alt_prepare(_ptr(fmap1), ptrs, _ptr(ws), nbytes, B, C, H, W, L, _stream(fmap1.device)))
+    _launch("alo_corr_alt_prepare", fmap1.device, "corr_alt_prepare", moved, 0.0, fmap1, ptrs, ws, nbytes, B, C, H, W, L)
     return ws
 
 
@@ -693,9 +649,8 @@ def corr_alt_lookup(workspace, coords, channels, num_levels, radius=4):
     out = torch.empty((B, L * win, H, W), dtype=torch.float32, device=coords.device)
     flops = 2.0 * B * H * W * L * (2 * radius + 2) ** 2 * C          # the lattice's inner products (the mixes are noise)
     nbytes = 4.0 * B * H * W * (L * win + 2 + L * C)                 # out + coords + fmap1 once per level (footprints: cache hits)
-    with torch.cuda.device(coords.device), _timed("corr_alt_lookup", nbytes, flops):
-        _check(lib().alo_corr_alt_lookup(_ptr(workspace), workspace.numel(), _ptr(coords), _ptr(out), B, C, H, W, radius, L,
-                                         _stream(coords.device)))
+    _launch("alo_corr_alt_lookup", coords.device, "corr_alt_lookup", nbytes, flops, workspace, workspace.numel(), coords, out,
+            B, C, H, W, radius, L)
     return out
 
 
@@ -747,11 +702,8 @@ def add_layernorm(x, residual, weight, bias, eps=1e-5, pos=None):
     out = torch.empty_like(x)
     out_pos = None if pos is None else torch.empty_like(x)
     nbytes = x.element_size() * x.numel() * (2 + (residual is not None) + 2 * (pos is not None))
-    with torch.cuda.device(x.device), _timed(f"add_layernorm/rows={rows}", nbytes):
-        _check(lib().alo_add_layernorm(_ptr(x), None if residual is None else _ptr(residual), _ptr(weight), _ptr(bias),
-                                       _ptr(out), None if pos is None else _ptr(pos),
-                                       None if pos is None else _ptr(out_pos), rows, C, float(eps),
-                                       _DTYPE_CODE[x.dtype], _stream(x.device)))
+    _launch("alo_add_layernorm", x.device, f"add_layernorm/rows={rows}", nbytes, 0.0, x, residual, weight, bias, out, pos, out_pos,
+            rows, C, float(eps), _DTYPE_CODE[x.dtype])
     return out if pos is None else (out, out_pos)
 
 
@@ -774,9 +726,8 @@ def bias_act_(x, bias, residual=None, relu=True):
         raise RuntimeError("bias_act_: residual must have the dtype of x")
     bias = bias.to(x.dtype).contiguous()
     nbytes = x.element_size() * x.numel() * (2 + (residual is not None))
-    with torch.cuda.device(x.device), _timed(f"bias_act/C={C}", nbytes):
-        _check(lib().alo_bias_act(_ptr(x), _ptr(bias), None if residual is None else _ptr(residual), _ptr(x),
-                                  x.numel() // C, C, 1 if relu else 0, _DTYPE_CODE[x.dtype], _stream(x.device)))
+    _launch("alo_bias_act", x.device, f"bias_act/C={C}", nbytes, 0.0, x, bias, residual, x, x.numel() // C, C, 1 if relu else 0,
+            _DTYPE_CODE[x.dtype])
     return x
 
 
@@ -790,9 +741,8 @@ def bias_act_nchw_(x, bias, relu=True):
     """In place: ``x = act(x + bias[None, :, None, None])`` — the bias MIOpen would add in a second kernel plus the ReLU."""
     _require_f32_nchw("x", x)
     B, C, H, W = x.shape
-    with torch.cuda.device(x.device), _timed(f"bias_act_nchw/C={C}", 8.0 * x.numel()):
-        _check(lib().alo_bias_act_nchw(_ptr(x), _ptr(bias.float().contiguous()), _ptr(x), B, C, H * W, 1 if relu else 0,
-                                       _stream(x.device)))
+    _launch("alo_bias_act_nchw", x.device, f"bias_act_nchw/C={C}", 8.0 * x.numel(), 0.0, x, bias.float().contiguous(), x, B, C, H * W,
+            1 if relu else 0)
     return x
 
 
@@ -802,9 +752,8 @@ def gru_gate_(zr, bias_zr, hx, rhx, C):
     B, C2, H, W = zr.shape
     if C2 != 2 * C or hx.shape != rhx.shape or hx.shape[0] != B or hx.shape[2:] != zr.shape[2:] or hx.shape[1] < C:
         raise RuntimeError("gru_gate_: zr must be (B,2C,H,W) and hx / rhx (B,C+Cx,H,W)")
-    with torch.cuda.device(zr.device), _timed(f"gru_gate/C={C}", 4.0 * B * C * H * W * 5):
-        _check(lib().alo_gru_gate(_ptr(zr), _ptr(bias_zr), _ptr(hx), _ptr(rhx), B, C, H * W, hx.stride(0), rhx.stride(0),
-                                  _stream(zr.device)))
+    _launch("alo_gru_gate", zr.device, f"gru_gate/C={C}", 4.0 * B * C * H * W * 5, 0.0, zr, bias_zr, hx, rhx, B, C, H * W,
+            hx.stride(0), rhx.stride(0))
 
 
 def gru_update_(q, bias_q, zr, hx, C, net=None):
@@ -815,9 +764,8 @@ def gru_update_(q, bias_q, zr, hx, C, net=None):
         raise RuntimeError("gru_update_: q must be (B,C,H,W), zr (B,2C,H,W), hx (B,C+Cx,H,W)")
     if net is not None:
         _require_f32_nchw("net", net)
-    with torch.cuda.device(q.device), _timed(f"gru_update/C={C}", 4.0 * B * C * H * W * (4 + (net is not None))):
-        _check(lib().alo_gru_update(_ptr(q), _ptr(bias_q), _ptr(zr), _ptr(hx), None if net is None else _ptr(net), B, C,
-                                    H * W, hx.stride(0), _stream(q.device)))
+    _launch("alo_gru_update", q.device, f"gru_update/C={C}", 4.0 * B * C * H * W * (4 + (net is not None)), 0.0, q, bias_q, zr, hx, net,
+            B, C, H * W, hx.stride(0))
 
 
 def pos_sine_flat(mask_flatten, spatial_shapes, level_start_index, dim_t, level_embed, normalize, center, scale, dtype,
@@ -835,11 +783,9 @@ def pos_sine_flat(mask_flatten, spatial_shapes, level_start_index, dim_t, level_
             raise RuntimeError("pos_sine_flat: level_embed must be (L, 2 * num_pos_feats)")
     out = torch.empty((B, S, 2 * F), dtype=dtype, device=mask_flatten.device)
     work = torch.empty((B, S, 2), dtype=torch.float32, device=mask_flatten.device)
-    with torch.cuda.device(out.device), _timed(f"pos_sine_flat/S={S}", out.element_size() * out.numel()):
-        _check(lib().alo_pos_sine_flat(_ptr(mask_flatten), _ptr(spatial_shapes), _ptr(level_start_index), _ptr(dim_t),
-                                       None if level_embed is None else _ptr(level_embed), _ptr(out), _ptr(work), B, S, L, F,
-                                       1 if normalize else 0, 1 if center else 0, float(scale), float(eps),
-                                       _DTYPE_CODE[dtype], _stream(out.device)))
+    _launch("alo_pos_sine_flat", out.device, f"pos_sine_flat/S={S}", out.element_size() * out.numel(), 0.0, mask_flatten, spatial_shapes,
+            level_start_index, dim_t, level_embed, out, work, B, S, L, F, 1 if normalize else 0, 1 if center else 0, float(scale),
+            float(eps), _DTYPE_CODE[dtype])
     return out
 
 
@@ -866,10 +812,8 @@ def linear_shortk(x, weight, bias=None, relu=False, residual=None):
             raise RuntimeError("linear_shortk: residual must be a contiguous (M, N) tensor of x's dtype")
     if M:
         nbytes = 2.0 * (x2.numel() + y.numel() * (2 if residual is not None else 1))
-        with torch.cuda.device(x.device), _timed(f"linear_shortk/N={N},K={K}", nbytes, 2.0 * M * N * K):
-            _check(lib().alo_linear_shortk(_ptr(x2), _ptr(weight.contiguous()), None if bias is None else _ptr(bias.contiguous()),
-                                           None if residual is None else _ptr(residual), _ptr(y), M, N, K, 1 if relu else 0,
-                                           ALO_BF16, _stream(x.device)))
+        _launch("alo_linear_shortk", x.device, f"linear_shortk/N={N},K={K}", nbytes, 2.0 * M * N * K, x2, weight.contiguous(),
+                None if bias is None else bias.contiguous(), residual, y, M, N, K, 1 if relu else 0, ALO_BF16)
     return y.view(*x.shape[:-1], N)
 
 
@@ -898,11 +842,8 @@ def linear_packed(x, weight, bias=None, relu=False, residual=None):
     if M:
         packed = pack_mfma_b(weight)
         bias_c = None if bias is None else bias.to(x.dtype).contiguous()
-        with torch.cuda.device(x.device), _timed(f"linear_packed/K={K}/N={N}", 2.0 * (M * K + M * N * (2 if residual is not None else 1)),
-                                                 2.0 * M * N * K):
-            _check(lib().alo_linear_packed(_ptr(x2), _ptr(packed), None if bias_c is None else _ptr(bias_c),
-                                           None if residual is None else _ptr(residual), _ptr(y), M, N, K, 1 if relu else 0,
-                                           ALO_BF16, _stream(x.device)))
+        _launch("alo_linear_packed", x.device, f"linear_packed/K={K}/N={N}", 2.0 * (M * K + M * N * (2 if residual is not None else 1)),
+                2.0 * M * N * K, x2, packed, bias_c, residual, y, M, N, K, 1 if relu else 0, ALO_BF16)
     return y.view(*x.shape[:-1], N)
 
 
@@ -930,10 +871,8 @@ def conv1x1_strided(x, weight2d, bias, stride, relu=False):
     packed = not linear_shortk_supported(x.permute(0, 2, 3, 1), weight2d)
     wt = pack_mfma_b(weight2d) if packed else weight2d.contiguous()
     bias_c = None if bias is None else bias.to(x.dtype).contiguous()
-    with torch.cuda.device(x.device), _timed(f"conv1x1_strided/K={cin}/N={cout}", 2.0 * (y.numel() // cout * cin + y.numel()),
-                                             2.0 * y.numel() * cin):
-        _check(lib().alo_conv1x1_nhwc(_ptr(x), _ptr(wt), 1 if packed else 0, None if bias_c is None else _ptr(bias_c), None, _ptr(y),
-                                      n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16, _stream(x.device)))
+    _launch("alo_conv1x1_nhwc", x.device, f"conv1x1_strided/K={cin}/N={cout}", 2.0 * (y.numel() // cout * cin + y.numel()),
+            2.0 * y.numel() * cin, x, wt, 1 if packed else 0, bias_c, None, y, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16)
     return y
 
 
@@ -976,8 +915,7 @@ def pack_mfma_b(weight):
 def _pack_mfma_b(w):
     """The pack kernel on a contiguous (N, K) bf16 matrix."""
     packed = torch.empty_like(w)
-    with torch.cuda.device(w.device):
-        _check(lib().alo_pack_mfma_b(_ptr(w), _ptr(packed), w.shape[0], w.shape[1], ALO_BF16, _stream(w.device)))
+    _launch("alo_pack_mfma_b", w.device, None, 0.0, 0.0, w, packed, w.shape[0], w.shape[1], ALO_BF16)   # once per weight version: untimed
     return packed
 
 
@@ -992,10 +930,8 @@ def ffn256(x, w1, b1, w2, b2):
     M, Fh = x2.shape[0], w1.shape[0]
     if M:
         p1, p2 = pack_mfma_b(w1), pack_mfma_b(w2)
-        with torch.cuda.device(x.device), _timed(f"ffn256/F={Fh}", 4.0 * x2.numel(), 4.0 * M * 256 * Fh):
-            _check(lib().alo_ffn256(_ptr(x2), _ptr(p1), None if b1 is None else _ptr(b1.contiguous()),
-                                    _ptr(p2), None if b2 is None else _ptr(b2.contiguous()), _ptr(y), M, Fh,
-                                    ALO_BF16, _stream(x.device)))
+        _launch("alo_ffn256", x.device, f"ffn256/F={Fh}", 4.0 * x2.numel(), 4.0 * M * 256 * Fh, x2, p1,
+                None if b1 is None else b1.contiguous(), p2, None if b2 is None else b2.contiguous(), y, M, Fh, ALO_BF16)
     return y.view(x.shape)
 
 
@@ -1025,10 +961,8 @@ def conv3x3(x, weight, bias=None, relu=False, stride=1):
     bias_c = None if bias is None else bias.contiguous()
     ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, stride)   # split-K partial sums (few-tile shapes only)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
-    with torch.cuda.device(x.device), _timed(f"conv3x3/C={cin}/s={stride}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel()):
-        _check(lib().alo_conv3x3_nhwc(_ptr(x), _ptr(packed), None if bias_c is None else _ptr(bias_c), _ptr(y),
-                                      None if ws is None else _ptr(ws), n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16,
-                                      _stream(x.device)))
+    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3/C={cin}/s={stride}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
+            x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16)
     return y
 
 
@@ -1057,9 +991,8 @@ def stem_conv_pool(x, weight, bias=None):
     y = torch.empty((n, 64, hp, wp), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.contiguous()
     sn, sc, sh, sw = x.stride()
-    with torch.cuda.device(x.device), _timed("stem_conv_pool", 2.0 * (x.numel() + y.numel()), 2.0 * 147 * 64 * n * hc * wc):
-        _check(lib().alo_stem_conv_pool(_ptr(x), _ptr(packed), None if bias_c is None else _ptr(bias_c), _ptr(y), n, h, w_,
-                                        sn, sc, sh, sw, ALO_BF16, _stream(x.device)))
+    _launch("alo_stem_conv_pool", x.device, "stem_conv_pool", 2.0 * (x.numel() + y.numel()), 2.0 * 147 * 64 * n * hc * wc,
+            x, packed, bias_c, y, n, h, w_, sn, sc, sh, sw, ALO_BF16)
     return y
 
 
@@ -1091,10 +1024,8 @@ def groupnorm_nhwc(x, norm, relu=False):
     if n and h * w_:
         nbytes = lib().alo_groupnorm_rows_workspace_bytes(n, h * w_, norm.num_groups)
         ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device), _timed(f"groupnorm_nhwc/C={c_}", 6.0 * x.numel()):
-            _check(lib().alo_groupnorm_rows_act(_ptr(rows), _ptr(norm.weight.contiguous()), _ptr(norm.bias.contiguous()), _ptr(out),
-                                                _ptr(ws), n, h * w_, c_, norm.num_groups, float(norm.eps), h * w_ * c_,
-                                                1 if relu else 0, ALO_BF16, _stream(x.device)))
+        _launch("alo_groupnorm_rows_act", x.device, f"groupnorm_nhwc/C={c_}", 6.0 * x.numel(), 0.0, rows, norm.weight.contiguous(),
+                norm.bias.contiguous(), out, ws, n, h * w_, c_, norm.num_groups, float(norm.eps), h * w_ * c_, 1 if relu else 0, ALO_BF16)
     return out
 
 
@@ -1136,8 +1067,8 @@ def conv3x3_small(x, conv):
     frag, bias32 = _small_conv_operands(conv)
     y = torch.empty((n, cout, h, w_), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     if y.numel():
-        with torch.cuda.device(x.device), _timed(f"conv3x3_small/C={cin}->{cout}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * cout * n * h * w_):
-            _check(lib().alo_conv3x3_small_nhwc(_ptr(x), _ptr(frag), _ptr(bias32), _ptr(y), n, h, w_, cin, cout, ALO_BF16, _stream(x.device)))
+        _launch("alo_conv3x3_small_nhwc", x.device, f"conv3x3_small/C={cin}->{cout}", 2.0 * (x.numel() + y.numel()),
+                2.0 * 9 * cin * cout * n * h * w_, x, frag, bias32, y, n, h, w_, cin, cout, ALO_BF16)
     return y
 
 
@@ -1157,8 +1088,8 @@ def upsample_add(x_low, fpn):
     b_, _, H, W = fpn.shape
     out = torch.empty((bq, c_, H, W), dtype=x_low.dtype, device=x_low.device, memory_format=torch.channels_last)
     if out.numel():
-        with torch.cuda.device(x_low.device), _timed(f"upsample_add/C={c_}", 2.0 * (out.numel() + x_low.numel() + fpn.numel())):
-            _check(lib().alo_upsample_add_nhwc(_ptr(x_low), _ptr(fpn), _ptr(out), bq, bq // b_, c_, h, w_, H, W, ALO_BF16, _stream(x_low.device)))
+        _launch("alo_upsample_add_nhwc", x_low.device, f"upsample_add/C={c_}", 2.0 * (out.numel() + x_low.numel() + fpn.numel()), 0.0,
+                x_low, fpn, out, bq, bq // b_, c_, h, w_, H, W, ALO_BF16)
     return out
 
 
@@ -1176,10 +1107,8 @@ def groupnorm_rows(x, weight, bias, groups, eps=1e-5, out=None):
     if b_ and hw:
         nbytes = lib().alo_groupnorm_rows_workspace_bytes(b_, hw, groups)
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device), _timed(f"groupnorm_rows/HW={hw}", 6.0 * x.numel()):
-            _check(lib().alo_groupnorm_rows(_ptr(x), _ptr(weight.contiguous()), _ptr(bias.contiguous()), _ptr(out), _ptr(ws), b_, hw,
-                                            c_, groups, float(eps), out.stride(0) if b_ > 1 else hw * c_, ALO_BF16,
-                                            _stream(x.device)))
+        _launch("alo_groupnorm_rows", x.device, f"groupnorm_rows/HW={hw}", 6.0 * x.numel(), 0.0, x, weight.contiguous(), bias.contiguous(),
+                out, ws, b_, hw, c_, groups, float(eps), out.stride(0) if b_ > 1 else hw * c_, ALO_BF16)
     return out
 
 
@@ -1209,9 +1138,8 @@ def mask_pyramid(frame_mask, shapes, nearest_levels=()):
     bits = 0
     for l in nearest_levels:
         bits |= 1 << int(l)
-    with torch.cuda.device(frame_mask.device), _timed("mask_pyramid", float(frame_mask.numel() + mask_flat.numel())):
-        _check(lib().alo_mask_pyramid(_ptr(frame_mask), 1 if frame_mask.dtype == torch.float32 else 0, _ptr(mask_flat), _ptr(ratios),
-                                      b_, h, w_, L, arr, bits, _stream(frame_mask.device)))
+    _launch("alo_mask_pyramid", frame_mask.device, "mask_pyramid", float(frame_mask.numel() + mask_flat.numel()), 0.0, frame_mask,
+            1 if frame_mask.dtype == torch.float32 else 0, mask_flat, ratios, b_, h, w_, L, arr, bits)
     return mask_flat.view(torch.bool), ratios
 
 
@@ -1225,9 +1153,8 @@ def encoder_reference_points(valid_ratios, shapes):
         raise RuntimeError("encoder_reference_points: one (h, w) per level of valid_ratios")
     S = sum(int(a) * int(b) for a, b in shapes)
     out = torch.empty((valid_ratios.shape[0], S, L, 2), dtype=torch.float32, device=valid_ratios.device)
-    with torch.cuda.device(valid_ratios.device), _timed("encoder_reference_points", 4.0 * out.numel()):
-        _check(lib().alo_encoder_reference_points(_ptr(valid_ratios), _ptr(out), valid_ratios.shape[0], L, arr,
-                                                  _stream(valid_ratios.device)))
+    _launch("alo_encoder_reference_points", valid_ratios.device, "encoder_reference_points", 4.0 * out.numel(), 0.0, valid_ratios, out,
+            valid_ratios.shape[0], L, arr)
     return out
 
 
@@ -1247,41 +1174,12 @@ def value_proj_head_major(x, weight, bias, padding_mask, heads):
             raise RuntimeError("padding_mask must be a (N, S) bool tensor")
         padding_mask = padding_mask.contiguous()
     out = torch.empty((N, heads, S, 32), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device), _timed(f"value_proj_hm/S={S}", 2.0 * (x.numel() + out.numel()), 2.0 * N * S * heads * 32 * K):
-        _check(lib().alo_value_proj_head_major(_ptr(x), _ptr(weight.contiguous()), None if bias is None else _ptr(bias.contiguous()),
-                                               None if padding_mask is None else _ptr(padding_mask), _ptr(out), N, S, heads, K,
-                                               ALO_BF16, _stream(x.device)))
+    _launch("alo_value_proj_head_major", x.device, f"value_proj_hm/S={S}", 2.0 * (x.numel() + out.numel()), 2.0 * N * S * heads * 32 * K,
+            x, weight.contiguous(), None if bias is None else bias.contiguous(), padding_mask, out, N, S, heads, K, ALO_BF16)
     return out
 
 
-# ---- the encoder layer's row-local chain in one kernel (libalo_encoder_block.so, include/alo_encoder_block.h) ---------------------
-ENCODER_BLOCK_LIB_PATH = os.path.join(_PKG_ROOT, "libalo_encoder_block.so")
-_encoder_block_lib = None
-
-
-def encoder_block_lib():
-    """The loaded libalo_encoder_block.so (it reports errors through libalo_hotpath.so's ``alo_last_error``); raises
-    :class:`HotpathUnavailable` when it is missing or has another ABI."""
-    global _encoder_block_lib
-    if _encoder_block_lib is None:
-        lib()   # first: the library links against it
-        if not os.path.exists(ENCODER_BLOCK_LIB_PATH):
-            raise HotpathUnavailable(f"{ENCODER_BLOCK_LIB_PATH} is missing: build it with `make -C {CSRC_DIR}` (hipcc, --offload-arch=gfx950)")
-        try:
-            handle = ctypes.CDLL(ENCODER_BLOCK_LIB_PATH)
-        except OSError as e:  # pragma: no cover - depends on the box
-            raise HotpathUnavailable(f"cannot load {ENCODER_BLOCK_LIB_PATH}: {e}") from e
-        vp, ip = ctypes.c_void_p, ctypes.c_int
-        handle.alo_encoder_block_abi_version.restype = ip
-        handle.alo_encoder_block_abi_version.argtypes = []
-        handle.alo_encoder_block.restype = ip
-        handle.alo_encoder_block.argtypes = [vp] * 21 + [ip] * 3 + [ctypes.c_float] * 2 + [ip, vp]
-        if handle.alo_encoder_block_abi_version() != 1:
-            raise HotpathUnavailable(f"{ENCODER_BLOCK_LIB_PATH} has ABI version {handle.alo_encoder_block_abi_version()}, expected 1")
-        _encoder_block_lib = handle
-    return _encoder_block_lib
-
-
+# ---- the encoder layer's row-local chain in one kernel (include/alo_encoder_block.h) -------------------------------------------------
 def encoder_block_enabled():
     """``ALO_ENC_BLOCK=off`` (read per call) keeps the encoder on its separate launches: for tests and profiling."""
     return os.environ.get("ALO_ENC_BLOCK", "on").lower() not in ("off", "0")
@@ -1346,15 +1244,12 @@ def encoder_block(src, w1, b1, w2, b2, norm2, tail=None, nxt=None):
         if tuple(w.shape) != shape or w.dtype != dt or w.device != dev:
             raise RuntimeError(f"encoder_block: {name} must be a {shape} tensor of src's dtype on its device")
     f_args = [src, pack_mfma_b(w1), _vec(b1, dt), pack_mfma_b(w2), _vec(b2, dt), _vec(norm2[0], dt), _vec(norm2[1], dt), out]
-    ptr = lambda t: None if t is None else _ptr(t)
     rows = N * S
     # what the result needs: src, src' (+ attn_out) (+ pos, value, offsets + logits, mask bytes)
     nbytes = 2.0 * rows * (256 * (2 + (tail is not None) + 2 * (nxt is not None)) + 384 * (nxt is not None)) + rows * (nxt is not None)
     flops = 2.0 * rows * 256 * (2 * Fh + 256 * (tail is not None) + (256 + 384) * (nxt is not None))
     tag = f"encoder_block/{'tail+' if tail is not None else ''}ffn{'+proj' if nxt is not None else ''}/rows={rows}"
-    with torch.cuda.device(dev), _timed(tag, nbytes, flops):
-        _check(encoder_block_lib().alo_encoder_block(*[ptr(t) for t in t_args + f_args + n_args], N, S, Fh, float(eps1), float(norm2[2]),
-                                                     ALO_BF16, _stream(dev)))
+    _launch("alo_encoder_block", dev, tag, nbytes, flops, *t_args, *f_args, *n_args, N, S, Fh, float(eps1), float(norm2[2]), ALO_BF16)
     return out, value, both
 
 
@@ -1369,46 +1264,11 @@ def panoptic_onehot(mask_logits, frame_size, threshold=0.5):
     H, W = int(frame_size[0]), int(frame_size[1])
     out = torch.empty((b_, q, H, W), dtype=torch.long, device=x.device)
     if out.numel():
-        with torch.cuda.device(x.device), _timed("panoptic_onehot", 8.0 * out.numel()):
-            _check(lib().alo_panoptic_onehot(_ptr(x), _ptr(out), b_, q, h, w_, H, W, float(threshold), _stream(x.device)))
+        _launch("alo_panoptic_onehot", x.device, "panoptic_onehot", 8.0 * out.numel(), 0.0, x, out, b_, q, h, w_, H, W, float(threshold))
     return out
 
 
-# ---- two-stage Deformable-DETR: proposals, row masking, decoder queries (libalo_two_stage.so, include/alo_two_stage.h) ------------
-TWO_STAGE_LIB_PATH = os.path.join(_PKG_ROOT, "libalo_two_stage.so")
-_two_stage_lib = None
-
-
-def two_stage_lib():
-    """The loaded libalo_two_stage.so (it reports errors through libalo_hotpath.so's ``alo_last_error``); raises
-    :class:`HotpathUnavailable` when it is missing or has another ABI."""
-    global _two_stage_lib
-    if _two_stage_lib is None:
-        lib()   # first: the two-stage library links against it
-        if not os.path.exists(TWO_STAGE_LIB_PATH):
-            raise HotpathUnavailable(f"{TWO_STAGE_LIB_PATH} is missing: build it with `make -C {CSRC_DIR}` (hipcc, --offload-arch=gfx950)")
-        try:
-            handle = ctypes.CDLL(TWO_STAGE_LIB_PATH)
-        except OSError as e:  # pragma: no cover - depends on the box
-            raise HotpathUnavailable(f"cannot load {TWO_STAGE_LIB_PATH}: {e}") from e
-        c = ctypes
-        vp, ip = c.c_void_p, c.c_int
-        handle.alo_two_stage_abi_version.restype = ip
-        handle.alo_two_stage_abi_version.argtypes = []
-        handle.alo_encoder_proposals.restype = ip
-        handle.alo_encoder_proposals.argtypes = [vp, vp, vp, ip, ip, c.POINTER(c.c_int), vp]
-        handle.alo_encoder_proposals_masked.restype = ip
-        handle.alo_encoder_proposals_masked.argtypes = [vp, vp, vp, vp, vp, ip, ip, c.POINTER(c.c_int), ip, ip, vp]
-        handle.alo_mask_rows.restype = ip
-        handle.alo_mask_rows.argtypes = [vp, vp, vp, c.c_long, ip, ip, vp]
-        handle.alo_proposal_queries.restype = ip
-        handle.alo_proposal_queries.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, vp]
-        if handle.alo_two_stage_abi_version() != 1:
-            raise HotpathUnavailable(f"{TWO_STAGE_LIB_PATH} has ABI version {handle.alo_two_stage_abi_version()}, expected 1")
-        _two_stage_lib = handle
-    return _two_stage_lib
-
-
+# ---- two-stage Deformable-DETR: proposals, row masking, decoder queries (include/alo_two_stage.h) ---------------------------------
 def encoder_proposals_supported(mask_flatten, shapes):
     """CUDA, contiguous (B, S) bool / uint8 mask of fewer than 2^31 tokens over at most 8 non-empty levels.  (The mask carries no
     gradient; whether the caller's other tensors do is the caller's question: :func:`fusable`.)"""
@@ -1428,9 +1288,8 @@ def encoder_proposals(mask_flatten, shapes):
     arr, L = _host_shapes(shapes)
     proposals = torch.empty((B, S, 4), dtype=torch.float32, device=mask_flatten.device)
     keep = torch.empty((B, S), dtype=torch.uint8, device=mask_flatten.device)
-    with torch.cuda.device(mask_flatten.device), _timed(f"encoder_proposals/S={S}", 18.0 * B * S):
-        _check(two_stage_lib().alo_encoder_proposals(_ptr(mask_flatten), _ptr(proposals), _ptr(keep), B, L, arr,
-                                                     _stream(mask_flatten.device)))
+    _launch("alo_encoder_proposals", mask_flatten.device, f"encoder_proposals/S={S}", 18.0 * B * S, 0.0, mask_flatten, proposals, keep,
+            B, L, arr)
     return proposals, keep.view(torch.bool)
 
 
@@ -1450,9 +1309,9 @@ def encoder_proposals_masked(mask_flatten, shapes, memory):
     proposals = torch.empty((B, S, 4), dtype=torch.float32, device=mask_flatten.device)
     keep = torch.empty((B, S), dtype=torch.uint8, device=mask_flatten.device)
     out = torch.empty_like(memory)
-    with torch.cuda.device(memory.device), _timed(f"encoder_proposals_masked/S={S}", 2.0 * memory.element_size() * memory.numel() + 18.0 * B * S):
-        _check(two_stage_lib().alo_encoder_proposals_masked(_ptr(mask_flatten), _ptr(proposals), _ptr(keep), _ptr(memory), _ptr(out), B, L,
-                                                            arr, memory.shape[-1], _DTYPE_CODE[memory.dtype], _stream(memory.device)))
+    _launch("alo_encoder_proposals_masked", memory.device, f"encoder_proposals_masked/S={S}",
+            2.0 * memory.element_size() * memory.numel() + 18.0 * B * S, 0.0, mask_flatten, proposals, keep, memory, out, B, L, arr,
+            memory.shape[-1], _DTYPE_CODE[memory.dtype])
     return proposals, keep.view(torch.bool), out
 
 
@@ -1471,9 +1330,8 @@ def mask_rows(memory, keep):
     C = memory.shape[-1]
     rows = memory.numel() // C
     out = torch.empty_like(memory)
-    with torch.cuda.device(memory.device), _timed(f"mask_rows/rows={rows}", 2.0 * memory.element_size() * memory.numel() + rows):
-        _check(two_stage_lib().alo_mask_rows(_ptr(memory), _ptr(keep), _ptr(out), rows, C, _DTYPE_CODE[memory.dtype],
-                                             _stream(memory.device)))
+    _launch("alo_mask_rows", memory.device, f"mask_rows/rows={rows}", 2.0 * memory.element_size() * memory.numel() + rows, 0.0,
+            memory, keep, out, rows, C, _DTYPE_CODE[memory.dtype])
     return out
 
 
@@ -1506,7 +1364,6 @@ def proposal_queries(coords_unact, topk, dtype, owner=None):
     ref = torch.empty((B, K, 4), dtype=torch.float32, device=coords_unact.device)
     embed = torch.empty((B, K, 512), dtype=dtype, device=coords_unact.device)
     dim_t = proposal_dim_t(coords_unact.device, owner)
-    with torch.cuda.device(coords_unact.device), _timed(f"proposal_queries/K={K}", B * K * (8.0 + 32.0 + 512.0 * embed.element_size())):
-        _check(two_stage_lib().alo_proposal_queries(_ptr(coords_unact), _ptr(topk), _ptr(dim_t), _ptr(ref), _ptr(embed), B, S, K,
-                                                    _DTYPE_CODE[dtype], _stream(coords_unact.device)))
+    _launch("alo_proposal_queries", coords_unact.device, f"proposal_queries/K={K}", B * K * (8.0 + 32.0 + 512.0 * embed.element_size()),
+            0.0, coords_unact, topk, dim_t, ref, embed, B, S, K, _DTYPE_CODE[dtype])
     return ref, embed

@@ -324,8 +324,6 @@ int launch_block(const EncBlockArgs& a, size_t lds, hipStream_t stream) {
 
 using namespace alo;
 
-extern "C" int alo_encoder_block_abi_version(void) { return ALO_ENCODER_BLOCK_ABI_VERSION; }
-
 extern "C" int alo_encoder_block(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b,
                                  const void* src, const void* w1_packed, const void* b1, const void* w2_packed, const void* b2,
                                  const void* norm2_w, const void* norm2_b, void* src_out, const void* pos, const void* padding_mask,

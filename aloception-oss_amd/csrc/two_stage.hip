@@ -192,8 +192,6 @@ proposal_queries_kernel(const float* __restrict__ coords, const long long* __res
 
 using namespace alo;
 
-extern "C" int alo_two_stage_abi_version(void) { return ALO_TWO_STAGE_ABI_VERSION; }
-
 // Level geometry of a launch whose blocks take `tokens_per_block` tokens of one (image, level); 0 or an error code.
 static int prop_dims(PropDims& dm, int B, int L, const int* level_shapes_host, int tokens_per_block, const char* what) {
     ALO_REQUIRE(B > 0 && L > 0 && L <= kMaxLevels, ALO_ERR_INVALID_ARGUMENT, "%s: needs B >= 1 and 1 <= L <= %d (got B = %d, L = %d)", what, kMaxLevels, B, L);

@@ -6,9 +6,9 @@
  * kept; every lookup computes the (2r+2)^2 inner products under each query's window on the fly and interpolates them.
  * The result equals alo_corr_lookup on alo_corr_build's pyramid up to fp32 rounding (2x2 means commute with the inner product).
  *
- * Part of libalo_hotpath.so and bound to the conventions of alo_hotpath.h: device pointers on the current HIP device, work
- * enqueued on `stream` (a hipStream_t as void*), no allocation and no synchronisation, ALO_OK or an alo_status_t with a
- * message in alo_last_error(), argument errors detected before anything is enqueued.
+ * Part of libalo_hotpath.so, under its one ABI number (alo_abi_version()), and bound to the conventions of alo_hotpath.h: device
+ * pointers on the current HIP device, work enqueued on `stream` (a hipStream_t as void*), no allocation and no synchronisation,
+ * ALO_OK or an alo_status_t with a message in alo_last_error(), argument errors detected before anything is enqueued.
  *
  * Limits (index arithmetic of the kernels): 1 <= B <= 65535, 1 <= C <= 65536, H * W <= 2^26, 1 <= num_levels <= 8,
  * 0 <= radius <= 7, and no pyramid level may be empty (alo_corr_level_shape: floor-halving per level).  Levels one pixel wide

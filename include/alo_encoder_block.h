@@ -14,11 +14,10 @@
  * are those of alo_linear_shortk, alo_add_layernorm, alo_ffn256 and alo_value_proj_head_major of alo_hotpath.h, so the results equal
  * the chain of those launches bit for bit.
  *
- * Built as libalo_encoder_block.so next to libalo_hotpath.so, which it links against for the launch path's error string: a failing
- * call leaves its message in alo_last_error() of alo_hotpath.h, and the alo_status_t codes are that header's.  The ABI number of
- * alo_hotpath.h does not cover this file; alo_encoder_block_abi_version() does.  Conventions are the same: device pointers on the
- * current HIP device, 16-byte aligned, work enqueued on `stream` (a hipStream_t as void*), no allocation, no synchronisation,
- * argument errors detected before anything is enqueued.  Forward only, bf16 only, d_model = 256, 8 heads of 32 channels.
+ * Part of libalo_hotpath.so, under its one ABI number (alo_abi_version()), and bound to the conventions of alo_hotpath.h: device
+ * pointers on the current HIP device, 16-byte aligned, work enqueued on `stream` (a hipStream_t as void*), no allocation, no
+ * synchronisation, ALO_OK or an alo_status_t with a message in alo_last_error(), argument errors detected before anything is
+ * enqueued.  Forward only, bf16 only, d_model = 256, 8 heads of 32 channels.
  */
 #ifndef ALO_ENCODER_BLOCK_H
 #define ALO_ENCODER_BLOCK_H
@@ -28,9 +27,6 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-
-#define ALO_ENCODER_BLOCK_ABI_VERSION 1
-int alo_encoder_block_abi_version(void);
 
 /*
  * All matrices are bf16; every *_packed weight is alo_pack_mfma_b of the row-major (N, K) weight; biases and LayerNorm parameters

@@ -1,8 +1,9 @@
 /*
  * alo_hotpath.h — C ABI of the MI355X (gfx950) dense-vision hot path of aloception.
  *
- * One shared library (libalo_hotpath.so, built from aloception-oss_amd/csrc/ with hipcc) exports exactly the entry
- * points the reference's own binding for this path would bind.  Plain pointers and sizes only: no torch / ATen types.
+ * One shared library (libalo_hotpath.so, built from aloception-oss_amd/csrc/ with hipcc) under one ABI number exports exactly
+ * the entry points of four headers, one per feature group: this one, alo_corr_alt.h, alo_two_stage.h and alo_encoder_block.h.
+ * Plain pointers and sizes only: no torch / ATen types.
  *
  * What each entry point replaces in the reference (/root/reference):
  *   alo_msda_forward   <- alonet_custom::ms_deform_attn_forward   alonet/deformable_detr/ops/src/vision.cpp:21-24,
@@ -33,7 +34,8 @@
 extern "C" {
 #endif
 
-#define ALO_HOTPATH_ABI_VERSION 2   /* 2: alo_corr_lookup_conv1x1[_kpad] removed (round 5), alo_msda_backward_path added */
+#define ALO_HOTPATH_ABI_VERSION 3   /* 3: the entry points of alo_two_stage.h and alo_encoder_block.h are part of this library;
+                                          their own version functions and *_ABI_VERSION macros are gone */
 
 typedef enum alo_status {
     ALO_OK = 0,

@@ -7,11 +7,9 @@
  * replace the element-wise torch chains around them (per-level meshgrid / divide / window test / log / two masked_fill pairs;
  * gather / sigmoid / divide / sin / cos / stack / flatten).
  *
- * Built as libalo_two_stage.so next to libalo_hotpath.so, which it links against for the launch path's error string:
- * a failing call leaves its message in alo_last_error() of alo_hotpath.h, and the alo_status_t codes are that header's.  The
- * ABI number of alo_hotpath.h does not cover this file; alo_two_stage_abi_version() does.  Conventions are the same: device
+ * Part of libalo_hotpath.so, under its one ABI number (alo_abi_version()), and bound to the conventions of alo_hotpath.h: device
  * pointers on the current HIP device, work enqueued on `stream` (a hipStream_t as void*), no allocation, no synchronisation,
- * argument errors detected before anything is enqueued.  Forward only.
+ * ALO_OK or an alo_status_t with a message in alo_last_error(), argument errors detected before anything is enqueued.  Forward only.
  *
  * Limits: 1 <= B, 1 <= L <= 8 levels, every level non-empty, B * S < 2^31 tokens, B * K < 2^31.
  */
@@ -23,9 +21,6 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-
-#define ALO_TWO_STAGE_ABI_VERSION 1
-int alo_two_stage_abi_version(void);
 
 /*
  * Box proposal of every token (gen_encoder_output_proposals, :145-171).

@@ -1,5 +1,33 @@
-"""Shared generators for the parity tests (seeded, numpy)."""
+"""Shared generators for the parity tests (seeded, numpy), and the census of the C ABI (headers against the library)."""
+import os
+import re
+import subprocess
+
 import numpy as np
+
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+HEADERS = ("alo_hotpath.h", "alo_corr_alt.h", "alo_two_stage.h", "alo_encoder_block.h")   # one library, one per feature group
+
+
+def header_text(header):
+    """``include/<header>`` without its comments."""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
+
+
+def declared_functions(header):
+    """Sorted names of the ``alo_*`` functions that ``include/<header>`` declares."""
+    return sorted(set(re.findall(r"\b(alo_[a-z0-9_]+)\s*\(", header_text(header))))
+
+
+def exported_alo_functions(path):
+    """The ``alo_*`` functions that the shared object at ``path`` defines in its dynamic symbol table."""
+    out = subprocess.run(["readelf", "--dyn-syms", "-W", path], capture_output=True, text=True, check=True).stdout
+    exported = set()
+    for line in out.splitlines():
+        cols = line.split()   # Num: Value Size Type Bind Vis Ndx Name
+        if len(cols) == 8 and cols[3] == "FUNC" and cols[6] != "UND" and cols[7].startswith("alo_"):
+            exported.add(cols[7].split("@")[0])
+    return exported
 
 
 def level_start(shapes):

@@ -1,60 +1,66 @@
-"""The C-ABI library loads without a GPU and exports exactly what include/alo_hotpath.h declares.  CPU only."""
+"""The C-ABI library loads without a GPU and exports exactly what the four headers under include/ declare; alo_hip's signature
+table names the same functions.  CPU only."""
 import ctypes
-import os
 import re
+import subprocess
 
 import pytest
 
 import alo_hip
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "alo_hotpath.h")
+from helpers import HEADERS, declared_functions, exported_alo_functions, header_text
 
 
-def declared_functions(header=HEADER):
-    text = open(header).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(alo_[a-z0-9_]+)\s*\(", text)))
+def all_declared():
+    return {name for header in HEADERS for name in declared_functions(header)}
 
 
 def test_header_declares_the_expected_entry_points():
-    assert declared_functions() == sorted(
+    assert declared_functions("alo_hotpath.h") == sorted(
         ["alo_abi_version", "alo_last_error", "alo_msda_forward", "alo_msda_forward_fused", "alo_msda_backward", "alo_msda_backward_hinted", "alo_msda_backward_path", "alo_corr_level_shape",
          "alo_corr_build_workspace_bytes", "alo_corr_build", "alo_corr_lookup", "alo_corr_lookup_backward", "alo_corr_lookup_backward_coords", "alo_add_layernorm", "alo_bias_act", "alo_msda_forward_fused_hm", "alo_msda_forward_fused_hm_rows", "alo_msda_forward_fused_hm_resident", "alo_msda_resident_levels", "alo_value_head_major", "alo_bias_act_nchw", "alo_gru_gate", "alo_gru_update", "alo_pos_sine_flat", "alo_linear_shortk", "alo_ffn256", "alo_pack_mfma_b", "alo_value_proj_head_major", "alo_conv3x3_nhwc", "alo_conv3x3_workspace_bytes", "alo_stem_conv_pool", "alo_mask_pyramid", "alo_panoptic_onehot", "alo_encoder_reference_points", "alo_linear_packed", "alo_conv1x1_nhwc", "alo_groupnorm_rows", "alo_groupnorm_rows_workspace_bytes", "alo_groupnorm_rows_act", "alo_upsample_add_nhwc", "alo_conv3x3_small_nhwc"]
     )
+    assert declared_functions("alo_encoder_block.h") == ["alo_encoder_block"]
 
 
 def test_library_exports_every_declared_symbol():
     lib = alo_hip.lib()
-    for name in declared_functions():
+    for name in all_declared():
         assert hasattr(lib, name), f"{name} missing from {alo_hip.LIB_PATH}"
-    assert lib.alo_abi_version() == 2
+    assert lib.alo_abi_version() == 3
     assert lib.alo_last_error() is not None
 
 
 def test_library_exports_nothing_but_the_declared_symbols():
     """Every alo_* function in the dynamic symbol table is declared in a public header: helpers shared between the library's
     own sources have C++ linkage (namespace alo) and never look like entry points."""
-    import subprocess
-
-    out = subprocess.run(["readelf", "--dyn-syms", "-W", alo_hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set()
-    for line in out.splitlines():
-        cols = line.split()   # Num: Value Size Type Bind Vis Ndx Name
-        if len(cols) == 8 and cols[3] == "FUNC" and cols[6] != "UND" and cols[7].startswith("alo_"):
-            exported.add(cols[7].split("@")[0])
-    declared = set(declared_functions()) | set(declared_functions(os.path.join(ROOT, "include", "alo_corr_alt.h")))
+    exported, declared = exported_alo_functions(alo_hip.LIB_PATH), all_declared()
     assert exported == declared, (sorted(exported - declared), sorted(declared - exported))
 
 
 def test_no_torch_symbols_in_the_abi():
-    """The boundary is plain C: the shared object must not link libtorch / libc10."""
-    import subprocess
-
+    """The boundary is plain C: the shared object must not link libtorch / libc10, nor a second library of this project."""
     out = subprocess.run(["readelf", "-d", alo_hip.LIB_PATH], capture_output=True, text=True).stdout
     needed = "\n".join(line for line in out.splitlines() if "NEEDED" in line)   # library names only, not addresses
-    assert "torch" not in needed and "c10" not in needed
+    assert "torch" not in needed and "c10" not in needed and "[libalo_" not in needed
     assert "libamdhip64" in needed
+
+
+def test_signature_table_names_what_the_headers_declare():
+    """alo_hip._SIGNATURES has one entry per declared function, and an entry ends in the stream's c_void_p exactly where the header's
+    prototype ends in ``void* stream``.  Names and that one property: the prototypes themselves are not compared."""
+    assert set(alo_hip._SIGNATURES) == all_declared()
+    text = " ".join(header_text(header) for header in HEADERS)
+    for name, (_, argtypes) in alo_hip._SIGNATURES.items():
+        params = re.search(rf"\b{name}\s*\(([^)]*)\)", text).group(1)
+        assert (bool(argtypes) and argtypes[-1] is ctypes.c_void_p) == params.rstrip().endswith("void* stream"), name
+
+
+def test_stale_library_fails_loudly(monkeypatch):
+    """A library built before an entry point was added: lib() names the missing symbol instead of an AttributeError in some forward."""
+    monkeypatch.setattr(alo_hip, "_lib", None)
+    monkeypatch.setattr(alo_hip, "_SIGNATURES", {**alo_hip._SIGNATURES, "alo_not_built_yet": (ctypes.c_int, [ctypes.c_void_p])})
+    with pytest.raises(alo_hip.HotpathUnavailable, match="alo_not_built_yet"):
+        alo_hip.lib()
 
 
 def test_pyramid_shape_helpers():

@@ -1,8 +1,6 @@
 """AlternateCorrBlock without a GPU: the torch yardstick on the G6 goldens, and the C ABI of include/alo_corr_alt.h (exports,
 argument checks before any launch)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,9 +8,7 @@ import torch
 
 import alo_hip
 from alonet.raft.corr import TorchAlternateCorrBlock
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "alo_corr_alt.h")
+from helpers import declared_functions
 
 
 def t(a):
@@ -39,13 +35,8 @@ def test_torch_block_keeps_the_reference_pyramid():
     torch.testing.assert_close(blk.pyramid[1][0], torch.nn.functional.avg_pool2d(f, 2, stride=2))
 
 
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(alo_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_library_exports_every_function_of_the_header():
-    names = declared_functions()
+    names = declared_functions("alo_corr_alt.h")
     assert names == ["alo_corr_alt_lookup", "alo_corr_alt_prepare", "alo_corr_alt_workspace_bytes"]
     lib = alo_hip.lib()
     for name in names:

@@ -105,7 +105,7 @@ def test_a_nan_stays_in_its_row(weights, form):
 
 def test_argument_errors_are_reported_before_anything_is_enqueued(weights):
     w = weights[1024]
-    lib = alo_hip.encoder_block_lib()
+    lib = alo_hip.lib()
     N, S, Fh = 2, 70, 1024
     big = lambda cols: torch.zeros(N * S * cols + 64, dtype=BF, device=DEV)   # room for a 2-byte shifted view
     bufs = dict(attn=big(256), src=big(256), out=big(256), pos=big(256), value=big(256), both=big(384))

@@ -1,11 +1,7 @@
 """Two-stage Deformable-DETR on the CPU: module wiring, parameter names and the torch restatements of the proposal arithmetic
-against the reference's own outputs (G19, tests/golden/make_golden_two_stage.py), plus the C ABI of libalo_two_stage.so.
+against the reference's own outputs (G19, tests/golden/make_golden_two_stage.py), plus the C ABI of include/alo_two_stage.h.
 
 As in test_models_cpu.py the deformable attention runs through the reference's ``is_tracing`` escape hatch (pure-torch op)."""
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 import torch
@@ -15,11 +11,9 @@ import alo_hip
 from alonet.deformable_detr import DeformableDETR, DeformableTransformer
 from alonet.deformable_detr.deformable_transformer import encoder_output_proposals, proposal_pos_embed
 from alonet.transformers import MLP
-from helpers import formula_state_dict
+from helpers import declared_functions, formula_state_dict
 
 t = torch.from_numpy
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "alo_two_stage.h")
 
 
 def build_g19_transformer(g, attach_heads=True):
@@ -193,38 +187,15 @@ def test_two_stage_model_forward_on_the_torch_branch():
         assert p.grad is not None and torch.isfinite(p.grad).all() and float(p.grad.abs().max()) > 0
 
 
-# ---- C ABI of libalo_two_stage.so -------------------------------------------------------------------------------------------
-def declared_functions(header=HEADER):
-    text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(alo_[a-z0-9_]+)\s*\(", text)))
-
-
+# ---- C ABI of include/alo_two_stage.h (the library's whole export set is held to its headers in test_cabi.py) ------------------
 def test_header_declares_the_three_kernels():   # and the first two as one launch
-    assert declared_functions() == ["alo_encoder_proposals", "alo_encoder_proposals_masked", "alo_mask_rows", "alo_proposal_queries",
-                                    "alo_two_stage_abi_version"]
-
-
-def test_library_exports_exactly_the_declared_symbols():
-    lib = alo_hip.two_stage_lib()
-    for name in declared_functions():
-        assert hasattr(lib, name), f"{name} missing from {alo_hip.TWO_STAGE_LIB_PATH}"
-    assert lib.alo_two_stage_abi_version() == 1
-    out = subprocess.run(["readelf", "--dyn-syms", "-W", alo_hip.TWO_STAGE_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set()
-    for line in out.splitlines():
-        cols = line.split()   # Num: Value Size Type Bind Vis Ndx Name
-        if len(cols) == 8 and cols[3] == "FUNC" and cols[6] != "UND" and cols[7].startswith("alo_"):
-            exported.add(cols[7].split("@")[0])
-    assert exported == set(declared_functions())
-    needed = subprocess.run(["readelf", "-d", alo_hip.TWO_STAGE_LIB_PATH], capture_output=True, text=True).stdout
-    needed = "\n".join(line for line in needed.splitlines() if "NEEDED" in line)
-    assert "libalo_hotpath.so" in needed and "libamdhip64" in needed and "torch" not in needed and "c10" not in needed
+    assert declared_functions("alo_two_stage.h") == ["alo_encoder_proposals", "alo_encoder_proposals_masked", "alo_mask_rows", "alo_proposal_queries"]
 
 
 def test_argument_errors_are_reported_before_any_launch():
     import ctypes
 
-    lib, hot = alo_hip.two_stage_lib(), alo_hip.lib()
+    lib = hot = alo_hip.lib()
     one = ctypes.c_void_p(16)   # never dereferenced: validation fails first
     shapes = (ctypes.c_int * 18)(*([2, 2] * 9))
     assert lib.alo_encoder_proposals(None, None, None, 1, 1, shapes, None) == 1 and b"null pointer" in hot.alo_last_error()
