@@ -20,9 +20,11 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_PKG_ROOT, "libalo_hotpath.so")
 CSRC_DIR = os.path.join(_PKG_ROOT, "csrc")
 
-ALO_F32, ALO_F64, ALO_BF16 = 0, 1, 2
+ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
-_DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16}
+# fp16 is a value dtype of the MSDA entry points and of value_head_major only; every other user of this table sits behind a gate that
+# names fp32 / bf16 (fusable, *_supported), so an fp16 tensor never reaches a kernel that lacks it
+_DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
 
 _lib = None
 _warned_inference_tensor = False
@@ -333,8 +335,8 @@ def _msda_prepare(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     vdt = _DTYPE_CODE.get(value.dtype)
     if vdt is None:
         raise RuntimeError(f"ms_deform_attn: unsupported value dtype {value.dtype}")
-    if value.dtype == torch.bfloat16:
-        # bf16 storage: sampling geometry stays fp32 (bf16 locations would cost ~0.3 px at 167-wide maps)
+    if value.dtype in (torch.bfloat16, torch.float16):
+        # 16-bit storage: sampling geometry stays fp32 (bf16 locations would cost ~0.3 px at 167-wide maps, fp16 ones 0.08 px)
         sampling_loc, attn_weight = sampling_loc.float(), attn_weight.float()
     elif sampling_loc.dtype != value.dtype or attn_weight.dtype != value.dtype:
         raise RuntimeError("sampling_loc and attn_weight must have the dtype of value")
@@ -368,7 +370,8 @@ def _check_fused_operands(value, spatial_shapes, level_start_index, sampling_off
 
 def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points):
     """MSDeformAttn's prologue + gather in one launch (inference): raw offsets (N,Lq,M,L,P,2) and raw attention logits
-    (N,Lq,M,L*P) in ``value``'s dtype, reference points (N,Lq,L,2|4) in fp32 (fp64 for fp64 values) -> (N,Lq,M*D)."""
+    (N,Lq,M,L*P) in ``value``'s dtype (fp32, fp64, bf16 or fp16), reference points (N,Lq,L,2|4) in fp32 (fp64 for fp64 values)
+    -> (N,Lq,M*D)."""
     if not value.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     N, S, M, D = value.shape
@@ -393,13 +396,13 @@ def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offset
 
 
 def head_major_supported(value, L, P):
-    """The head-major fast path of the fused forward exists for the DETR-family shape only: bf16, L = P = 4, D in {8..32}."""
-    return (value.is_cuda and value.dtype == torch.bfloat16 and L == 4 and P == 4 and value.shape[-1] % 8 == 0
+    """The head-major fast path of the fused forward exists for the DETR-family shape only: bf16 or fp16, L = P = 4, D in {8..32}."""
+    return (value.is_cuda and value.dtype in (torch.bfloat16, torch.float16) and L == 4 and P == 4 and value.shape[-1] % 8 == 0
             and value.shape[-1] <= 32)
 
 
 def value_head_major(value, padding_mask=None):
-    """(N, S, M, D) bf16 -> (N, M, S, D) with the rows of padded pixels zeroed: ``value.masked_fill(mask[..., None], 0)``
+    """(N, S, M, D) bf16 / fp16 -> (N, M, S, D) with the rows of padded pixels zeroed: ``value.masked_fill(mask[..., None], 0)``
     and the re-layout for ``msda_forward_fused_hm`` in one pass."""
     _require_cuda_contiguous([("value", value)])
     N, S, M, D = value.shape
@@ -441,7 +444,9 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     (``alo_msda_forward_fused_hm_resident``: same products, fp32 accumulation order of the levels unchanged; the library takes
     the plain head-major kernel by itself where that one is faster — launches with less than one 16-query run per wave of the
     chip).  ``resident="always"`` takes the resident kernel wherever it can run (ALO_RESIDENT_ALWAYS), ``resident=False`` always
-    runs the plain kernel, whose output is bit-identical to ``msda_forward_fused``."""
+    runs the plain kernel, whose bf16 output is bit-identical to ``msda_forward_fused``.  fp16 values never go resident (the
+    resident kernel is bf16 only): no hint is passed and ``resident`` changes nothing; their output is within half an fp16 ulp of
+    the exact result like ``msda_forward_fused``'s, not bit-identical to it (two-term weight split, see include/alo_hotpath.h)."""
     if not value_hm.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     N, M, S, D = value_hm.shape
@@ -459,7 +464,7 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     nbytes = e * (N * S * M * D + N * Lq * M * D + N * Lq * M * L * P * 3) + 4 * reference_points.numel()
     # coarse levels resident in LDS: needs a HOST copy of the shapes (it picks the resident levels, fixes the LDS layout and sizes the
     # grid; the kernel re-checks it against the device copy).  Only a copy that is already at hand is used — no device read in a forward.
-    host = _host_spatial_shapes(spatial_shapes, read=False) if resident else None
+    host = _host_spatial_shapes(spatial_shapes, read=False) if resident and value_hm.dtype == torch.bfloat16 else None
     starts = None
     if host is not None and D == 32 and len(host) == L and sum(int(h) * int(w) for h, w in host) == S:
         starts = (ctypes.c_int32 * (2 * L))(*[int(v) for hw in host for v in hw])
@@ -494,7 +499,8 @@ def _host_spatial_shapes(spatial_shapes, read=True):
 
 def _wide_backward_wants_host_shapes(value, dims, ldt):
     """Whether a host copy of the shapes is worth a device-to-host read: the launches msda_bwd_wide_kernel can take once it has
-    one (fp32 / bf16 values, D = 32 or 64, L = P = 4, queries = the pyramid's own pixels).  The library decides the route
+    one (fp32 / bf16 values, D = 32 or 64, L = P = 4, queries = the pyramid's own pixels; never fp16, whose backward is the generic
+    kernel).  The library decides the route
     (csrc/msda.hip plan_backward) but needs the host shapes to do so, hence this pre-filter; tests/test_cabi.py holds the two together."""
     N, S, M, D, L, Lq, P = dims
     return value.dtype in (torch.float32, torch.bfloat16) and ldt == ALO_F32 and D in (32, 64) and L == 4 and P == 4 and Lq == S

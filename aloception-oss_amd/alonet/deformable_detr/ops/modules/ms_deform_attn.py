@@ -5,9 +5,11 @@ output_proj``), initialisation and ``forward`` contract as the reference module
 (alonet/deformable_detr/ops/modules/ms_deform_attn.py:34-155).  The four linear layers stay on stock PyTorch-ROCm
 (hipBLASLt); the gather is ``MSDeformAttnFunction`` -> HIP.
 
-Reduced-precision use (``module.bfloat16()``): ``value`` is produced and gathered in bf16, but sampling locations and
-attention weights are evaluated in fp32 — an 8-bit mantissa on a location in [0,1] would move samples by a third of a
-pixel on a 167-wide map.  With fp32/fp64 parameters the arithmetic is the reference's, operation for operation.
+Reduced-precision use (``module.bfloat16()``, ``module.half()``, or fp32 parameters under ``torch.autocast("cuda")`` with
+either dtype): ``value`` is produced and gathered in bf16 / fp16, but sampling locations and attention weights are evaluated
+in fp32 — an 8-bit mantissa on a location in [0,1] would move samples by a third of a pixel on a 167-wide map, an 11-bit one
+still by 0.08 px.  Gradients come back as fp16 / bf16 for ``value`` and fp32 for locations and weights.  With fp32/fp64
+parameters the arithmetic is the reference's, operation for operation.
 """
 import math
 import warnings

@@ -5,6 +5,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/alo_hotpath.h"
 
@@ -116,6 +117,39 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {  // lo in 
     return __builtin_bit_cast(unsigned, r);
 }
 
+// fp16 storage (IEEE binary16): 11 significant bits, 5-bit exponent.  Both conversions are single hardware instructions;
+// fp32 -> fp16 rounds to nearest even (v_cvt_f16_f32 / v_cvt_pk_f16_f32), never toward zero (v_cvt_pkrtz_f16_f32).
+struct f16_t {
+    uint16_t bits;
+};
+__device__ __forceinline__ float f16_to_f32(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
+__device__ __forceinline__ uint16_t f32_to_f16(float f) {
+    const _Float16 h = static_cast<_Float16>(f);
+    return __builtin_bit_cast(uint16_t, h);
+}
+__device__ __forceinline__ unsigned pack_f16x2(float lo, float hi) {  // lo in bits 0-15
+    typedef _Float16 f16x2_hw __attribute__((ext_vector_type(2)));
+    typedef float f32x2_hw __attribute__((ext_vector_type(2)));
+    const f16x2_hw r = __builtin_convertvector(f32x2_hw{lo, hi}, f16x2_hw);
+    return __builtin_bit_cast(unsigned, r);
+}
+// the two 16-bit elements of one register, widened (lo = bits 0-15), and their packed store, by storage type
+template <typename T>
+__device__ __forceinline__ void unpack2(unsigned w, float& lo, float& hi) {
+    if constexpr (std::is_same<T, f16_t>::value) {
+        lo = f16_to_f32((uint16_t)(w & 0xffffu));
+        hi = f16_to_f32((uint16_t)(w >> 16));
+    } else {
+        lo = __uint_as_float(w << 16);
+        hi = __uint_as_float(w & 0xffff0000u);
+    }
+}
+template <typename T>
+__device__ __forceinline__ unsigned pack2(float lo, float hi) {
+    if constexpr (std::is_same<T, f16_t>::value) return pack_f16x2(lo, hi);
+    else return pack_bf16x2(lo, hi);
+}
+
 // the bf16 MFMA's operand type over the four registers a 16-byte load fills
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 __device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
@@ -223,13 +257,36 @@ struct Loader<bf16_t, float, 1> {
     static __device__ __forceinline__ void widen(const raw_t& x, float (&v)[1]) { v[0] = bf16_to_f32(x); }
 };
 
+template <>
+struct Loader<f16_t, float, 8> {
+    using raw_t = u32x4;
+    static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, unsigned off) {
+        return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+    }
+    static __device__ __forceinline__ void widen(const raw_t& x, float (&v)[8]) {
+        const unsigned w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) unpack2<f16_t>(w[i], v[2 * i], v[2 * i + 1]);
+    }
+};
+template <>
+struct Loader<f16_t, float, 1> {
+    using raw_t = unsigned short;
+    static __device__ __forceinline__ raw_t load(__amdgpu_buffer_rsrc_t r, unsigned off) {
+        return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0);
+    }
+    static __device__ __forceinline__ void widen(const raw_t& x, float (&v)[1]) { v[0] = f16_to_f32(x); }
+};
+
 // Scalar global load/store with widening / narrowing (sampling locations, attention weights, outputs).
 __device__ __forceinline__ float ld(const float* p) { return *p; }
 __device__ __forceinline__ double ld(const double* p) { return *p; }
 __device__ __forceinline__ float ld(const bf16_t* p) { return bf16_to_f32(p->bits); }
+__device__ __forceinline__ float ld(const f16_t* p) { return f16_to_f32(p->bits); }
 __device__ __forceinline__ void st(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st(double* p, double v) { *p = v; }
 __device__ __forceinline__ void st(bf16_t* p, float v) { p->bits = f32_to_bf16(v); }
+__device__ __forceinline__ void st(f16_t* p, float v) { p->bits = f32_to_f16(v); }
 
 // Store VEC consecutive outputs (16-byte vector store when VEC * sizeof(T) == 16).
 template <typename T, typename CT, int VEC>
@@ -240,10 +297,10 @@ __device__ __forceinline__ void store_vec(T* p, const CT (&v)[VEC]) {
         *reinterpret_cast<double2*>(p) = double2{(double)v[0], (double)v[1]};
     } else if constexpr (sizeof(T) == 2 && VEC == 8) {
         u32x4 o;
-        o.x = pack_bf16x2(v[0], v[1]);
-        o.y = pack_bf16x2(v[2], v[3]);
-        o.z = pack_bf16x2(v[4], v[5]);
-        o.w = pack_bf16x2(v[6], v[7]);
+        o.x = pack2<T>(v[0], v[1]);
+        o.y = pack2<T>(v[2], v[3]);
+        o.z = pack2<T>(v[4], v[5]);
+        o.w = pack2<T>(v[6], v[7]);
         *reinterpret_cast<u32x4*>(p) = o;
     } else {
 #pragma unroll

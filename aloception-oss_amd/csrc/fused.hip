@@ -133,7 +133,7 @@ bias_act_kernel(const T* x, const T* __restrict__ bias, const T* res, T* y,  // 
 
 // out[n, m, s, :] = mask[n, s] ? 0 : value[n, s, m, :]   (pixel-major -> head-major, padding zeroed on the way).
 // A workgroup moves 64 pixels: reads their (M*D)-element rows with 16-byte loads (fully coalesced), writes per head 64
-// consecutive D-element rows (64*D*2 bytes contiguous).  16 B = 8 bf16 per thread.
+// consecutive D-element rows (64*D*2 bytes contiguous).  16 B = 8 bf16 per thread (fp16 values take the same kernel: bits only).
 __global__ void __launch_bounds__(kThreads)
 value_head_major_kernel(const bf16_t* __restrict__ value, const unsigned char* __restrict__ mask,
                         bf16_t* __restrict__ out, int S, int M, int D) {
@@ -384,7 +384,7 @@ extern "C" int alo_value_head_major(const void* value, const void* padding_mask,
     ALO_REQUIRE(value && out, ALO_ERR_INVALID_ARGUMENT, "alo_value_head_major: null pointer argument");
     ALO_REQUIRE(N > 0 && S > 0 && M > 0 && D > 0 && D % 8 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_value_head_major: dimensions must be positive and D a multiple of 8 (N=%d S=%d M=%d D=%d)", N, S, M, D);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_value_head_major: bf16 only (dtype %d)", dtype);
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_value_head_major: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(value, out), ALO_ERR_INVALID_ARGUMENT, "alo_value_head_major: pointers must be 16-byte aligned");
     void* args[] = {&value, &padding_mask, &out, &S, &M, &D};
     return launch<value_head_major_kernel>(dim3((S + 63) / 64, N), kThreads, 0, static_cast<hipStream_t>(stream), "alo_value_head_major", args);

@@ -124,7 +124,7 @@ __device__ __forceinline__ FwdDesc<CT> make_desc(CT x, CT y, CT a, int H, int W,
     return d;
 }
 
-// (x, y) of one sampling location / offset: one 4-byte load for bf16, one 8- / 16-byte load otherwise.
+// (x, y) of one sampling location / offset: one 4-byte load for bf16 / fp16, one 8- / 16-byte load otherwise.
 __device__ __forceinline__ void ld2(const float* p, float& x, float& y) {
     const float2 v = *reinterpret_cast<const float2*>(p);
     x = v.x; y = v.y;
@@ -136,6 +136,9 @@ __device__ __forceinline__ void ld2(const double* p, double& x, double& y) {
 __device__ __forceinline__ void ld2(const bf16_t* p, float& x, float& y) {
     const unsigned v = *reinterpret_cast<const unsigned*>(p);
     x = __uint_as_float(v << 16); y = __uint_as_float(v & 0xffff0000u);
+}
+__device__ __forceinline__ void ld2(const f16_t* p, float& x, float& y) {
+    unpack2<f16_t>(*reinterpret_cast<const unsigned*>(p), x, y);
 }
 
 // All-reduce over an aligned row of 16 lanes.  fp32: four DPP row rotations (pure VALU, no LDS round trips).
@@ -260,9 +263,9 @@ msda_fwd_kernel(const T* __restrict__ value, const int32_t* __restrict__ shapes,
                 CT xx = x[j], yy = y[j], aa = a[j];
                 if constexpr (FUSED) {
                     // softmax over the pair's 16 logits, then loc = ref + off / (W_l, H_l)  |  ref_xy + off / P * ref_wh / 2.
-                    // Storage narrower than fp32 (bf16) carries 2^-9 relative error in the logits and offsets themselves,
-                    // so the hardware exp and reciprocal multiplies (<= 2 ulp) are used there; fp32 / fp64 keep the exact
-                    // library exp and true divisions of the unfused path.
+                    // Storage narrower than fp32 carries 2^-9 (bf16) / 2^-12 (fp16) relative error in the logits and offsets
+                    // themselves, so the hardware exp and reciprocal multiplies (<= 2 ulp of fp32) are used there; fp32 / fp64
+                    // keep the exact library exp and true divisions of the unfused path.
                     constexpr bool kFast = sizeof(T) < 4;
                     const CT mx = row16_max(aa);
                     if constexpr (kFast) aa = __expf(aa - mx); else aa = exp(aa - mx);
@@ -400,11 +403,28 @@ msda_fwd_kernel(const T* __restrict__ value, const int32_t* __restrict__ shapes,
 //              term each (row 3 is zero).  Every product bf16 x bf16 is exact in fp32, so D[0] + D[1] + D[2] is the
 //              fp32 weighted sum up to the order of the additions.
 // Per sampling point a lane then issues 4 row loads, 16 v_perm and 8 MFMA instead of 32 widen + 16 v_pk_fma.
+//
+// fp16 values take the same frame on v_mfma_f32_4x4x4_16B_f16 (the kernel's element type is a template parameter) where it is faster
+// than the generic kernel: on a head-major value (plan_forward has the measurement).  What differs is
+// the split of the weights: fp16 has 11 significant bits but a 5-bit exponent, so a weight is split into TWO terms hi + lo (22 bits,
+// rows 0 and 1; rows 2 and 3 are zero) after a power-of-two pre-scale chosen PER (query, head) PAIR from the largest of its corner
+// weights that meet a value (corners that are READ; lean_sample leaves finite weights on the others, which are zeroed here so that they
+// neither steer the scale nor overflow under it), which lands in [2^13, 2^14).  The guarantee: nothing overflows whatever the
+// attention weights are (softmax outputs or a caller's arbitrary floats); a weight within 2^-15 of the pair's largest read weight keeps
+// all 22 bits (lo's last bit is still on fp16's subnormal grid, 2^-24); a smaller one is off by at most 2^-25 on the scaled axis, i.e.
+// 2^-38 of the largest read weight, as the kernel runs (fp16 denormals on), and by at most 2^-14, i.e. 2^-27 of it, were subnormal
+// terms flushed — an absolute error per term of 2^-38 (2^-27) wmax |v|, below fp32 noise unless the output cancels to near zero among
+// values in the thousands.  fp16 x fp16 is exact in fp32 and the scale is undone exactly on the accumulator, so the result is the
+// fp32 weighted sum up to 2^-22 relative per weight and the order of the additions: close to the generic kernel's output, NOT
+// bit-identical to it (bf16's three-term split is).  A non-finite value makes its outputs non-finite as everywhere else, but an
+// infinite one may come out as NaN where the generic kernel gives +-inf (hi * inf + lo * inf with lo <= 0).  The value rows go to the
+// matrix pipe as they are: fp16 subnormal VALUES count as long as the kernel runs with fp16 denormals enabled, the compiler's default.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 struct alignas(16) MfmaDesc {
     unsigned off[4];      // corner byte offsets (kOutOfRange = not read)
-    unsigned arow[4][2];  // A rows: {hi, mid, lo, 0} x 4 corners, bf16 pairs packed low-half-first
+    unsigned arow[4][2];  // A rows: {hi, mid, lo, 0} (bf16) / {hi, lo, 0, 0} (fp16) x 4 corners, pairs packed low-half-first
 };
 constexpr int kMfmaPairStride = 16 * (int)sizeof(MfmaDesc) + 16;
 
@@ -470,21 +490,19 @@ __device__ __forceinline__ void lean_sample(float x, float y, float a, bool aliv
 }
 
 // MSDeformAttn's arithmetic between its linear layers and the op (ms_deform_attn.py:119-133) for the 4 points of ONE level of a
-// (query, head) pair, bf16 storage: lane q of a quad holds level q.  `lr` = the 4 raw (x, y) offsets, `ar` = the 4 raw logits,
+// (query, head) pair, 16-bit storage T (bf16 / fp16): lane q of a quad holds level q.  `lr` = the 4 raw (x, y) offsets, `ar` = the 4 raw logits,
 // r0..r3 = the reference point (r2, r3 used when ref_dim == 4).  Softmax over the pair's 16 logits (4 here, 12 in the other
-// lanes of the quad); bf16 inputs carry 2^-9 relative error themselves, so the hardware exp / reciprocal (<= 2 ulp) are used.
-// Shared by every wave kernel so that they agree bit for bit.
+// lanes of the quad); bf16 / fp16 inputs carry 2^-9 / 2^-12 relative error themselves, so the hardware exp / reciprocal (<= 2 ulp of
+// fp32) are used.  Shared by every wave kernel so that they agree bit for bit.
+template <typename T = bf16_t>
 __device__ __forceinline__ void wave_prologue(const u32x4 lr, const u32x2 ar, float r0, float r1, float r2, float r3, int ref_dim,
                                               float inv_w, float inv_h, int P, float (&x)[4], float (&y)[4], float (&a)[4]) {
 #pragma clang fp contract(off)
     const unsigned lw[4] = {lr.x, lr.y, lr.z, lr.w};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[i] = __uint_as_float(lw[i] << 16);
-        y[i] = __uint_as_float(lw[i] & 0xffff0000u);
-    }
-    a[0] = __uint_as_float(ar.x << 16); a[1] = __uint_as_float(ar.x & 0xffff0000u);
-    a[2] = __uint_as_float(ar.y << 16); a[3] = __uint_as_float(ar.y & 0xffff0000u);
+    for (int i = 0; i < 4; ++i) unpack2<T>(lw[i], x[i], y[i]);
+    unpack2<T>(ar.x, a[0], a[1]);
+    unpack2<T>(ar.y, a[2], a[3]);
     const float mx = quad_max(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])));
 #pragma unroll
     for (int i = 0; i < 4; ++i) a[i] = __expf(a[i] - mx);
@@ -526,26 +544,52 @@ __device__ __forceinline__ void split_weights(const float (&w)[4], u32x2 (&rows)
     rows[2] = u32x2{__builtin_amdgcn_perm(r2b[1], r2b[0], 0x07060302u), __builtin_amdgcn_perm(r2b[3], r2b[2], 0x07060302u)};
 }
 
+// fp16: the power-of-two scale that puts the largest corner weight of a pair that meets a value into [2^13, 2^14), and its inverse.  `wmax` >= 0 is the
+// largest |weight| (NaN weights do not take part, an infinite one gives the smallest scale); exponents are clamped so that both
+// factors are normal fp32 numbers whatever the weights are (all-zero weights included).
+__device__ __forceinline__ void weight_scale(float wmax, float& scale, float& inv) {
+    const unsigned e = max((__float_as_uint(wmax) >> 23) & 0xffu, 27u);
+    scale = __uint_as_float((267u - e) << 23);   // 2^(13 - (e - 127))
+    inv = __uint_as_float((e - 13u) << 23);
+}
+// The four scaled fp32 corner weights of a sample as the two A rows {hi, lo}: hi = fp16(w), lo = fp16(w - hi), both rounded to
+// nearest; w - hi is exact in fp32, so hi + lo carries 22 significant bits of w.
+__device__ __forceinline__ void split_weights_f16(const float (&w)[4], float scale, u32x2 (&rows)[2]) {
+#pragma clang fp contract(off)
+    float ws[4], r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ws[k] = w[k] * scale;
+    rows[0] = u32x2{pack_f16x2(ws[0], ws[1]), pack_f16x2(ws[2], ws[3])};
+    float h[4];
+    unpack2<f16_t>(rows[0].x, h[0], h[1]);
+    unpack2<f16_t>(rows[0].y, h[2], h[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = ws[k] - h[k];
+    rows[1] = u32x2{pack_f16x2(r[0], r[1]), pack_f16x2(r[2], r[3])};
+}
+
 // One WAVE is the unit of work (64-thread workgroups, no block barrier anywhere): its 16 quads serve 16 consecutive
 // (query, head) pairs.  In stage 1 lane q of a quad turns the pair's 4 sampling points of level q into descriptors — its
 // inputs are one 16-byte (offsets), one 8-byte (logits) and one 8/16-byte (reference point) load instead of 16 narrow
 // ones, which matters because the texture path charges per instruction — and parks them in the wave's own LDS slice; in
 // stage 2 the same quad gathers the pair's 64 corner rows.  Waves drift apart freely, so the VALU work of one wave's
 // stage 1 overlaps the gathers of the others.  L = P = 4 and D <= 32 (the DETR-family configuration) only.
+// T = bf16_t or f16_t (the kernel keeps the name it had when bf16 was its only element type).
 constexpr int kWaveLds = 16 * kMfmaPairStride;
 
 // HM = true: `value` is HEAD-major, (N, M, S, D) — what alo_value_head_major writes — and a wave serves 16 CONSECUTIVE
 // QUERIES of ONE head instead of 2 queries x 8 heads.  A head's row is D*2 = 64 bytes, half an L1 line: in the
 // pixel-major layout every request of a wave instruction lands in its own line (16 line reads), in the head-major one
 // neighbouring queries read neighbouring pixels of the same head, i.e. the same or the adjacent line.
-template <int SB, bool FUSED, bool HM>
+template <typename T, int SB, bool FUSED, bool HM>
 __global__ void __launch_bounds__(64)
-msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __restrict__ shapes,
+msda_fwd_bf16_mfma_kernel(const T* __restrict__ value, const int32_t* __restrict__ shapes,
                           const int32_t* __restrict__ lstart, const void* __restrict__ loc_,
-                          const void* __restrict__ attn_, const float* __restrict__ ref, bf16_t* __restrict__ out,
+                          const void* __restrict__ attn_, const float* __restrict__ ref, T* __restrict__ out,
                           const Dims dm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using Ld = Loader<bf16_t, float, 8>;
+    using Ld = Loader<T, float, 8>;
+    constexpr bool kF16 = std::is_same<T, f16_t>::value;
 
     const unsigned lb = xcd_contiguous_block(blockIdx.x, dm.nblocks);
     const int b = lb / dm.blocks_per_batch;
@@ -587,14 +631,15 @@ msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __res
         const long g0 = (batch_pair0 + pair) * 16 + 4 * lane;
 
         // ---- stage 1: the 4 points of level `lane` of this quad's pair ------------------------------------------------
+        float unscale = 1.f;   // fp16: the inverse of the pair's weight scale (the same in the four lanes of the quad)
         {
             float x[4], y[4], a[4];
             if constexpr (FUSED) {
                 // offsets / logits rows may be slices of one wider buffer (a merged projection): row strides are arguments
                 const int q = dm.m_shift >= 0 ? (pair >> dm.m_shift) : pair / dm.M;
                 const long qrow = (long)b * Lq + q;
-                const u32x4 lr = *reinterpret_cast<const u32x4*>(static_cast<const bf16_t*>(loc_) + qrow * dm.loc_row_elems + 32 * m + 8 * lane);
-                const u32x2 ar = *reinterpret_cast<const u32x2*>(static_cast<const bf16_t*>(attn_) + qrow * dm.attn_row_elems + 16 * m + 4 * lane);
+                const u32x4 lr = *reinterpret_cast<const u32x4*>(static_cast<const T*>(loc_) + qrow * dm.loc_row_elems + 32 * m + 8 * lane);
+                const u32x2 ar = *reinterpret_cast<const u32x2*>(static_cast<const T*>(attn_) + qrow * dm.attn_row_elems + 16 * m + 4 * lane);
                 const float* rp = ref + (((long)b * Lq + q) * dm.L + lane) * dm.ref_dim;
                 float r0, r1, r2 = 0.f, r3 = 0.f;
                 if (dm.ref_dim == 2) {
@@ -604,7 +649,7 @@ msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __res
                     const float4 rv = *reinterpret_cast<const float4*>(rp);
                     r0 = rv.x; r1 = rv.y; r2 = rv.z; r3 = rv.w;
                 }
-                wave_prologue(lr, ar, r0, r1, r2, r3, dm.ref_dim, inv_w, inv_h, dm.P, x, y, a);
+                wave_prologue<T>(lr, ar, r0, r1, r2, r3, dm.ref_dim, inv_w, inv_h, dm.P, x, y, a);
             } else {
                 const float* lp = static_cast<const float*>(loc_) + 2 * g0;
                 const f32x4 l0 = *reinterpret_cast<const f32x4*>(lp), l1 = *reinterpret_cast<const f32x4*>(lp + 4);
@@ -614,6 +659,34 @@ msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __res
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a[i] = av[i];
             }
+            if constexpr (kF16) {
+                // all four samples first: the pre-scale comes from the largest of the pair's weights on corners that are read (16 candidates
+                // here, 48 in the other lanes); weights of corners that are not read are zeroed, scaled they could leave fp16's range
+                MfmaDesc d[4];
+                float w4[4][4];
+                float wmax = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    lean_sample(x[i], y[i], a[i], !dead, Hf, Wf, Wf, 1.0f, base0, row_bytes, row_bytes, w_bytes, kOutOfRange, d[i].off, w4[i]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        w4[i][k] = d[i].off[k] != kOutOfRange ? w4[i][k] : 0.f;
+                        wmax = fmaxf(wmax, fabsf(w4[i][k]));
+                    }
+                }
+                float scale;
+                weight_scale(quad_max(wmax), scale, unscale);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    u32x2 rows[2];
+                    split_weights_f16(w4[i], scale, rows);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) { d[i].arow[t][0] = rows[t].x; d[i].arow[t][1] = rows[t].y; }
+#pragma unroll
+                    for (int t = 2; t < 4; ++t) { d[i].arow[t][0] = 0u; d[i].arow[t][1] = 0u; }
+                    *reinterpret_cast<MfmaDesc*>(dp + (4 * lane + i) * (int)sizeof(MfmaDesc)) = d[i];
+                }
+            } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 MfmaDesc d;
@@ -626,6 +699,7 @@ msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __res
                 d.arow[3][0] = 0u;
                 d.arow[3][1] = 0u;
                 *reinterpret_cast<MfmaDesc*>(dp + (4 * lane + i) * (int)sizeof(MfmaDesc)) = d;
+            }
             }
         }
         // descriptors are exchanged inside the wave only: LDS operations of one wave execute in order, the fence keeps the
@@ -662,16 +736,24 @@ msda_fwd_bf16_mfma_kernel(const bf16_t* __restrict__ value, const int32_t* __res
                                                       __builtin_amdgcn_perm(t3, t2, 0x05040100u));
                         const s16x4 b_odd = as_s16x4(__builtin_amdgcn_perm(t1, t0, 0x07060302u),
                                                      __builtin_amdgcn_perm(t3, t2, 0x07060302u));
-                        acc[2 * q] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(arow[j], b_even, acc[2 * q], 0, 0, 0);
-                        acc[2 * q + 1] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(arow[j], b_odd, acc[2 * q + 1], 0, 0, 0);
+                        if constexpr (kF16) {
+                            acc[2 * q] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(f16x4, arow[j]), __builtin_bit_cast(f16x4, b_even), acc[2 * q], 0, 0, 0);
+                            acc[2 * q + 1] = __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(f16x4, arow[j]), __builtin_bit_cast(f16x4, b_odd), acc[2 * q + 1], 0, 0, 0);
+                        } else {
+                            acc[2 * q] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(arow[j], b_even, acc[2 * q], 0, 0, 0);
+                            acc[2 * q + 1] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(arow[j], b_odd, acc[2 * q + 1], 0, 0, 0);
+                        }
                     }
                 }
             }
             if (!dead && c0 < dm.D) {
                 float o[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) o[i] = (acc[i][0] + acc[i][1]) + acc[i][2];
-                store_vec<bf16_t, float, 8>(out + (batch_pair0 + pair) * dm.D + c0, o);
+                for (int i = 0; i < 8; ++i) {
+                    if constexpr (kF16) o[i] = (acc[i][0] + acc[i][1]) * unscale;   // rows hi + lo, scale undone exactly
+                    else o[i] = (acc[i][0] + acc[i][1]) + acc[i][2];
+                }
+                store_vec<T, float, 8>(out + (batch_pair0 + pair) * dm.D + c0, o);
             }
         }
         ALO_WAVE_LDS_ORDER();
@@ -1655,7 +1737,8 @@ int validate(const Shape& s, int ldt) {
     ALO_REQUIRE(N > 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq > 0 && P > 0, ALO_ERR_INVALID_ARGUMENT,
                 "msda: dimensions must be positive (N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d)", N, S, M, D, L, Lq, P);
     ALO_REQUIRE(L <= kMaxLevels, ALO_ERR_UNSUPPORTED, "msda: at most %d levels are supported, got %d", kMaxLevels, L);
-    ALO_REQUIRE((vdt == ALO_F32 && ldt == ALO_F32) || (vdt == ALO_F64 && ldt == ALO_F64) || (vdt == ALO_BF16 && ldt == ALO_F32),
+    ALO_REQUIRE((vdt == ALO_F32 && ldt == ALO_F32) || (vdt == ALO_F64 && ldt == ALO_F64) || (vdt == ALO_BF16 && ldt == ALO_F32) ||
+                    (vdt == ALO_F16 && ldt == ALO_F32),
                 ALO_ERR_UNSUPPORTED, "msda: unsupported dtype pair (value=%d, loc=%d)", vdt, ldt);
     ALO_REQUIRE((double)S * M * D * s.elem() < 3.0 * 1024 * 1024 * 1024, ALO_ERR_UNSUPPORTED,
                 "msda: one batch item of value must stay below 3 GiB");
@@ -1718,7 +1801,8 @@ struct FwdArgs {
 };
 
 // Forward routes.  NONE: head-major asked for a launch the wave kernel does not take; GENERIC: the msda_fwd_kernel that `plan` names;
-// WAVE / WAVE_HM: msda_fwd_bf16_mfma_kernel on a pixel-major / head-major value; RESIDENT: msda_fwd_bf16_resident_kernel, with `rd`.
+// WAVE / WAVE_HM: msda_fwd_bf16_mfma_kernel on a pixel-major (bf16) / head-major (bf16, fp16) value; RESIDENT:
+// msda_fwd_bf16_resident_kernel (bf16 only: fp16 takes WAVE_HM under either policy), with `rd`.
 enum FwdRoute { FWD_NONE, FWD_GENERIC, FWD_WAVE, FWD_WAVE_HM, FWD_RESIDENT };
 
 // What a plan hands to the launch: the route and the dims of the kernel it names.
@@ -1736,8 +1820,10 @@ LaunchPlan plan_forward(const Shape& s, const FwdArgs& a) {
     const auto [N, S, M, D, L, Lq, P, vdt] = s;
     LaunchPlan fp;
     fp.plan = make_plan(D, L, P, s.elem(), a.aligned);
-    // bf16 rows go to the matrix pipe untouched, one wave per 16 pairs (see msda_fwd_bf16_mfma_kernel)
-    const bool wave = vdt == ALO_BF16 && a.aligned && a.in_aligned && L == 4 && P == 4 && D % 8 == 0 && D <= 32 &&
+    // bf16 rows go to the matrix pipe untouched, one wave per 16 pairs (see msda_fwd_bf16_mfma_kernel); fp16 rows only when they are
+    // head-major: pixel-major, the fp16 wave kernel measured level with the generic one (encoder launch, N = 8: 0.255 against 0.255 ms
+    // on the ring, 0.304 against 0.303 trained-like), head-major it is 16 % / 24 % ahead of it (docs/experiments.md)
+    const bool wave = (vdt == ALO_BF16 || (vdt == ALO_F16 && a.head_major)) && a.aligned && a.in_aligned && L == 4 && P == 4 && D % 8 == 0 && D <= 32 &&
                       (size_t)M * D * 2 < (1u << 23) && S < (1 << 23);
     fp.route = a.head_major ? (wave && a.fused ? FWD_WAVE_HM : FWD_NONE) : (wave ? FWD_WAVE : FWD_GENERIC);
     Dims& dm = fp.dm;
@@ -1753,7 +1839,7 @@ LaunchPlan plan_forward(const Shape& s, const FwdArgs& a) {
     dm.nblocks = (unsigned)(dm.blocks_per_batch * N);
     const bool offs32 = (double)Lq * dm.loc_row_elems < 4.0e9 && (double)Lq * dm.attn_row_elems < 4.0e9 &&
                         (double)Lq * M * 32 < 4.0e9 && (double)Lq * 4 * a.ref_dim < 4.0e9;   // 32-bit element offsets per image
-    if (a.host_shapes && D == 32 && offs32 && resident_plan(a.host_shapes, s, a.resident_policy, &fp.rd)) {
+    if (vdt == ALO_BF16 && a.host_shapes && D == 32 && offs32 && resident_plan(a.host_shapes, s, a.resident_policy, &fp.rd)) {
         // coarse levels resident in LDS: one 12-wave workgroup per CU pinned to an (image, head) slab
         fp.route = FWD_RESIDENT;
         dm.nblocks = (unsigned)((long)N * M * fp.rd.wps);
@@ -1776,20 +1862,23 @@ int forward_impl(const void* value, const int32_t* spatial_shapes, const int32_t
     switch ((FwdRoute)lp.route) {
     case FWD_NONE:
         return fail(ALO_ERR_UNSUPPORTED,
-                    "alo_msda_forward_fused_hm: needs bf16, L = P = 4, D %% 8 == 0, D <= 32 and 16-byte aligned pointers");
+                    "alo_msda_forward_fused_hm: needs bf16 / fp16, L = P = 4, D %% 8 == 0, D <= 32 and 16-byte aligned pointers");
     case FWD_RESIDENT:
         return launch<msda_fwd_bf16_resident_kernel>(nblocks, kResThreads, (size_t)lp.rd.image_bytes + kResFixed + kResWaves * kResWaveLds,
                                                      stream, "alo_msda_forward_fused_hm_resident", args);
     case FWD_WAVE_HM:
-        return launch<msda_fwd_bf16_mfma_kernel<4, true, true>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused_hm", args);
+        if (s.value_dtype == ALO_F16)
+            return launch<msda_fwd_bf16_mfma_kernel<f16_t, 4, true, true>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused_hm", args);
+        return launch<msda_fwd_bf16_mfma_kernel<bf16_t, 4, true, true>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused_hm", args);
     case FWD_WAVE:
-        if (fused) return launch<msda_fwd_bf16_mfma_kernel<4, true, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused", args);
-        return launch<msda_fwd_bf16_mfma_kernel<4, false, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward", args);
+        if (fused) return launch<msda_fwd_bf16_mfma_kernel<bf16_t, 4, true, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward_fused", args);
+        return launch<msda_fwd_bf16_mfma_kernel<bf16_t, 4, false, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward", args);
     case FWD_GENERIC:;
     }
     if (s.value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_FWD_CASE, float, float, float, 4) }
     if (s.value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_FWD_CASE, double, double, double, 2) }
     if (s.value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_FWD_CASE, bf16_t, float, float, 8) }
+    if (s.value_dtype == ALO_F16) { ALO_ALL_CASES(ALO_FWD_CASE, f16_t, float, float, 8) }
     return fail(ALO_ERR_UNSUPPORTED, "alo_msda_forward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
 }
 
@@ -1955,6 +2044,7 @@ extern "C" int alo_msda_backward_hinted(const void* value, const int32_t* spatia
     if (value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_BWD_CASE, float, float, float, 4) }
     if (value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_BWD_CASE, double, double, double, 2) }
     if (value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_BWD_CASE, bf16_t, float, float, 8) }
+    if (value_dtype == ALO_F16) { ALO_ALL_CASES(ALO_BWD_CASE, f16_t, float, float, 8) }
     return fail(ALO_ERR_UNSUPPORTED, "alo_msda_backward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
 }
 

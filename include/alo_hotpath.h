@@ -45,11 +45,13 @@ typedef enum alo_status {
 } alo_status_t;
 
 /* Element types.  For MSDA the reference dispatches float and double (AT_DISPATCH_FLOATING_TYPES,
- * ms_deform_attn_cuda.cu:64,134); bf16 storage with fp32 arithmetic is this library's addition. */
+ * ms_deform_attn_cuda.cu:64,134); bf16 and fp16 storage with fp32 arithmetic are this library's addition.  ALO_F16 (IEEE binary16) is
+ * accepted by the MSDA entry points and alo_value_head_major only; every other entry point that takes a dtype refuses it. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
     ALO_F64 = 1,
-    ALO_BF16 = 2
+    ALO_BF16 = 2,
+    ALO_F16 = 3
 } alo_dtype_t;
 
 /* ABI version of the loaded library (== ALO_HOTPATH_ABI_VERSION it was built with). */
@@ -73,8 +75,11 @@ const char* alo_last_error(void);
  *   attn_weight         (N, Lq, M, L, P)    loc_dtype
  *   out                 (N, Lq, M*D)        value_dtype          m-major, c-minor
  *
- * dtype pairs (value_dtype, loc_dtype): (F32,F32) (F64,F64) (BF16,F32).  Arithmetic is fp64 for F64 and fp32
- * otherwise (bf16 locations would cost a third of a pixel on a 167-wide map, so they are not offered).  Any D >= 1 is accepted; D % (16 / sizeof(value element)) == 0 with 16-byte aligned `value`/`out`
+ * dtype pairs (value_dtype, loc_dtype): (F32,F32) (F64,F64) (BF16,F32) (F16,F32).  Arithmetic is fp64 for F64 and fp32
+ * otherwise (bf16 locations would cost a third of a pixel on a 167-wide map and fp16 ones 0.08 px, so neither is offered); `out` is
+ * rounded to nearest even.  bf16 values with L = P = 4, D % 8 == 0, D <= 32 and 16-byte aligned pointers take the matrix-pipe
+ * kernel (csrc/msda.hip: msda_fwd_bf16_mfma_kernel), which gives the bits of the generic kernel; fp16 values take the generic kernel
+ * here and in alo_msda_forward_fused, the matrix-pipe kernel in alo_msda_forward_fused_hm.  Any D >= 1 is accepted; D % (16 / sizeof(value element)) == 0 with 16-byte aligned `value`/`out`
  * takes the vectorised path.  L <= 32.  N*S*M*D*sizeof(element) per batch item must stay below 3 GiB.
  * The reference's `im2col_step` is a scheduling hint with no effect on results and has no counterpart here.
  */
@@ -92,7 +97,7 @@ int alo_msda_forward(const void* value, const int32_t* spatial_shapes, const int
  *                  = ref[b,q,l,0:2] + sampling_offsets[b,q,m,l,p,:] / P * ref[b,q,l,2:4] * 0.5          (ref_dim == 4)
  *   out            = alo_msda_forward(value, ..., loc, attn)
  *
- *   sampling_offsets    (N, Lq, M, L, P, 2)   value_dtype      raw output of the sampling_offsets linear layer
+ *   sampling_offsets    (N, Lq, M, L, P, 2)   value_dtype      raw output of the sampling_offsets linear layer (fp16 for F16 values)
  *   attn_logits         (N, Lq, M, L*P)       value_dtype      raw output of the attention_weights linear layer
  *   reference_points    (N, Lq, L, ref_dim)   F64 when value_dtype is F64, F32 otherwise
  *
@@ -107,7 +112,14 @@ int alo_msda_forward_fused(const void* value, const int32_t* spatial_shapes, con
 /*
  * Head-major variant of alo_msda_forward_fused (extension).  `value_hm` is (N, M, S, D): what alo_value_head_major
  * writes from the boundary layout.  Everything else as above; results are bit-identical to alo_msda_forward_fused on
- * the same data.  bf16, L = P = 4, D % 8 == 0, D <= 32 only (ALO_ERR_UNSUPPORTED otherwise).  Why it exists: a head's
+ * the same data — for bf16.  bf16 or fp16, L = P = 4, D % 8 == 0, D <= 32 only (ALO_ERR_UNSUPPORTED otherwise).  fp16: the corner
+ * weights go to the matrix pipe as two fp16 terms (22 significant bits, after a power-of-two scale per (query, head) pair) where
+ * bf16 uses an exact three-term split, and alo_msda_forward_fused runs fp16 on the generic kernel, so fp16 results are NOT
+ * bit-identical to alo_msda_forward_fused: before the final rounding they differ from it by up to 2^-22 relative per weight and the
+ * order of the additions, far below half an fp16 ulp (both are held to half an fp16 ulp + 1e-6 of the float64 result).  The scale comes
+ * from the pair's largest weight on a corner that is read; a weight more than 2^15 below it is exact to 2^-38 of that largest weight in
+ * absolute terms rather than to 22 bits of its own.  A non-finite value reaches the same outputs as in the other kernels, but an infinite
+ * one may arrive as NaN where they give +-inf.  Why it exists: a head's
  * row is 64 bytes = half an L1 line; head-major rows of neighbouring pixels share lines, pixel-major ones never do.
  */
 int alo_msda_forward_fused_hm(const void* value_hm, const int32_t* spatial_shapes, const int32_t* level_start_index,
@@ -135,10 +147,12 @@ int alo_msda_forward_fused_hm_rows(const void* value_hm, const int32_t* spatial_
  * per wave of the chip (N * M * ceil(Lq / 16) >= CUs * 12; measured 0.77-0.86 of the plain kernel's time above that, 1.2-1.6 x
  * below) — and the plain head-major kernel otherwise (small frames, the decoder's 300 queries): callers may use it unconditionally.
  * ALO_RESIDENT_ALWAYS takes the resident kernel wherever it can run (tests; callers that know better).  Results are bit-identical
- * to alo_msda_forward_fused_hm either way (same products, same order of the sum).
+ * to alo_msda_forward_fused_hm either way (same products, same order of the sum).  The resident kernel is bf16 only: with ALO_F16
+ * this entry point is alo_msda_forward_fused_hm_rows under either policy.
  * alo_msda_resident_levels reports what a launch of these dimensions would do under `policy`: 2 (levels 2-3 resident) or 0 (plain),
  * from the plan the launch itself follows.  Its signature has no D, P, dtype, row strides or pointers: it answers for bf16, D = 32,
- * P = 4, dense rows and 16-byte aligned pointers (any other launch is plain or refused), and 0 for dimensions the library refuses.
+ * P = 4, dense rows and 16-byte aligned pointers (any other launch — an fp16 one included — is plain or refused), and 0 for
+ * dimensions the library refuses.
  */
 #define ALO_RESIDENT_AUTO 0
 #define ALO_RESIDENT_ALWAYS 1
@@ -152,7 +166,7 @@ int alo_msda_resident_levels(const int32_t* host_spatial_shapes, int N, int S, i
 /*
  * value (N, S, M, D) -> out (N, M, S, D), rows of padded pixels zeroed (padding_mask (N, S) uint8/bool, nullable):
  * MSDeformAttn's `value.masked_fill(input_padding_mask[..., None], 0)` (ms_deform_attn.py:112-113) and the re-layout
- * in one pass.  bf16, D % 8 == 0.
+ * in one pass.  bf16 or fp16 (a 16-bit re-layout: no arithmetic), D % 8 == 0.
  */
 int alo_value_head_major(const void* value, const void* padding_mask, void* out, int N, int S, int M, int D,
                          int dtype, void* stream);
@@ -165,8 +179,8 @@ int alo_value_head_major(const void* value, const void* padding_mask, void* out,
  *   grad_sampling_loc   (N, Lq, M, L, P, 2) grad dtype           fully written (0 for skipped samples)
  *   grad_attn_weight    (N, Lq, M, L, P)    grad dtype
  *
- * grad dtype is F64 when value_dtype is F64 and F32 otherwise (bf16 storage accumulates its gradients in fp32; the
- * caller narrows afterwards).  Supported (value_dtype, loc_dtype): (F32,F32) (F64,F64) (BF16,F32).
+ * grad dtype is F64 when value_dtype is F64 and F32 otherwise (bf16 / fp16 storage accumulates its gradients in fp32; the
+ * caller narrows afterwards).  Supported (value_dtype, loc_dtype): (F32,F32) (F64,F64) (BF16,F32) (F16,F32).
  * grad_value is accumulated with hardware floating-point atomics, so — exactly like the reference — its low-order
  * bits depend on scheduling.
  */
@@ -194,7 +208,8 @@ int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, c
  * Which kernel alo_msda_backward_hinted takes for a launch of these dimensions (pointers assumed 16-byte aligned), without
  * enqueuing anything: ALO_MSDA_BWD_WIDE (16x16 query blocks sorted on chip, one atomic row per touched pixel per block: fp32 / bf16
  * values, D = 32 or 64, L = P = 4, Lq == S and a host copy of the shapes), ALO_MSDA_BWD_TILED (4x4 query tiles on the fp32 matrix cores:
- * fp32, D = 32, L = P = 4), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else); -1 for a launch the library refuses
+ * fp32, D = 32, L = P = 4), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else, every fp16 launch included); -1 for a
+ * launch the library refuses
  * (dtype pair, dimensions, sizes: alo_last_error says which).  The launch and this query read one plan, so they cannot disagree.
  */
 #define ALO_MSDA_BWD_GENERIC 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel-level micro-benchmarks of the hot path at BASELINE.json sizes (HIP events on the launch stream).
 
-    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup,alt_corr_lookup] [--reps 20] [--dtype f32|bf16]
+    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup,alt_corr_lookup] [--reps 20] [--dtype f32|bf16|f16]
 
 Prints one JSON object per kernel: average launch time, algorithmic bytes / flops (SURVEY.md section 8d formulas),
 achieved GB/s or TFLOP/s.  Tuning knobs are environment variables of the library (ALO_MSDA_FWD_WAVES, ALO_MSDA_ITERS).
@@ -211,6 +211,38 @@ def bench_msda_fused_hm(N, reps, resident=True, kind="ring"):
                  GBps=nbytes / t / 1e9)]
 
 
+def bench_msda_f16_ab(N, reps, rounds=5):
+    """The fp16 matrix-pipe forward (head-major) against the fp16 generic kernel (pixel-major) on the encoder launch, ring and
+    trained-like, in ONE run with the variants alternating (``rounds`` rounds of ``reps`` launches each; min / median / max over
+    the rounds), next to the two bf16 matrix-pipe launches.  "layer" rows add what each route costs MSDeformAttn around the
+    kernel: the padding mask as an in-place ``masked_fill_`` before the generic kernel, as part of the head-major re-layout
+    (``value_head_major``) before the other."""
+    out = []
+    for kind in ("ring", "trained"):
+        runs = {}
+        for name, dtype in (("f16", torch.float16), ("bf16", torch.bfloat16)):
+            value, shapes, start, offsets, logits, ref = fused_inputs(N, dtype, kind=kind)
+            S = value.shape[1]
+            mask = torch.zeros(N, S, dtype=torch.bool, device=DEV)
+            vhm = alo_hip.value_head_major(value, mask)
+            pm = lambda v=value, o=offsets, lg=logits, r=ref: alo_hip.msda_forward_fused(v, shapes, start, o, lg, r)  # noqa: E731
+            hm = lambda v=vhm, o=offsets, lg=logits, r=ref: alo_hip.msda_forward_fused_hm(v, shapes, start, o, lg, r, resident=False)  # noqa: E731
+            runs[f"{name} {'generic' if dtype == torch.float16 else 'wave'} pixel-major"] = pm
+            runs[f"{name} wave head-major"] = hm
+            if dtype == torch.float16:
+                runs["f16 layer: masked_fill_ + generic"] = lambda v=value, m=mask, f=pm: (v.masked_fill_(m[..., None, None], 0.0), f())
+                runs["f16 layer: value_head_major + wave"] = lambda v=value, m=mask, o=offsets, lg=logits, r=ref: alo_hip.msda_forward_fused_hm(
+                    alo_hip.value_head_major(v, m), shapes, start, o, lg, r, resident=False)
+        times = {k: [] for k in runs}
+        for _ in range(rounds):
+            for k, fn in runs.items():
+                times[k].append(time_launches(fn, reps) * 1e3)
+        for k, ts in times.items():
+            ts = sorted(ts)
+            out.append(dict(kernel=f"msda_fwd_fused[{kind}] {k}", N=N, Lq=S, ms_min=ts[0], ms_median=ts[len(ts) // 2], ms_max=ts[-1]))
+    return out
+
+
 def bench_msda_bwd(N, Lq, kind, dtype, reps):
     value, shapes, start, loc, attn = msda_inputs(N, Lq, kind, dtype)
     go = torch.randn(N, Lq, 256, device=DEV).to(dtype)
@@ -336,7 +368,7 @@ def main():
     ap.add_argument("--N", type=int, default=8)
     ap.add_argument("--B", type=int, default=4)
     a = ap.parse_args()
-    dts = [dict(f32=torch.float32, bf16=torch.bfloat16, f64=torch.float64)[d] for d in a.dtype.split(",")]
+    dts = [dict(f32=torch.float32, bf16=torch.bfloat16, f64=torch.float64, f16=torch.float16)[d] for d in a.dtype.split(",")]
     S = sum(h * w for h, w in DETR_SHAPES)
     tags = {k: os.environ[k] for k in os.environ if k.startswith("ALO_")}
     for w in a.which.split(","):
@@ -352,6 +384,8 @@ def main():
         elif w in ("msda_fused_hm_survey", "msda_fused_hm_uniform", "msda_fused_hm_trained"):   # the headline kernel away from the init-time ring
             kind = w.rsplit("_", 1)[1]
             res = bench_msda_fused_hm(a.N, a.reps, kind=kind)[1:] + bench_msda_fused_hm(a.N, a.reps, resident=False, kind=kind)[1:]
+        elif w == "msda_f16_ab":   # fp16: head-major matrix-pipe kernel against the generic one, alternating, with bf16 alongside
+            res = bench_msda_f16_ab(a.N, a.reps)
         elif w == "msda_rand":
             res = [bench_msda_fwd(a.N, S, "uniform", dt, a.reps) for dt in dts]
         elif w == "msda_dec":
