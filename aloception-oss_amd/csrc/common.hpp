@@ -69,10 +69,17 @@ __device__ __forceinline__ unsigned xcd_contiguous_block(unsigned bid, unsigned 
     return start + k;
 }
 
-// msda_bwd_wide.hip: the 16x16-block backward (fp32 / bf16, D = 32 or 64, L = P = 4, Lq == S).  ALO_ERR_UNSUPPORTED = nothing enqueued.
-int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
-                       const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, int N, int S, int M, int D, int Lq,
-                       int value_dtype, const int32_t* host_shapes, hipStream_t stream, bool plan_only = false);
+// msda_bwd_wide.hip: the 16x16-block backward.  msda_wide_plan is pure host logic: whether the path takes a launch (fp32 / bf16 values,
+// D = 32 or 64, Lq == S, a host copy of the shapes its block table can describe; the caller vouches for L = P = 4 and 16-byte aligned
+// pointers), filling `wp` when it does.  WidePlan is that file's WideDims, the kernel's by-value argument, opaque here: WideDims stays
+// in its anonymous namespace because the kernels' names carry it.  A field added there needs `words` resized (a static_assert says so).
+struct WidePlan {
+    int words[31];
+};
+bool msda_wide_plan(int N, int S, int M, int D, int Lq, int value_dtype, const int32_t* host_shapes, WidePlan* wp);
+int msda_wide_launch(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
+                     const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, const WidePlan& wp, int D,
+                     int value_dtype, hipStream_t stream);
 
 // Strided 1x1 convolution over an NHWC map read as a GEMM: row r of X' = pixel (n, s * yo, s * xo) of X; s <= 1: X' = X.
 struct RowGather {

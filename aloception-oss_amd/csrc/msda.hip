@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 #include "common.hpp"
 
@@ -1668,20 +1669,62 @@ struct Plan {
     bool lp16;
 };
 
-Plan make_plan(int D, int L, int P, size_t elem, bool aligned16) {
-    Plan p;
+// The generic forward's variant for a launch: G lanes x VEC channels cover a row.
+constexpr Plan make_plan(int D, int L, int P, size_t elem, bool aligned16) {
     const int vec = (int)(16 / elem);
-    if (aligned16 && D % vec == 0) {
-        p.vec = vec;
-        const int lanes = D / vec;
-        p.g = lanes <= 4 ? 4 : (lanes <= 8 ? 8 : (lanes <= 16 ? 16 : 64));
-    } else {
-        p.vec = 1;
-        p.g = D <= 8 ? 8 : 64;
-    }
-    p.lp16 = (L * P == 16) && p.vec != 1 && p.g != 64;
-    return p;
+    if (!aligned16 || D % vec != 0) return {1, D <= 8 ? 8 : 64, false};
+    const int lanes = D / vec;
+    const int g = lanes <= 4 ? 4 : (lanes <= 8 ? 8 : (lanes <= 16 ? 16 : 64));
+    return {vec, g, L * P == 16 && g != 64};
 }
+
+// The generic backward's.  Up to D = 64 one channel per lane: each of the four atomics of a sampling point then covers D consecutive
+// elements of ONE row (a whole 128-byte line for D = 32 fp32) instead of every VEC-th element of it.
+constexpr Plan make_bwd_plan(int D, int L, int P, size_t elem, bool aligned16) {
+    if (D <= 64) return {1, D <= 8 ? 8 : (D <= 32 ? 32 : 64), false};
+    return make_plan(D, L, P, elem, aligned16);
+}
+
+// Every (VEC, G, LP) a plan function can return, per direction: the instantiations of msda_fwd_kernel (plain and fused) and
+// msda_bwd_kernel that exist.  `wide`: VEC = the dtype's 16-byte vector (4 fp32, 2 fp64, 8 bf16 / fp16), else 1.  The backward's last two
+// rows are for 2-byte values only: D = 72 ... 128 is 9 ... 16 lanes of 8 there, more than 16 lanes of the wider types.
+struct Variant {
+    bool wide;
+    int g;
+    bool lp16;
+};
+constexpr Variant kFwdVariants[] = {{true, 4, true}, {true, 8, true}, {true, 16, true}, {true, 4, false}, {true, 8, false},
+                                    {true, 16, false}, {true, 64, false}, {false, 8, false}, {false, 64, false}};
+constexpr Variant kBwdVariants[] = {{false, 8, false}, {false, 32, false}, {false, 64, false}, {true, 64, false}, {true, 16, true}, {true, 16, false}};
+constexpr int kFwdRows = sizeof(kFwdVariants) / sizeof(Variant), kBwdRows = sizeof(kBwdVariants) / sizeof(Variant);
+constexpr int num_variants(bool bwd, size_t elem) { return !bwd ? kFwdRows : (elem == 2 ? kBwdRows : kBwdRows - 2); }
+constexpr const Variant& variant(bool bwd, int i) { return bwd ? kBwdVariants[i] : kFwdVariants[i]; }
+constexpr bool variant_is(const Variant& v, size_t elem, const Plan& p) {
+    return p.vec == (v.wide ? (int)(16 / elem) : 1) && p.g == v.g && p.lp16 == v.lp16;
+}
+
+// Plan function and table name the same set for values of `elem` bytes (bf16 and fp16 share 2): every plan is a row, every row is some
+// launch's plan.  D = 1 ... 256 is every case: beyond 128 (more than 16 lanes of any VEC, past both D thresholds) a plan depends on
+// D % VEC alone, and VEC <= 8.  L * P enters as == 16 or not.
+constexpr bool plans_are_table(bool bwd, size_t elem) {
+    const int n = num_variants(bwd, elem);
+    bool hit[kFwdRows > kBwdRows ? kFwdRows : kBwdRows] = {};
+    for (int D = 1; D <= 256; ++D)
+        for (int aligned = 0; aligned < 2; ++aligned)
+            for (int P = 3; P <= 4; ++P) {
+                const Plan p = bwd ? make_bwd_plan(D, 4, P, elem, aligned) : make_plan(D, 4, P, elem, aligned);
+                int row = -1;
+                for (int i = 0; i < n; ++i)
+                    if (variant_is(variant(bwd, i), elem, p)) row = i;
+                if (row < 0) return false;
+                hit[row] = true;
+            }
+    for (int i = 0; i < n; ++i)
+        if (!hit[i]) return false;
+    return true;
+}
+static_assert(plans_are_table(false, 4) && plans_are_table(false, 8) && plans_are_table(false, 2), "make_plan and kFwdVariants disagree");
+static_assert(plans_are_table(true, 4) && plans_are_table(true, 8) && plans_are_table(true, 2), "make_bwd_plan and kBwdVariants disagree");
 
 Dims make_dims(const Shape& s, int G, long target_blocks = 4096) {
     Dims d;
@@ -1713,23 +1756,37 @@ int launch_lp(unsigned nblocks, size_t lds, hipStream_t stream, const char* what
     return launch<kernel>(nblocks, kThreads, lds, stream, what, args);
 }
 
-#define ALO_FWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
-    if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
-        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(FwdDesc<CT>) + 16); \
-        if (fused)                                                                                                 \
-            return launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), true>>(lp.dm.nblocks, lds, stream, "alo_msda_forward_fused", args); \
-        return launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LPCT, (LPCT ? 4 : 2), false>>(lp.dm.nblocks, lds, stream, "alo_msda_forward", args);     \
-    }
-#define ALO_BWD_CASE(T, LT, CT, VEC, G, LPCT)                                                                     \
-    if (lp.plan.vec == VEC && lp.plan.g == G && lp.plan.lp16 == (LPCT == 16)) {                                    \
-        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)lp.dm.L * lp.dm.P * sizeof(BwdDesc<CT>) + 16); \
-        return launch_lp<msda_bwd_kernel<T, LT, CT, VEC, G, LPCT>>(lp.dm.nblocks, lds, stream, "alo_msda_backward", args); \
-    }
-// every (vector width, group) pair a plan can produce for one dtype
-#define ALO_ALL_CASES(CASE, T, LT, CT, VECW)                                                       \
-    CASE(T, LT, CT, VECW, 4, 16) CASE(T, LT, CT, VECW, 8, 16) CASE(T, LT, CT, VECW, 16, 16)         \
-    CASE(T, LT, CT, VECW, 4, 0) CASE(T, LT, CT, VECW, 8, 0) CASE(T, LT, CT, VECW, 16, 0)            \
-    CASE(T, LT, CT, VECW, 64, 0) CASE(T, LT, CT, 1, 8, 0) CASE(T, LT, CT, 1, 32, 0) CASE(T, LT, CT, 1, 64, 0)
+// The table rows for values of type T, tried in turn: the row that is the plan's launches its instantiation.
+template <bool BWD, typename T, typename LT, typename CT, int... I>
+int launch_rows(std::integer_sequence<int, I...>, const Plan& plan, const Dims& dm, bool fused, hipStream_t stream, void** args) {
+    int rc = ALO_OK;
+    auto row = [&](auto i) {
+        constexpr Variant v = variant(BWD, decltype(i)::value);
+        constexpr int VEC = v.wide ? (int)(16 / sizeof(T)) : 1, G = v.g, LP = v.lp16 ? 16 : 0;
+        if (!variant_is(v, sizeof(T), plan)) return false;
+        using Desc = std::conditional_t<BWD, BwdDesc<CT>, FwdDesc<CT>>;
+        const size_t lds = kMetaBytes + (size_t)(kThreads / G) * ((size_t)dm.L * dm.P * sizeof(Desc) + 16);
+        if constexpr (BWD)
+            rc = launch_lp<msda_bwd_kernel<T, LT, CT, VEC, G, LP>>(dm.nblocks, lds, stream, "alo_msda_backward", args);
+        else if (fused)
+            rc = launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LP, (LP ? 4 : 2), true>>(dm.nblocks, lds, stream, "alo_msda_forward_fused", args);
+        else
+            rc = launch_lp<msda_fwd_kernel<T, LT, CT, VEC, G, LP, (LP ? 4 : 2), false>>(dm.nblocks, lds, stream, "alo_msda_forward", args);
+        return true;
+    };
+    if ((... || row(std::integral_constant<int, I>{}))) return rc;
+    return fail(ALO_ERR_UNSUPPORTED, "msda: no generic kernel for vec=%d group=%d", plan.vec, plan.g);   // the static_asserts rule it out
+}
+// The generic kernel `plan` names, by value dtype (validate() has checked it).
+template <bool BWD>
+int launch_generic(int value_dtype, const Plan& plan, const Dims& dm, bool fused, hipStream_t stream, void** args) {
+    constexpr auto rows4 = std::make_integer_sequence<int, num_variants(BWD, 4)>{};   // fp64 has fp32's rows
+    constexpr auto rows2 = std::make_integer_sequence<int, num_variants(BWD, 2)>{};
+    if (value_dtype == ALO_F32) return launch_rows<BWD, float, float, float>(rows4, plan, dm, fused, stream, args);
+    if (value_dtype == ALO_F64) return launch_rows<BWD, double, double, double>(rows4, plan, dm, fused, stream, args);
+    if (value_dtype == ALO_BF16) return launch_rows<BWD, bf16_t, float, float>(rows2, plan, dm, fused, stream, args);
+    return launch_rows<BWD, f16_t, float, float>(rows2, plan, dm, fused, stream, args);
+}
 
 // What the library accepts at all, pointers aside.  The path queries ask this too, so they never name a kernel for a refused launch.
 int validate(const Shape& s, int ldt) {
@@ -1812,6 +1869,7 @@ struct LaunchPlan {
     Dims dm;       // every kernel but the tiled and the wide backward
     ResDims rd;    // resident forward
     TileDims td;   // tiled backward
+    WidePlan wd;   // wide backward
 };
 
 // Pure host logic: which forward kernel a launch takes and that kernel's dims.  forward_impl launches what this says,
@@ -1875,11 +1933,7 @@ int forward_impl(const void* value, const int32_t* spatial_shapes, const int32_t
         return launch<msda_fwd_bf16_mfma_kernel<bf16_t, 4, false, false>>(nblocks, 64, kWaveLds, stream, "alo_msda_forward", args);
     case FWD_GENERIC:;
     }
-    if (s.value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_FWD_CASE, float, float, float, 4) }
-    if (s.value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_FWD_CASE, double, double, double, 2) }
-    if (s.value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_FWD_CASE, bf16_t, float, float, 8) }
-    if (s.value_dtype == ALO_F16) { ALO_ALL_CASES(ALO_FWD_CASE, f16_t, float, float, 8) }
-    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_forward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
+    return launch_generic<false>(s.value_dtype, lp.plan, lp.dm, fused, stream, args);
 }
 
 // The argument checks the fused entry points share; `rows` = {offsets_row_elems, logits_row_elems} where the entry point takes them.
@@ -1973,11 +2027,9 @@ LaunchPlan plan_backward(const Shape& s, const int32_t* host_shapes, bool aligne
     const bool frame32 = (double)S * M * 128 < 4.0e9 && (double)Lq * M * 32 < 2.0e9;   // 32-bit byte offsets inside one frame
     const bool detr = L == 4 && P == 4 && all_aligned && frame32;
     const bool pyramid = host_shapes && Lq == S;   // queries = the pyramid's own pixels (encoder self-attention)
-    // 16x16 query blocks, sorted on chip (msda_bwd_wide.hip).  That file's host side has the last word: a geometry its block table
-    // cannot describe goes to the kernels below.
-    if ((vdt == ALO_F32 || vdt == ALO_BF16) && (D == 32 || D == 64) && detr && pyramid && !no_wide &&
-        msda_backward_wide(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, S, M, D, Lq, vdt, host_shapes,
-                           nullptr, true) == ALO_OK) {
+    // 16x16 query blocks, sorted on chip (msda_bwd_wide.hip).  That file says which dtypes, D and geometries it takes: a launch its
+    // block table cannot describe goes to the kernels below.
+    if (detr && !no_wide && msda_wide_plan(N, S, M, D, Lq, vdt, host_shapes, &bp.wd)) {
         bp.route = ALO_MSDA_BWD_WIDE;
     } else if (vdt == ALO_F32 && D == 32 && detr) {
         // the DETR-family shape: tiled, window-dense backward on the fp32 matrix cores (msda_bwd_tiled_kernel)
@@ -2006,14 +2058,7 @@ LaunchPlan plan_backward(const Shape& s, const int32_t* host_shapes, bool aligne
         td.nblocks = (unsigned)nb;
     } else {
         bp.route = ALO_MSDA_BWD_GENERIC;
-        bp.plan = make_plan(D, L, P, s.elem(), aligned);
-        if (D <= 64) {
-            // one channel per lane: each of the four atomics of a sampling point then covers D consecutive elements of ONE row
-            // (a whole 128-byte line for D = 32 fp32) instead of every VEC-th element of it
-            bp.plan.vec = 1;
-            bp.plan.g = D <= 8 ? 8 : (D <= 32 ? 32 : 64);
-            bp.plan.lp16 = false;
-        }
+        bp.plan = make_bwd_plan(D, L, P, s.elem(), aligned);
         bp.dm = make_dims(s, bp.plan.g);
     }
     return bp;
@@ -2036,16 +2081,12 @@ extern "C" int alo_msda_backward_hinted(const void* value, const int32_t* spatia
     hipError_t e = hipMemsetAsync(grad_value, 0, (size_t)N * S * M * D * (value_dtype == ALO_F64 ? 8 : 4), stream);
     if (e != hipSuccess) return fail(ALO_ERR_LAUNCH, "alo_msda_backward: memset: %s", hipGetErrorString(e));
     if (lp.route == ALO_MSDA_BWD_WIDE)
-        return msda_backward_wide(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
-                                  grad_sampling_loc, grad_attn_weight, N, S, M, D, Lq, value_dtype, host_spatial_shapes, stream);
+        return msda_wide_launch(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_value,
+                                grad_sampling_loc, grad_attn_weight, lp.wd, D, value_dtype, stream);
     void* args[] = {&value, &spatial_shapes, &level_start_index, &sampling_loc, &attn_weight, &grad_out, &grad_value,
                     &grad_sampling_loc, &grad_attn_weight, lp.route == ALO_MSDA_BWD_TILED ? (void*)&lp.td : (void*)&lp.dm};
     if (lp.route == ALO_MSDA_BWD_TILED) return launch<msda_bwd_tiled_kernel>(lp.td.nblocks, 64, kTileLds, stream, "alo_msda_backward", args);
-    if (value_dtype == ALO_F32) { ALO_ALL_CASES(ALO_BWD_CASE, float, float, float, 4) }
-    if (value_dtype == ALO_F64) { ALO_ALL_CASES(ALO_BWD_CASE, double, double, double, 2) }
-    if (value_dtype == ALO_BF16) { ALO_ALL_CASES(ALO_BWD_CASE, bf16_t, float, float, 8) }
-    if (value_dtype == ALO_F16) { ALO_ALL_CASES(ALO_BWD_CASE, f16_t, float, float, 8) }
-    return fail(ALO_ERR_UNSUPPORTED, "alo_msda_backward: no kernel for vec=%d group=%d", lp.plan.vec, lp.plan.g);
+    return launch_generic<true>(value_dtype, lp.plan, lp.dm, false, stream, args);
 }
 
 extern "C" int alo_msda_backward(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,

@@ -38,11 +38,13 @@
 // 4.1 / 3.9 for msda_bwd_kernel; D = 64 1.36 / 1.55 against 8.4 / 7.8.  VALU-issue bound (67 % of the SIMD time): the build log with every
 // intermediate number is docs/experiments.md R6.1.
 //
-// Shapes served: value / grad_out fp32 or bf16 (gradients fp32), D = 32, L = P = 4, queries = the pyramid's own pixels (Lq == S).
+// Shapes served: value / grad_out fp32 or bf16 (gradients fp32), D = 32 or 64, L = P = 4, queries = the pyramid's own pixels (Lq == S);
+// what msda_wide_plan turns down goes to msda_bwd_tiled_kernel when it is fp32 with D = 32, else (D = 64, bf16) to the generic msda_bwd_kernel.
 // The host copy of the shapes sizes the grid AND travels by value; a launch whose device shapes differ from it sends every
 // sample down the per-corner route with the queries grouped 256 in a row (correct, slow — the Python host never caches shapes).
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "common.hpp"
@@ -248,8 +250,6 @@ msda_bwd_wide_kernel(const T* __restrict__ value, const int32_t* __restrict__ sh
     }
     for (int r = tid; r < kCnt; r += kWThreads) cnt[r] = 0;
     if (tid < 128) ovf[tid] = same ? 0u : 0xffffffffu;
-    // the walk reads up to 15 entries past an item's end: every list slot always holds a valid entry number (weights are masked, the
-    // grad_out row it names is finite)
     for (int i = tid; i < (4096 + 32) / 2; i += kWThreads) reinterpret_cast<unsigned*>(list)[i] = 0;
 
     const int slot = tid >> 1, ph = tid & 1;   // neighbouring lanes hold the two point pairs of a query: 32 contiguous bytes of loc / grad_loc
@@ -591,15 +591,15 @@ msda_bwd_wide_kernel(const T* __restrict__ value, const int32_t* __restrict__ sh
 
 }  // namespace
 
-// Host side of the wide path.  Returns ALO_OK after enqueuing, or ALO_ERR_UNSUPPORTED (nothing enqueued) when the geometry is not
-// one the block table can describe — the caller then takes msda_bwd_tiled_kernel.
-int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
-                       const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, int N, int S, int M, int D, int Lq,
-                       int value_dtype, const int32_t* host_shapes, hipStream_t stream, bool plan_only) {
-    if (!host_shapes || Lq != S || (D != 32 && D != 64)) return ALO_ERR_UNSUPPORTED;
-    if (value_dtype != ALO_F32 && value_dtype != ALO_BF16) return ALO_ERR_UNSUPPORTED;
-    if (S >= (1 << 24) || (long)M * D * 4 >= (1L << 24)) return ALO_ERR_UNSUPPORTED;   // 24-bit multiplies in the gather's address arithmetic
-    if ((double)S * M * D * 4 >= 4.0e9) return ALO_ERR_UNSUPPORTED;     // 32-bit byte offsets inside one frame
+static_assert(sizeof(WideDims) == sizeof(WidePlan) && alignof(WideDims) == alignof(WidePlan), "common.hpp's WidePlan must hold a WideDims");
+
+// Host side of the wide path: plan, then launch.  The plan is false when the launch is not one the path serves or the geometry is
+// not one the block table can describe (see "Shapes served" above for where it goes then).
+bool msda_wide_plan(int N, int S, int M, int D, int Lq, int value_dtype, const int32_t* host_shapes, WidePlan* wp) {
+    if (!host_shapes || Lq != S || (D != 32 && D != 64)) return false;
+    if (value_dtype != ALO_F32 && value_dtype != ALO_BF16) return false;
+    if (S >= (1 << 24) || (long)M * D * 4 >= (1L << 24)) return false;   // 24-bit multiplies in the gather's address arithmetic
+    if ((double)S * M * D * 4 >= 4.0e9) return false;     // 32-bit byte offsets inside one frame
     WideDims wd;
     wd.N = N; wd.S = S; wd.M = M; wd.Lq = Lq;
     long total = 0;
@@ -607,13 +607,13 @@ int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* 
     for (int l = 0; l < 4; ++l) {
         wd.h[l] = host_shapes[2 * l];
         wd.w[l] = host_shapes[2 * l + 1];
-        if (wd.h[l] <= 0 || wd.w[l] <= 0 || wd.h[l] >= 32768 || wd.w[l] >= 32768) return ALO_ERR_UNSUPPORTED;
+        if (wd.h[l] <= 0 || wd.w[l] <= 0 || wd.h[l] >= 32768 || wd.w[l] >= 32768) return false;
         wd.start[l] = (int)total;
         total += (long)wd.h[l] * wd.w[l];
         hmax = wd.h[l] > hmax ? wd.h[l] : hmax;
         wmax = wd.w[l] > wmax ? wd.w[l] : wmax;
     }
-    if (total != S) return ALO_ERR_UNSUPPORTED;
+    if (total != S) return false;
     int blocks = 0;
     for (int l = 0; l < 4; ++l) {
         // the block's footprint on the finest level stays within 32 px (5 % slack: 167 / 84, 100 / 13 are not powers of two)
@@ -627,11 +627,20 @@ int msda_backward_wide(const void* value, const int32_t* shapes, const int32_t* 
         blocks += wd.nbx[l] * ((wd.h[l] + bs - 1) / bs);
     }
     wd.first[4] = blocks;
-    if (blocks * kSlots < Lq) return ALO_ERR_UNSUPPORTED;   // cannot happen (a block holds at most 256 queries)
+    if (blocks * kSlots < Lq) return false;   // cannot happen (a block holds at most 256 queries)
     const long nb = (long)N * blocks * M;
-    if (nb >= 0x7fffffffL) return ALO_ERR_UNSUPPORTED;
+    if (nb >= 0x7fffffffL) return false;
     wd.nblocks = (unsigned)nb;
-    if (plan_only) return ALO_OK;
+    wd.dbg = 0;
+    memcpy(wp, &wd, sizeof wd);
+    return true;
+}
+
+int msda_wide_launch(const void* value, const int32_t* shapes, const int32_t* lstart, const void* loc, const void* attn,
+                     const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, const WidePlan& wp, int D,
+                     int value_dtype, hipStream_t stream) {
+    WideDims wd;
+    memcpy(&wd, &wp, sizeof wd);
     wd.dbg = getenv("ALO_WIDE_DBG") ? atoi(getenv("ALO_WIDE_DBG")) : 0;
     void* args[] = {&value, &shapes, &lstart, &loc, &attn, &grad_out, &grad_value, &grad_loc, &grad_attn, &wd};
     const char* what = "alo_msda_backward (wide)";

@@ -194,9 +194,9 @@ int alo_msda_backward(const void* value, const int32_t* spatial_shapes, const in
  * The same operation with a scheduling hint: `host_spatial_shapes` is a HOST copy of spatial_shapes (L x 2 int32, may be NULL).
  * When the queries are the pyramid's own pixels (Lq == S, the encoder's self-attention) the D = 32 or 64, L = P = 4 launches (fp32 or
  * bf16 values) then group them as 16x16 blocks of their level, sort a block's sampling corners by pixel on chip and issue ONE atomic
- * row per touched pixel per block (msda_bwd_wide.hip); without the hint fp32 D = 32 takes 4x4 tiles of 16 consecutive queries.  Results do not depend on
- * the hint (up to the order of the floating-point additions, which atomics leave undefined anyway); alo_msda_backward is this
- * call with a NULL hint.
+ * row per touched pixel per block (msda_bwd_wide.hip).  Without the hint, or with a pyramid that path cannot describe, fp32 D = 32
+ * takes 4x4 tiles of 16 consecutive queries and the others (D = 64, bf16) the generic kernel.  Results do not depend on the hint (up to
+ * the order of the floating-point additions, which atomics leave undefined anyway); alo_msda_backward is this call with a NULL hint.
  */
 int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, const int32_t* level_start_index,
                              const void* sampling_loc, const void* attn_weight, const void* grad_out,
@@ -208,8 +208,8 @@ int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, c
  * Which kernel alo_msda_backward_hinted takes for a launch of these dimensions (pointers assumed 16-byte aligned), without
  * enqueuing anything: ALO_MSDA_BWD_WIDE (16x16 query blocks sorted on chip, one atomic row per touched pixel per block: fp32 / bf16
  * values, D = 32 or 64, L = P = 4, Lq == S and a host copy of the shapes), ALO_MSDA_BWD_TILED (4x4 query tiles on the fp32 matrix cores:
- * fp32, D = 32, L = P = 4), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else, every fp16 launch included); -1 for a
- * launch the library refuses
+ * fp32, D = 32, L = P = 4 that the wide path does not take), ALO_MSDA_BWD_GENERIC (one atomic row per corner: everything else,
+ * including D = 64 or bf16 launches the wide path turns down, and every fp16 launch); -1 for a launch the library refuses
  * (dtype pair, dimensions, sizes: alo_last_error says which).  The launch and this query read one plan, so they cannot disagree.
  */
 #define ALO_MSDA_BWD_GENERIC 0
