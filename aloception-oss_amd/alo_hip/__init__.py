@@ -22,9 +22,18 @@ CSRC_DIR = os.path.join(_PKG_ROOT, "csrc")
 
 ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
-# fp16 is a value dtype of the MSDA entry points and of value_head_major only; every other user of this table sits behind a gate that
-# names fp32 / bf16 (fusable, *_supported), so an fp16 tensor never reaches a kernel that lacks it
+# fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
+# value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
+# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only.  fp16 is opt-in per call site: `fusable`
+# and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
+# fp16 kernels do (the transformer's layers), so an fp16 tensor never reaches a kernel that lacks it
 _DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
+
+
+def _half(f16):
+    """The 16-bit storage types a gate of the MFMA layer kernels lets through."""
+    return (torch.bfloat16, torch.float16) if f16 else (torch.bfloat16,)
+
 
 _lib = None
 _warned_inference_tensor = False
@@ -660,12 +669,14 @@ def corr_alt_lookup(workspace, coords, channels, num_levels, radius=4):
     return out
 
 
-def fusable(*tensors):
-    """True when the fused epilogues may replace the stock ops: inference (no autograd graph), CUDA, fp32 or bf16."""
+def fusable(*tensors, f16=False):
+    """True when the fused epilogues may replace the stock ops: inference (no autograd graph), CUDA, fp32 or bf16 — and fp16 with
+    ``f16=True``, which a caller passes when every kernel behind it serves fp16 (the transformer's layers do; the backbone, the
+    input projections, the mask head and RAFT's update block do not)."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
         return False
     first = tensors[0]
-    return first.is_cuda and first.dtype in (torch.float32, torch.bfloat16)
+    return first.is_cuda and first.dtype in (torch.float32, *_half(f16))
 
 
 def add_layernorm_supported(x):
@@ -796,16 +807,19 @@ def pos_sine_flat(mask_flatten, spatial_shapes, level_start_index, dim_t, level_
 
 
 # ---- short-K linear layers on the streaming MFMA kernel (alo_linear_shortk) -----------------------------------------------------
-def linear_shortk_supported(x, weight):
-    return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x.shape[-1] in (64, 128, 256)
+def linear_shortk_supported(x, weight, f16=False):
+    """bf16 (with ``f16=True``: or fp16) CUDA input and weight of one dtype, K in (64, 128, 256), N % 64 == 0."""
+    return (x.is_cuda and x.dtype in _half(f16) and weight.dtype == x.dtype and x.shape[-1] in (64, 128, 256)
             and weight.dim() == 2 and weight.shape[1] == x.shape[-1] and weight.shape[0] % 64 == 0)
 
 
 def linear_shortk(x, weight, bias=None, relu=False, residual=None):
-    """``act(x @ weight.T + bias [+ residual])`` over the last dim (64 / 128 / 256) of a bf16 ``x``; weight (N, K), N % 64 == 0;
+    """``act(x @ weight.T + bias [+ residual])`` over the last dim (64 / 128 / 256) of a bf16 / fp16 ``x``; weight (N, K), N % 64 == 0;
     ``residual`` has the shape of the result and is added before the activation."""
-    if not linear_shortk_supported(x, weight):
-        raise RuntimeError("linear_shortk: needs bf16 CUDA tensors, K in (64, 128, 256) and N % 64 == 0")
+    if not linear_shortk_supported(x, weight, f16=True):
+        raise RuntimeError("linear_shortk: needs bf16 / fp16 CUDA tensors of one dtype, K in (64, 128, 256) and N % 64 == 0")
+    if bias is not None and bias.dtype != x.dtype:
+        raise RuntimeError("linear_shortk: bias must have the dtype of x")
     N, K = weight.shape
     x2 = x.reshape(-1, K)
     if not x2.is_contiguous():
@@ -819,13 +833,14 @@ def linear_shortk(x, weight, bias=None, relu=False, residual=None):
     if M:
         nbytes = 2.0 * (x2.numel() + y.numel() * (2 if residual is not None else 1))
         _launch("alo_linear_shortk", x.device, f"linear_shortk/N={N},K={K}", nbytes, 2.0 * M * N * K, x2, weight.contiguous(),
-                None if bias is None else bias.contiguous(), residual, y, M, N, K, 1 if relu else 0, ALO_BF16)
+                None if bias is None else bias.contiguous(), residual, y, M, N, K, 1 if relu else 0, _DTYPE_CODE[x.dtype])
     return y.view(*x.shape[:-1], N)
 
 
-def linear_packed_supported(x, weight):
-    """bf16 CUDA, K % 256 == 0 (K >= 512: below that linear_shortk keeps the weights in registers), N % 128 == 0, inference."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and weight.dim() == 2
+def linear_packed_supported(x, weight, f16=False):
+    """bf16 (with ``f16=True``: or fp16) CUDA (input and weight of one dtype), K % 256 == 0 (K >= 512: below that linear_shortk keeps the weights in
+    registers), N % 128 == 0, inference."""
+    return (x.is_cuda and x.dtype in _half(f16) and weight.dtype == x.dtype and weight.dim() == 2
             and x.shape[-1] == weight.shape[1] and weight.shape[1] % 256 == 0 and weight.shape[1] >= 512
             and weight.shape[0] % 128 == 0 and not torch.is_grad_enabled())
 
@@ -833,8 +848,8 @@ def linear_packed_supported(x, weight):
 def linear_packed(x, weight, bias=None, relu=False, residual=None):
     """``act(F.linear(x, weight, bias) [+ residual])`` with the weight streamed in MFMA fragment order (packed once per weight
     version, cached on the tensor)."""
-    if not linear_packed_supported(x, weight):
-        raise RuntimeError("linear_packed: needs bf16 CUDA tensors, K % 256 == 0, K >= 512, N % 128 == 0, no autograd")
+    if not linear_packed_supported(x, weight, f16=True):
+        raise RuntimeError("linear_packed: needs bf16 / fp16 CUDA tensors of one dtype, K % 256 == 0, K >= 512, N % 128 == 0, no autograd")
     x2 = x.reshape(-1, x.shape[-1])
     if not x2.is_contiguous():
         x2 = x2.contiguous()
@@ -849,7 +864,7 @@ def linear_packed(x, weight, bias=None, relu=False, residual=None):
         packed = pack_mfma_b(weight)
         bias_c = None if bias is None else bias.to(x.dtype).contiguous()
         _launch("alo_linear_packed", x.device, f"linear_packed/K={K}/N={N}", 2.0 * (M * K + M * N * (2 if residual is not None else 1)),
-                2.0 * M * N * K, x2, packed, bias_c, residual, y, M, N, K, 1 if relu else 0, ALO_BF16)
+                2.0 * M * N * K, x2, packed, bias_c, residual, y, M, N, K, 1 if relu else 0, _DTYPE_CODE[x.dtype])
     return y.view(*x.shape[:-1], N)
 
 
@@ -857,7 +872,7 @@ def conv1x1_strided_supported(x, weight2d):
     """Strided 1x1 convolution of a channels-last bf16 map addressed inside the GEMM's tile loader: the shapes linear_auto
     would send to one of the streaming kernels."""
     if not (x.dim() == 4 and x.is_cuda and x.is_contiguous(memory_format=torch.channels_last)):
-        return False
+        return False   # (alo_conv1x1_nhwc is bf16 only: the two GEMM gates below are asked without f16)
     if os.environ.get("ALO_CONV1X1_GATHER") == "0":   # A/B knob: gather the kept pixels with a copy kernel first
         return False
     rows = x.permute(0, 2, 3, 1)
@@ -884,11 +899,11 @@ def conv1x1_strided(x, weight2d, bias, stride, relu=False):
 
 def linear_auto(x, weight, bias=None, relu=False, residual=None):
     """Inference-time ``act(F.linear(x, weight, bias) [+ residual])``: the streaming MFMA kernels when the shape allows it
-    (bf16; K in {64, 128, 256} with N % 64 == 0, or K % 256 == 0 with N % 128 == 0), otherwise the stock GEMM with the bias /
+    (bf16 / fp16; K in {64, 128, 256} with N % 64 == 0, or K % 256 == 0 with N % 128 == 0), otherwise the stock GEMM with the bias /
     ReLU epilogue."""
-    if linear_shortk_supported(x, weight) and (bias is None or bias.dtype == x.dtype):
+    if linear_shortk_supported(x, weight, f16=True) and (bias is None or bias.dtype == x.dtype):
         return linear_shortk(x, weight, bias, relu, residual=residual)
-    if linear_packed_supported(x, weight) and (bias is None or bias.dtype == x.dtype) and (
+    if linear_packed_supported(x, weight, f16=True) and (bias is None or bias.dtype == x.dtype) and (
             residual is not None or weight.shape[0] >= 1024 or tuple(weight.shape) == (128, 512)):
         # measured on MI355X at the backbone's shapes: the streaming kernel wins with many output columns, with the identity
         # fused in, and at (N, K) = (128, 512); hipBLASLt wins the rest
@@ -906,29 +921,33 @@ def linear_auto(x, weight, bias=None, relu=False, residual=None):
     return y.view(*x.shape[:-1], weight.shape[0])
 
 
-def ffn256_supported(x, w1, w2):
-    return (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] == 256 and w1.dtype == torch.bfloat16
-            and w2.dtype == torch.bfloat16 and w1.dim() == 2 and w1.shape[1] == 256 and w1.shape[0] % 256 == 0
+def ffn256_supported(x, w1, w2, f16=False):
+    """bf16 (with ``f16=True``: or fp16) CUDA (input and both weights of one dtype), d_model = 256, hidden width % 256 == 0."""
+    return (x.is_cuda and x.dtype in _half(f16) and x.shape[-1] == 256 and w1.dtype == x.dtype
+            and w2.dtype == x.dtype and w1.dim() == 2 and w1.shape[1] == 256 and w1.shape[0] % 256 == 0
             and tuple(w2.shape) == (256, w1.shape[0]))
 
 
 def pack_mfma_b(weight):
-    """(N, K) bf16 weight -> MFMA B-fragment order.  The packed copy rides on the weight tensor object itself
+    """(N, K) bf16 / fp16 weight -> MFMA B-fragment order (16-bit elements moved as bits).  The packed copy rides on the weight tensor object itself
     (:func:`derived`): packed once per weight update, gone with the tensor."""
     return derived(weight, "mfma_b", (weight,), lambda: _pack_mfma_b(weight.contiguous()))
 
 
 def _pack_mfma_b(w):
-    """The pack kernel on a contiguous (N, K) bf16 matrix."""
+    """The pack kernel on a contiguous (N, K) bf16 / fp16 matrix."""
+    if w.dtype not in _half(True):
+        raise RuntimeError("pack_mfma_b: needs a bf16 / fp16 weight")
     packed = torch.empty_like(w)
-    _launch("alo_pack_mfma_b", w.device, None, 0.0, 0.0, w, packed, w.shape[0], w.shape[1], ALO_BF16)   # once per weight version: untimed
+    _launch("alo_pack_mfma_b", w.device, None, 0.0, 0.0, w, packed, w.shape[0], w.shape[1], _DTYPE_CODE[w.dtype])   # once per weight version: untimed
     return packed
 
 
 def ffn256(x, w1, b1, w2, b2):
-    """``relu(x @ w1.T + b1) @ w2.T + b2`` over the last dim (= 256) of a bf16 ``x`` in one kernel (hidden width % 256 == 0)."""
-    if not ffn256_supported(x, w1, w2):
-        raise RuntimeError("ffn256: needs bf16 CUDA tensors, d_model = 256 and a hidden width that is a multiple of 256")
+    """``relu(x @ w1.T + b1) @ w2.T + b2`` over the last dim (= 256) of a bf16 / fp16 ``x`` in one kernel (hidden width % 256 == 0);
+    the hidden activation is rounded to ``x``'s dtype before the second product, as two launches would store it."""
+    if not ffn256_supported(x, w1, w2, f16=True):
+        raise RuntimeError("ffn256: needs bf16 / fp16 CUDA tensors of one dtype, d_model = 256 and a hidden width that is a multiple of 256")
     x2 = x.reshape(-1, 256)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
@@ -937,7 +956,8 @@ def ffn256(x, w1, b1, w2, b2):
     if M:
         p1, p2 = pack_mfma_b(w1), pack_mfma_b(w2)
         _launch("alo_ffn256", x.device, f"ffn256/F={Fh}", 4.0 * x2.numel(), 4.0 * M * 256 * Fh, x2, p1,
-                None if b1 is None else b1.contiguous(), p2, None if b2 is None else b2.contiguous(), y, M, Fh, ALO_BF16)
+                None if b1 is None else b1.to(x.dtype).contiguous(), p2, None if b2 is None else b2.to(x.dtype).contiguous(), y, M, Fh,
+                _DTYPE_CODE[x.dtype])
     return y.view(x.shape)
 
 
@@ -1164,15 +1184,17 @@ def encoder_reference_points(valid_ratios, shapes):
     return out
 
 
-def value_proj_head_major_supported(x, weight, heads):
-    return (linear_shortk_supported(x, weight) and heads % 2 == 0 and weight.shape[0] == heads * 32 and x.dim() == 3)
+def value_proj_head_major_supported(x, weight, heads, f16=False):
+    return (linear_shortk_supported(x, weight, f16) and heads % 2 == 0 and weight.shape[0] == heads * 32 and x.dim() == 3)
 
 
 def value_proj_head_major(x, weight, bias, padding_mask, heads):
-    """``value_proj`` + ``masked_fill(padding_mask, 0)`` + head-major layout in one kernel: x (N, S, K) bf16 ->
+    """``value_proj`` + ``masked_fill(padding_mask, 0)`` + head-major layout in one kernel: x (N, S, K) bf16 / fp16 ->
     (N, heads, S, 32) for ``msda_forward_fused_hm``."""
-    if not value_proj_head_major_supported(x, weight, heads):
-        raise RuntimeError("value_proj_head_major: needs bf16 (N, S, K) input, K in (64, 128, 256), head dimension 32")
+    if not value_proj_head_major_supported(x, weight, heads, f16=True):
+        raise RuntimeError("value_proj_head_major: needs bf16 / fp16 (N, S, K) input, K in (64, 128, 256), head dimension 32")
+    if bias is not None and bias.dtype != x.dtype:
+        raise RuntimeError("value_proj_head_major: bias must have the dtype of x")
     N, S, K = x.shape
     x = x if x.is_contiguous() else x.contiguous()
     if padding_mask is not None:
@@ -1181,7 +1203,7 @@ def value_proj_head_major(x, weight, bias, padding_mask, heads):
         padding_mask = padding_mask.contiguous()
     out = torch.empty((N, heads, S, 32), dtype=x.dtype, device=x.device)
     _launch("alo_value_proj_head_major", x.device, f"value_proj_hm/S={S}", 2.0 * (x.numel() + out.numel()), 2.0 * N * S * heads * 32 * K,
-            x, weight.contiguous(), None if bias is None else bias.contiguous(), padding_mask, out, N, S, heads, K, ALO_BF16)
+            x, weight.contiguous(), None if bias is None else bias.contiguous(), padding_mask, out, N, S, heads, K, _DTYPE_CODE[x.dtype])
     return out
 
 
@@ -1299,16 +1321,16 @@ def encoder_proposals(mask_flatten, shapes):
     return proposals, keep.view(torch.bool)
 
 
-def encoder_proposals_masked_supported(mask_flatten, shapes, memory):
+def encoder_proposals_masked_supported(mask_flatten, shapes, memory, f16=False):
     """What :func:`encoder_proposals` needs of the mask and :func:`mask_rows` of the rows, for memory (B, S, C) on the mask's device."""
     return (encoder_proposals_supported(mask_flatten, shapes) and memory.dim() == 3 and memory.device == mask_flatten.device
-            and tuple(memory.shape[:2]) == tuple(mask_flatten.shape) and mask_rows_supported(memory, mask_flatten))
+            and tuple(memory.shape[:2]) == tuple(mask_flatten.shape) and mask_rows_supported(memory, mask_flatten, f16))
 
 
 def encoder_proposals_masked(mask_flatten, shapes, memory):
     """:func:`encoder_proposals` and :func:`mask_rows` in one launch -> (proposals, keep, memory with the dropped rows zeroed):
     0.026 against 0.029 ms for the two launches at the headline size (docs/experiments.md)."""
-    if not encoder_proposals_masked_supported(mask_flatten, shapes, memory):
+    if not encoder_proposals_masked_supported(mask_flatten, shapes, memory, f16=True):
         raise RuntimeError("encoder_proposals_masked: needs what encoder_proposals and mask_rows need, memory (B, S, C) on the mask's device")
     B, S = mask_flatten.shape
     arr, L = _host_shapes(shapes)
@@ -1321,9 +1343,10 @@ def encoder_proposals_masked(mask_flatten, shapes, memory):
     return proposals, keep.view(torch.bool), out
 
 
-def mask_rows_supported(memory, keep):
-    """CUDA, contiguous fp32 / bf16 rows of a multiple of 8 channels, one bool / uint8 per row, 16-byte aligned."""
-    return (memory.is_cuda and memory.dtype in (torch.float32, torch.bfloat16) and memory.is_contiguous() and memory.dim() >= 2
+def mask_rows_supported(memory, keep, f16=False):
+    """CUDA, contiguous fp32 / bf16 (with ``f16=True``: or fp16) rows of a multiple of 8 channels, one bool / uint8 per row, 16-byte
+    aligned."""
+    return (memory.is_cuda and memory.dtype in (torch.float32, *_half(f16)) and memory.is_contiguous() and memory.dim() >= 2
             and memory.shape[-1] % 8 == 0 and memory.numel() > 0 and memory.data_ptr() % 16 == 0
             and keep.is_cuda and keep.dtype in (torch.bool, torch.uint8) and keep.is_contiguous()
             and tuple(keep.shape) == tuple(memory.shape[:-1]))
@@ -1331,8 +1354,8 @@ def mask_rows_supported(memory, keep):
 
 def mask_rows(memory, keep):
     """``memory.masked_fill(~keep[..., None], 0)`` in one pass of 16-byte vectors; dropped rows are written, not read."""
-    if not mask_rows_supported(memory, keep):
-        raise RuntimeError("mask_rows: needs contiguous CUDA fp32 / bf16 rows with C % 8 == 0 and one bool / uint8 `keep` per row")
+    if not mask_rows_supported(memory, keep, f16=True):
+        raise RuntimeError("mask_rows: needs contiguous CUDA fp32 / bf16 / fp16 rows with C % 8 == 0 and one bool / uint8 `keep` per row")
     C = memory.shape[-1]
     rows = memory.numel() // C
     out = torch.empty_like(memory)
@@ -1341,11 +1364,11 @@ def mask_rows(memory, keep):
     return out
 
 
-def proposal_queries_supported(coords_unact, topk, dtype):
+def proposal_queries_supported(coords_unact, topk, dtype, f16=False):
     return (coords_unact.is_cuda and coords_unact.dtype == torch.float32 and coords_unact.dim() == 3 and coords_unact.shape[2] == 4
             and coords_unact.is_contiguous() and coords_unact.numel() > 0 and coords_unact.data_ptr() % 16 == 0
             and topk.is_cuda and topk.dtype == torch.int64 and topk.dim() == 2 and topk.shape[0] == coords_unact.shape[0]
-            and topk.is_contiguous() and topk.numel() > 0 and dtype in (torch.float32, torch.bfloat16))
+            and topk.is_contiguous() and topk.numel() > 0 and dtype in (torch.float32, *_half(f16)))
 
 
 def proposal_dim_t(device, owner=None):
@@ -1363,8 +1386,8 @@ def proposal_queries(coords_unact, topk, dtype, owner=None):
     (reference_points (B, K, 4) float32 = sigmoid of the gathered rows, embed (B, K, 512) ``dtype`` = their sine embedding,
     ``get_proposal_pos_embed``).  ``owner``: the weight the embedding feeds (``pos_trans.weight``), which keeps the 64 frequencies
     (:func:`proposal_dim_t`); without one they are computed per call."""
-    if not proposal_queries_supported(coords_unact, topk, dtype):
-        raise RuntimeError("proposal_queries: needs contiguous CUDA (B, S, 4) float32 coordinates, (B, K) int64 indices, fp32 / bf16 output")
+    if not proposal_queries_supported(coords_unact, topk, dtype, f16=True):
+        raise RuntimeError("proposal_queries: needs contiguous CUDA (B, S, 4) float32 coordinates, (B, K) int64 indices, fp32 / bf16 / fp16 output")
     B, S, _ = coords_unact.shape
     K = topk.shape[1]
     ref = torch.empty((B, K, 4), dtype=torch.float32, device=coords_unact.device)

@@ -155,7 +155,7 @@ class DeformableDETR(nn.Module):
         lean = getattr(self, "_alo_lean_bb_outputs", False)
         lazy_pos = ((not self.return_bb_outputs or lean) and "is_tracing" not in kwargs and not self.training
                     and isinstance(self.backbone[1], PositionEmbeddingSine) and self.backbone[1].num_pos_feats % 4 == 0
-                    and alo_hip.fusable(frames.as_tensor(), self.transformer.level_embed))
+                    and alo_hip.fusable(frames.as_tensor(), self.transformer.level_embed, f16=True))   # alo_pos_sine_flat serves fp16
         skip = tuple(range(len(self.backbone.num_channels))) if lazy_pos else (() if self.return_bb_outputs else (0,))
         # inference: the per-level padding masks come from one kernel below, not from one F.interpolate per backbone stage
         features, pos = self.backbone(frames, skip_pos_levels=skip, **(dict(kwargs, skip_masks=True) if lazy_pos else kwargs))

@@ -44,8 +44,8 @@ def _level_geometry(shapes, device):
 
 def _fused_ok(module, kwargs, *tensors):
     """The one-pass HIP epilogues (alo_add_layernorm) stand in for ``norm(x + dropout(y))`` when nothing is lost: eval mode
-    (dropout is the identity), no autograd graph, CUDA, fp32 / bf16, and not the pure-torch export branch."""
-    return (not module.training and "is_tracing" not in kwargs and alo_hip.fusable(*tensors)
+    (dropout is the identity), no autograd graph, CUDA, fp32 / bf16 / fp16, and not the pure-torch export branch."""
+    return (not module.training and "is_tracing" not in kwargs and alo_hip.fusable(*tensors, f16=True)
             and alo_hip.add_layernorm_supported(tensors[0]))
 
 
@@ -71,10 +71,10 @@ def _self_attention(mha, qk_in, v_in):
 
 def _ffn(linear1, activation, linear2, x):
     """``linear2(act(linear1(x)))``; for ReLU the activation rides in the first GEMM's epilogue (alo_linear_shortk when
-    d_model is 64 / 128 / 256 and the tensors are bf16, else hipBLASLt's RELU_BIAS via ``torch._addmm_activation``) instead
+    d_model is 64 / 128 / 256 and the tensors are bf16 / fp16, else hipBLASLt's RELU_BIAS via ``torch._addmm_activation``) instead
     of a separate pass over the (rows, d_ffn) intermediate."""
-    if activation is F.relu and alo_hip.ffn256_supported(x, linear1.weight, linear2.weight):
-        # d_model = 256, bf16: both layers in one kernel, the hidden activation never leaves the chip
+    if activation is F.relu and alo_hip.ffn256_supported(x, linear1.weight, linear2.weight, f16=True):
+        # d_model = 256, bf16 / fp16: both layers in one kernel, the hidden activation never leaves the chip
         return alo_hip.ffn256(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
     if activation is F.relu and linear1.bias is not None:
         h = alo_hip.linear_auto(x, linear1.weight, linear1.bias, relu=True)
@@ -436,14 +436,14 @@ class DeformableTransformer(nn.Module):
         """(``enc_output_norm(enc_output(memory with dropped rows zeroed))``, proposals (B, S, 4) float32): see
         :func:`encoder_output_proposals` for the semantics.  ``shapes``: [(h, w)] as Python ints.  ``fused``: inference, the
         element-wise part on alo_encoder_proposals_masked (or, where that does not apply, alo_encoder_proposals / alo_mask_rows)."""
-        if fused and alo_hip.encoder_proposals_masked_supported(memory_padding_mask, shapes, memory):
+        if fused and alo_hip.encoder_proposals_masked_supported(memory_padding_mask, shapes, memory, f16=True):
             proposals, keep, output_memory = alo_hip.encoder_proposals_masked(memory_padding_mask, shapes, memory)   # both in one launch
         else:
             if fused and alo_hip.encoder_proposals_supported(memory_padding_mask, shapes):
                 proposals, keep = alo_hip.encoder_proposals(memory_padding_mask, shapes)
             else:
                 proposals, keep = encoder_output_proposals(memory_padding_mask, shapes)
-            if fused and alo_hip.mask_rows_supported(memory, keep):
+            if fused and alo_hip.mask_rows_supported(memory, keep, f16=True):
                 output_memory = alo_hip.mask_rows(memory, keep)
             else:
                 output_memory = memory.masked_fill(~keep.unsqueeze(-1), 0.0)
@@ -478,7 +478,7 @@ class DeformableTransformer(nn.Module):
         enc_outputs_class = class_head(output_memory)
         enc_outputs_coord_unact = box_head(output_memory) + output_proposals
         topk = torch.topk(enc_outputs_class[..., 0], self.two_stage_num_proposals, dim=1)[1]
-        if fused and alo_hip.proposal_queries_supported(enc_outputs_coord_unact, topk, memory.dtype):
+        if fused and alo_hip.proposal_queries_supported(enc_outputs_coord_unact, topk, memory.dtype, f16=True):
             reference_points, embed = alo_hip.proposal_queries(enc_outputs_coord_unact, topk, memory.dtype, owner=self.pos_trans.weight)
         else:
             coords = torch.gather(enc_outputs_coord_unact, 1, topk.unsqueeze(-1).expand(-1, -1, 4)).detach()

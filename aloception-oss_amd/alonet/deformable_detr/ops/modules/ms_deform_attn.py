@@ -84,12 +84,12 @@ class MSDeformAttn(nn.Module):
 
     def head_major_supported(self, query, input_flatten):
         """Whether the inference path of the DETR-family shape applies (:meth:`head_major_inputs`, :meth:`forward_head_major`):
-        bf16, head dimension 32, L = P = 4, every projection with its bias."""
+        bf16 or fp16, head dimension 32, L = P = 4, every projection with its bias."""
         return (self.fused_prologue and query.is_cuda and self.d_model // self.n_heads == 32 and self.n_levels == 4
                 and self.n_points == 4 and self.value_proj.bias is not None and self.sampling_offsets.bias is not None
                 and self.attention_weights.bias is not None
-                and alo_hip.linear_shortk_supported(query, self.sampling_offsets.weight)
-                and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, self.n_heads))
+                and alo_hip.linear_shortk_supported(query, self.sampling_offsets.weight, f16=True)
+                and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, self.n_heads, f16=True))
 
     def head_major_inputs(self, query, input_flatten, input_padding_mask=None):
         """What the attention kernel reads, in two launches -> (value (N, M, S, 32) head-major with the padded rows zeroed,
@@ -141,11 +141,11 @@ class MSDeformAttn(nn.Module):
             any(t.requires_grad for t in (query, input_flatten, reference_points))
             or any(p.requires_grad for p in self.parameters()))
         fused = "is_tracing" not in kwargs and not needs_grad and self.fused_prologue and query.is_cuda
-        # inference: the four K = d_model linears go through the streaming MFMA kernel when it fits (bf16, d_model = 256)
+        # inference: the four K = d_model linears go through the streaming MFMA kernel when it fits (bf16 / fp16, d_model = 256)
         proj = (lambda lin, t: alo_hip.linear_auto(t, lin.weight, lin.bias)) if fused else (lambda lin, t: lin(t))
         D = self.d_model // M
         hm = (fused and D == 32 and L == 4 and P == 4 and self.value_proj.bias is not None
-              and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, M))
+              and alo_hip.value_proj_head_major_supported(input_flatten, self.value_proj.weight, M, f16=True))
         if hm and self.sampling_offsets.bias is not None and self.attention_weights.bias is not None:
             # inference, DETR-family shape: three launches (head_major_inputs), the attention kernel, the output projection
             value, both = self.head_major_inputs(query, input_flatten, input_padding_mask)

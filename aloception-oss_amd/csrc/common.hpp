@@ -165,17 +165,32 @@ __device__ __forceinline__ bf16x8_t as_bf16x8(const u32x4& v) {
     return x.b;
 }
 
-// GEMM epilogue on 8 bf16 outputs: + identity (same coordinates as y), then the activation, re-packed to bf16
-template <bool RELU>
-__device__ __forceinline__ u32x4 add_residual_bf16x8(const u32x4& v, const u32x4& rv) {
+// the fp16 MFMA's operand type, and the 32x32x16 MFMA of storage type T (same operand layout for both: 8 consecutive k per lane)
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+__device__ __forceinline__ f16x8_t as_f16x8(const u32x4& v) {
+    union { u32x4 u; f16x8_t h; } x;
+    x.u = v;
+    return x.h;
+}
+template <typename T>
+__device__ __forceinline__ f32x16 mfma_32x32x16(const u32x4& a, const u32x4& b, const f32x16& c) {
+    if constexpr (std::is_same<T, f16_t>::value) return __builtin_amdgcn_mfma_f32_32x32x16_f16(as_f16x8(a), as_f16x8(b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b), c, 0, 0, 0);
+}
+
+// GEMM epilogue on 8 outputs of storage type T (bf16 / fp16): + identity (same coordinates as y), then the activation, re-packed to T
+template <typename T, bool RELU>
+__device__ __forceinline__ u32x4 add_residual_x8(const u32x4& v, const u32x4& rv) {
     const unsigned a4[4] = {v.x, v.y, v.z, v.w}, r4[4] = {rv.x, rv.y, rv.z, rv.w};
     unsigned o4[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        float lo = __uint_as_float(a4[i] << 16) + __uint_as_float(r4[i] << 16);
-        float hi = __uint_as_float(a4[i] & 0xffff0000u) + __uint_as_float(r4[i] & 0xffff0000u);
+        float alo, ahi, rlo, rhi;
+        unpack2<T>(a4[i], alo, ahi);
+        unpack2<T>(r4[i], rlo, rhi);
+        float lo = alo + rlo, hi = ahi + rhi;
         if (RELU) { lo = relu_keep_nan(lo); hi = relu_keep_nan(hi); }
-        o4[i] = pack_bf16x2(lo, hi);
+        o4[i] = pack2<T>(lo, hi);
     }
     return u32x4{o4[0], o4[1], o4[2], o4[3]};
 }
@@ -322,7 +337,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// ---- 64 x 256 bf16 row tiles in LDS against weights streamed in MFMA fragment order (ffn256_kernel, encoder_block_kernel) ----------
+// ---- 64 x 256 row tiles (16-bit storage T: bf16, the default, or fp16) in LDS against weights streamed in MFMA fragment order (ffn256_kernel, encoder_block_kernel) ----------
 // A workgroup of 4 waves owns 64 rows; wave w computes 64 output columns of them as [2 row tiles][2 column tiles] of 32 x 32.  The
 // products are computed transposed (weights = the MFMA's row operand), so a lane owns ONE row of the tile and four consecutive
 // columns per accumulator quad.
@@ -335,7 +350,8 @@ constexpr int kTileBatches = 16 / kTileKB; // batches per 256-deep contraction
 // batch i+1 is requested before batch i is consumed (L2 latency ~ the MFMA time of one batch).  frag0 = this lane's 16 bytes of the
 // first fragment of column tile 0 (alo_pack_mfma_b order: a fragment is 64 lanes x 16 B contiguous), tile_stride = elements between
 // the two column tiles.  sched_barrier keeps the compiler from sinking the requests next to their first use.
-__device__ __forceinline__ void load_batch(u32x4 (&buf)[2][kTileKB], const bf16_t* frag0, size_t tile_stride, int batch) {
+template <typename T>
+__device__ __forceinline__ void load_batch(u32x4 (&buf)[2][kTileKB], const T* frag0, size_t tile_stride, int batch) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -344,6 +360,7 @@ __device__ __forceinline__ void load_batch(u32x4 (&buf)[2][kTileKB], const bf16_
     __builtin_amdgcn_sched_barrier(0);
 }
 // acc[row tile][column tile] += A (the LDS tile, k-steps kTileKB * batch ..) x the batch's weight fragments; nl = lane & 31, kg = lane >> 5
+template <typename T = bf16_t>
 __device__ __forceinline__ void mma_batch(f32x16 (&acc)[2][2], const unsigned char* a_lds, const u32x4 (&buf)[2][kTileKB], int batch,
                                           int nl, int kg) {
     u32x4 af[2][kTileKB];  // A fragments of the whole batch first: their LDS latency overlaps instead of preceding each MFMA group
@@ -356,31 +373,33 @@ __device__ __forceinline__ void mma_batch(f32x16 (&acc)[2][2], const unsigned ch
 #pragma unroll
     for (int j = 0; j < kTileKB; ++j) {
         const u32x4 a0 = af[0][j], a1 = af[1][j];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a0), acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a0), acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[0][j]), as_bf16x8(a1), acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[1][j]), as_bf16x8(a1), acc[1][1], 0, 0, 0);
+        acc[0][0] = mfma_32x32x16<T>(buf[0][j], a0, acc[0][0]);
+        acc[0][1] = mfma_32x32x16<T>(buf[1][j], a0, acc[0][1]);
+        acc[1][0] = mfma_32x32x16<T>(buf[0][j], a1, acc[1][0]);
+        acc[1][1] = mfma_32x32x16<T>(buf[1][j], a1, acc[1][1]);
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 // One whole 256-deep contraction of the LDS tile against weights w (fragment pointer of k-step 0), through bufa / bufb.  bufa already
 // holds batch 0; on return it holds batch 0 of `next` (same tile stride) when next != nullptr.
+template <typename T>
 __device__ __forceinline__ void mma_tile256(f32x16 (&acc)[2][2], const unsigned char* a_lds, u32x4 (&bufa)[2][kTileKB],
-                                            u32x4 (&bufb)[2][kTileKB], const bf16_t* w, size_t tile_stride, const bf16_t* next,
+                                            u32x4 (&bufb)[2][kTileKB], const T* w, size_t tile_stride, const T* next,
                                             size_t next_stride, int nl, int kg) {
 #pragma unroll
     for (int bt = 0; bt < kTileBatches; bt += 2) {
         load_batch(bufb, w, tile_stride, bt + 1);
-        mma_batch(acc, a_lds, bufa, bt, nl, kg);
+        mma_batch<T>(acc, a_lds, bufa, bt, nl, kg);
         if (bt + 2 < kTileBatches) load_batch(bufa, w, tile_stride, bt + 2);
         else if (next != nullptr) load_batch(bufa, next, next_stride, 0);
-        mma_batch(acc, a_lds, bufb, bt + 1, nl, kg);
+        mma_batch<T>(acc, a_lds, bufb, bt + 1, nl, kg);
     }
 }
 
-// The tile loader: rows [row0, row0 + 64) of a (M, 256) bf16 matrix, 8 pieces of 16 B per thread, rows contiguous across lanes.  Rows
+// The tile loader: rows [row0, row0 + 64) of a (M, 256) matrix of 16-bit elements, 8 pieces of 16 B per thread, rows contiguous across lanes.  Rows
 // past the end are read from the last row (never stored) so that all eight requests go out back to back, unpredicated.
-__device__ __forceinline__ void fetch_tile256(u32x4 (&v)[8], const bf16_t* X, long row0, long M, int tid) {
+template <typename T>
+__device__ __forceinline__ void fetch_tile256(u32x4 (&v)[8], const T* X, long row0, long M, int tid) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int p = tid + 256 * j;
@@ -396,8 +415,9 @@ __device__ __forceinline__ void park_tile256(unsigned char* lds, const u32x4 (&v
         *reinterpret_cast<u32x4*>(lds + (p >> 5) * kTileStride + (p & 31) * 16) = v[j];
     }
 }
-// this wave's accumulators (+ bias[column] when ADD_BIAS) -> bf16 -> the LDS tile, [row][column], as 8-byte writes
-template <bool ADD_BIAS, bool RELU>
+// this wave's accumulators (+ bias[column] when ADD_BIAS) -> T (one rounding to nearest even) -> the LDS tile, [row][column], as
+// 8-byte writes
+template <bool ADD_BIAS, bool RELU, typename T = bf16_t>
 __device__ __forceinline__ void stage_tile256(unsigned char* lds, const f32x16 (&acc)[2][2], const float* bias, int wave, int nl, int kg) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -411,7 +431,7 @@ __device__ __forceinline__ void stage_tile256(unsigned char* lds, const f32x16 (
                 float v0 = acc[a][t][4 * q], v1 = acc[a][t][4 * q + 1], v2 = acc[a][t][4 * q + 2], v3 = acc[a][t][4 * q + 3];
                 if constexpr (ADD_BIAS) { v0 += bb[0]; v1 += bb[1]; v2 += bb[2]; v3 += bb[3]; }
                 if constexpr (RELU) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                *reinterpret_cast<u32x2*>(lds + (32 * a + nl) * kTileStride + col * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+                *reinterpret_cast<u32x2*>(lds + (32 * a + nl) * kTileStride + col * 2) = u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
             }
         }
 }

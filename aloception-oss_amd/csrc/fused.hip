@@ -21,6 +21,11 @@ __device__ __forceinline__ void load4(const bf16_t* p, float (&v)[4]) {
     v[0] = __uint_as_float(x.x << 16); v[1] = __uint_as_float(x.x & 0xffff0000u);
     v[2] = __uint_as_float(x.y << 16); v[3] = __uint_as_float(x.y & 0xffff0000u);
 }
+__device__ __forceinline__ void load4(const f16_t* p, float (&v)[4]) {
+    const u32x2 x = *reinterpret_cast<const u32x2*>(p);
+    unpack2<f16_t>(x.x, v[0], v[1]);
+    unpack2<f16_t>(x.y, v[2], v[3]);
+}
 __device__ __forceinline__ void store4(float* p, const float (&v)[4]) {
     *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
 }
@@ -29,6 +34,20 @@ __device__ __forceinline__ void store4(bf16_t* p, const float (&v)[4]) {
     o.x = pack_bf16x2(v[0], v[1]);
     o.y = pack_bf16x2(v[2], v[3]);
     *reinterpret_cast<u32x2*>(p) = o;
+}
+
+__device__ __forceinline__ void store4(f16_t* p, const float (&v)[4]) {
+    u32x2 o;
+    o.x = pack_f16x2(v[0], v[1]);
+    o.y = pack_f16x2(v[2], v[3]);
+    *reinterpret_cast<u32x2*>(p) = o;
+}
+// v as the caller will read it back from a tensor of T (one rounding to nearest even for the 16-bit types)
+template <typename T>
+__device__ __forceinline__ float as_stored(float v) {
+    if constexpr (std::is_same<T, bf16_t>::value) return bf16_to_f32(f32_to_bf16(v));
+    else if constexpr (std::is_same<T, f16_t>::value) return f16_to_f32(f32_to_f16(v));
+    else return v;
 }
 
 // One wave per row; lane i holds elements [256*k + 4*i, +4) of the row for k < CHUNKS (coalesced 8-/16-byte accesses).
@@ -92,7 +111,7 @@ add_layernorm_kernel(const T* x, const T* res, const T* __restrict__ gamma, cons
                     // the sum is taken on the value the caller will see in `out` (rounded to T), as `out + pos` would be
                     if constexpr (sizeof(T) == 2) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) y[i] = bf16_to_f32(f32_to_bf16(y[i]));
+                        for (int i = 0; i < 4; ++i) y[i] = as_stored<T>(y[i]);
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) y[i] += p[i];
@@ -354,6 +373,8 @@ using namespace alo;
 
 extern "C" int alo_add_layernorm(const void* x, const void* residual, const void* gamma, const void* beta, void* out,
                                  const void* pos, void* out_pos, long rows, int C, float eps, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED,
+                "alo_add_layernorm: dtype %d (F32, BF16 and F16 are supported)", dtype);
     ALO_REQUIRE(x && gamma && beta && out, ALO_ERR_INVALID_ARGUMENT, "alo_add_layernorm: null pointer argument");
     ALO_REQUIRE((pos == nullptr) == (out_pos == nullptr), ALO_ERR_INVALID_ARGUMENT,
                 "alo_add_layernorm: pos and out_pos go together");
@@ -364,11 +385,13 @@ extern "C" int alo_add_layernorm(const void* x, const void* residual, const void
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == ALO_F32) return add_layernorm_t<float>(x, residual, gamma, beta, out, pos, out_pos, rows, C, eps, s);
     if (dtype == ALO_BF16) return add_layernorm_t<bf16_t>(x, residual, gamma, beta, out, pos, out_pos, rows, C, eps, s);
-    return fail(ALO_ERR_UNSUPPORTED, "alo_add_layernorm: dtype %d (F32 and BF16 are supported)", dtype);
+    return add_layernorm_t<f16_t>(x, residual, gamma, beta, out, pos, out_pos, rows, C, eps, s);
 }
 
 extern "C" int alo_bias_act(const void* x, const void* bias, const void* residual, void* y, long rows, int C, int relu,
                             int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED,
+                "alo_bias_act: dtype %d (F32, BF16 and F16 are supported)", dtype);
     ALO_REQUIRE(x && bias && y, ALO_ERR_INVALID_ARGUMENT, "alo_bias_act: null pointer argument");
     ALO_REQUIRE(rows > 0 && C > 0 && C % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_bias_act: rows must be positive and C a positive multiple of 4 (rows=%ld C=%d)", rows, C);
@@ -376,7 +399,7 @@ extern "C" int alo_bias_act(const void* x, const void* bias, const void* residua
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == ALO_F32) return bias_act_t<float>(x, bias, residual, y, rows, C, relu, s);
     if (dtype == ALO_BF16) return bias_act_t<bf16_t>(x, bias, residual, y, rows, C, relu, s);
-    return fail(ALO_ERR_UNSUPPORTED, "alo_bias_act: dtype %d (F32 and BF16 are supported)", dtype);
+    return bias_act_t<f16_t>(x, bias, residual, y, rows, C, relu, s);
 }
 
 extern "C" int alo_value_head_major(const void* value, const void* padding_mask, void* out, int N, int S, int M, int D,
@@ -437,12 +460,12 @@ extern "C" int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatia
                                  const float* dim_t, const void* level_embed, void* out, float* workspace, int B, int S,
                                  int L, int num_pos_feats, int normalize, int center, float scale, float eps, int dtype,
                                  void* stream) {
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_pos_sine_flat: dtype %d", dtype);
     ALO_REQUIRE(padding_mask && spatial_shapes && level_start_index && dim_t && out && workspace, ALO_ERR_INVALID_ARGUMENT,
                 "alo_pos_sine_flat: null pointer argument");
     ALO_REQUIRE(B > 0 && S > 0 && L > 0 && num_pos_feats > 0 && num_pos_feats % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_pos_sine_flat: sizes must be positive and num_pos_feats a multiple of 4 (B=%d S=%d L=%d F=%d)", B, S, L,
                 num_pos_feats);
-    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_pos_sine_flat: dtype %d", dtype);
     ALO_REQUIRE(aligned16(out, level_embed), ALO_ERR_INVALID_ARGUMENT, "alo_pos_sine_flat: out / level_embed must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     {
@@ -452,5 +475,6 @@ extern "C" int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatia
     long n4 = (long)B * S * (2 * num_pos_feats) / 4;
     void* args[] = {&workspace, &dim_t, &level_embed, &level_start_index, &out, &n4, &S, &L, &num_pos_feats};
     if (dtype == ALO_F32) return launch<pos_generate_kernel<float>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
+    if (dtype == ALO_F16) return launch<pos_generate_kernel<f16_t>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
     return launch<pos_generate_kernel<bf16_t>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
 }

@@ -1,9 +1,11 @@
-// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias), K in {64, 128, 256}, bf16 with fp32 accumulation: the short-K linear layers
+// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias), K in {64, 128, 256}, bf16 or fp16 with fp32 accumulation: the short-K linear layers
 // around the attention op — MSDeformAttn's value_proj / sampling_offsets / attention_weights / output_proj and the FFN's
 // first layer over the encoder's 177784 rows, the backbone's 1x1 convolutions with few input channels over NHWC rows.
 //
 // These products are memory bound (23 GFLOP against 182 MB at N = 256) and the library kernel PyTorch reaches streams them
 // at 2.8 TB/s.  This kernel is built around the stream instead of around the tile:
+// The kernels are templated on the 16-bit storage type T (bf16_t / f16_t): same tiles, same operand layout, v_mfma_f32_32x32x16_bf16
+// or _f16, one rounding to nearest even per stored result (the comments below say bf16 for both).
 //   * the WEIGHTS never move: each of a workgroup's 4 waves keeps its 64 output columns of W (64 x 256 bf16 = 128 VGPRs) in
 //     registers for the whole launch, already in the lane order v_mfma_f32_32x32x16_bf16 wants for its B operand;
 //   * X streams through: persistent workgroups walk 64-row tiles; a tile is fetched with fully coalesced 16-byte loads
@@ -31,10 +33,10 @@ struct GemmDims {
 // byte is set are written as zeros — `value.masked_fill(mask, 0)` and the re-layout the head-major attention kernel wants,
 // for free in the epilogue (a wave's 64 columns are two heads; 16 rows of a head are 1 KB contiguous).  R then carries the
 // (M,) uint8 mask (or NULL) and dm.S the rows per batch item.
-template <int kK, bool RELU, bool HAS_RES, bool HM>
+template <typename T, int kK, bool RELU, bool HAS_RES, bool HM>
 __global__ void __launch_bounds__(256, 2)
-linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, const bf16_t* __restrict__ bias,
-                     const bf16_t* __restrict__ R, bf16_t* __restrict__ Y, const GemmDims dm) {
+linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* __restrict__ bias,
+                     const T* __restrict__ R, T* __restrict__ Y, const GemmDims dm) {
     constexpr int kRowBytes = kK * 2 + 16;  // LDS row stride of the X tile: +16 B keeps the 16-byte fragment reads conflict-free
     constexpr int kSteps = kK / 16;         // MFMA k-steps per tile
     constexpr int kPieces = kK / 8;         // 16-byte pieces per row
@@ -59,12 +61,12 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
     if (has_cols) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const bf16_t* wr = W + (size_t)(col0 + 32 * t + nl) * kK + 8 * kg;
+            const T* wr = W + (size_t)(col0 + 32 * t + nl) * kK + 8 * kg;
 #pragma unroll
             for (int s = 0; s < kSteps; ++s) wreg[t][s] = *reinterpret_cast<const u32x4*>(wr + 16 * s);
         }
         const int r = lane & 15, t = (lane >> 4) & 1, k2 = lane >> 5;
-        bias_tab[lane] = bias != nullptr ? bf16_to_f32(bias[col0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * k2].bits) : 0.f;
+        bias_tab[lane] = bias != nullptr ? ld(&bias[col0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * k2]) : 0.f;
     }
 
     // ---- tile loader: kRows rows x 2K bytes in 16-byte pieces; thread -> (row, piece) keeps rows contiguous.  Rows past the
@@ -114,8 +116,8 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                 for (int s = 0; s < kSteps; ++s) {
                     // X fragment: X[tile row 32 half + nl][16 s + 8 kg .. + 8)
                     const u32x4 a = *reinterpret_cast<const u32x4*>(xbuf + (32 * half + nl) * kRowBytes + (16 * s + 8 * kg) * 2);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wreg[0][s]), as_bf16x8(a), acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wreg[1][s]), as_bf16x8(a), acc[1], 0, 0, 0);
+                    acc[0] = mfma_32x32x16<T>(wreg[0][s], a, acc[0]);
+                    acc[1] = mfma_32x32x16<T>(wreg[1][s], a, acc[1]);
                 }
                 // lane = tile row 32 half + nl; registers 4 q .. 4 q + 3 = columns 32 t + 8 q + 4 kg .. + 3 -> bf16 -> LDS [row][col]
 #pragma unroll
@@ -125,7 +127,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                         float v0 = acc[t][4 * q], v1 = acc[t][4 * q + 1], v2 = acc[t][4 * q + 2], v3 = acc[t][4 * q + 3];
                         if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
                         *reinterpret_cast<u32x2*>(obuf + (32 * half + nl) * kOutStride + (32 * t + 8 * q + 4 * kg) * 2) =
-                            u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+                            u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
                     }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -159,7 +161,7 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                 u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
                 if (grow < dm.M) {
                     if constexpr (HAS_RES) {  // + identity (same coordinates as y), then the activation
-                        v = add_residual_bf16x8<RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
+                        v = add_residual_x8<T, RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
                     }
                     *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
                 }
@@ -177,41 +179,61 @@ linear_shortk_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
 using namespace alo;
 
 namespace {
-template <int K, bool RELU, bool HAS_RES, bool HM = false>
+// storage type and K of a launch as ONE template argument (ALO_RELU_RES takes a single leading argument)
+template <typename T, int kK>
+struct ShortK {
+    using type = T;
+    static constexpr int K = kK;
+};
+
+template <class Cfg, bool RELU, bool HAS_RES, bool HM = false>
 int launch_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N,
                   hipStream_t stream, int S = 0, const RowGather& gather = row_gather()) {
     GemmDims dm;
     dm.M = M; dm.N = N; dm.tiles = (int)((M + kRows - 1) / kRows); dm.S = S; dm.g = gather;
+    constexpr int K = Cfg::K;
     const size_t lds = kRows * (K * 2 + 16) + 4 * kRows * kOutStride + 4 * 64 * sizeof(float);
     const int cols = (N + 255) / 256;
     int gx = 512 / cols;  // persistent: about two workgroups per CU in total
     if (gx > dm.tiles) gx = dm.tiles;
     if (gx < 1) gx = 1;
     void* args[] = {&x, &weight, &bias, &residual, &y, &dm};
-    return launch<linear_shortk_kernel<K, RELU, HAS_RES, HM>>(dim3(gx, cols), 256, lds, stream, "alo_linear_shortk", args);
+    return launch<linear_shortk_kernel<typename Cfg::type, K, RELU, HAS_RES, HM>>(dim3(gx, cols), 256, lds, stream, "alo_linear_shortk", args);
+}
+
+// K x relu x residual -> the launch, for storage type T
+template <typename T>
+int dispatch_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K, int relu,
+                    const RowGather& gather, hipStream_t stream) {
+    using K64 = ShortK<T, 64>;
+    using K128 = ShortK<T, 128>;
+    using K256 = ShortK<T, 256>;
+    if (K == 64) return ALO_RELU_RES(launch_shortk, K64, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    if (K == 128) return ALO_RELU_RES(launch_shortk, K128, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    if (K == 256) return ALO_RELU_RES(launch_shortk, K256, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    return fail(ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: the resident-weight kernel needs Cin in (64, 128, 256), got %d", K);
 }
 }  // namespace
 
 extern "C" int alo_linear_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M,
                                  int N, int K, int relu, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(x && weight && y, ALO_ERR_INVALID_ARGUMENT, "alo_linear_shortk: null pointer argument");
     ALO_REQUIRE(M > 0 && N > 0 && N % 64 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_linear_shortk: M must be positive and N a positive multiple of 64 (M=%ld N=%d)", M, N);
     ALO_REQUIRE(K == 64 || K == 128 || K == 256, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: K must be 64, 128 or 256, got %d", K);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: bf16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(x, weight, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_shortk: pointers must be 16-byte aligned");
-    return linear_shortk_gather(x, weight, bias, residual, y, M, N, K, relu, row_gather(), static_cast<hipStream_t>(stream));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == ALO_F16) return dispatch_shortk<f16_t>(x, weight, bias, residual, y, M, N, K, relu, row_gather(), st);
+    return dispatch_shortk<bf16_t>(x, weight, bias, residual, y, M, N, K, relu, row_gather(), st);
 }
 
 // 1x1 convolution with a spatial stride over an NHWC map, resident-weight flavour: the kept pixels are addressed by the tile
 // loader itself (no gathered copy of the input): alo_linear_shortk with the identity gather, alo_conv1x1_nhwc (gemm_packed.hip)
-// for unpacked weights.
+// for unpacked weights.  bf16 (the backbone's kernels are).
 int alo::linear_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K,
                               int relu, const RowGather& gather, hipStream_t stream) {
-    if (K == 64) return ALO_RELU_RES(launch_shortk, 64, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    if (K == 128) return ALO_RELU_RES(launch_shortk, 128, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    if (K == 256) return ALO_RELU_RES(launch_shortk, 256, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    return fail(ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: the resident-weight kernel needs Cin in (64, 128, 256), got %d", K);
+    return dispatch_shortk<bf16_t>(x, weight, bias, residual, y, M, N, K, relu, gather, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -221,7 +243,8 @@ int alo::linear_shortk_gather(const void* x, const void* weight, const void* bia
 // Run as two library GEMMs the (M, F) hidden activation makes a round trip through HBM (2 x 364 MB at M = 177784, F = 1024)
 // and the pair takes 316 us.  Here a workgroup owns 64 rows: it keeps them in LDS, produces the hidden activation 256
 // units at a time (each wave 64 of them) straight into LDS as bf16, and immediately contracts that chunk into its
-// 64 x 256 output accumulators (each wave 64 output columns), so the hidden tensor never exists in memory.  The weights
+// 64 x 256 output accumulators (each wave 64 output columns), so the hidden tensor never exists in memory (it is rounded to the
+// storage type, bf16 or fp16, on its way into LDS, as the two-launch path stores it).  The weights
 // (2 x 512 KB, L2 resident) stream through registers; x is read once, y written once, in whole lines.
 // ------------------------------------------------------------------------------------------------------------------
 namespace alo {
@@ -236,9 +259,10 @@ struct FfnDims {
     int tiles;  // ceil(M / 64)
 };
 
+template <typename T>
 __global__ void __launch_bounds__(256, 2)
-ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const bf16_t* __restrict__ B1,
-              const bf16_t* __restrict__ W2, const bf16_t* __restrict__ B2, bf16_t* __restrict__ Y, const FfnDims dm) {
+ffn256_kernel(const T* __restrict__ X, const T* __restrict__ W1, const T* __restrict__ B1,
+              const T* __restrict__ W2, const T* __restrict__ B2, T* __restrict__ Y, const FfnDims dm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const xs = smem;                            // x tile        [64][256] bf16
     unsigned char* const hs = smem + kFfnRows * kFfnStride;    // hidden chunk  [64][256] bf16, then the output staging
@@ -251,8 +275,8 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
     // conversion work on quads and leave as 8-byte LDS writes
     float* const b1s = reinterpret_cast<float*>(smem + 2 * kFfnRows * kFfnStride);
     float* const b2s = b1s + F;
-    for (int i = tid; i < F; i += 256) b1s[i] = B1 ? bf16_to_f32(B1[i].bits) : 0.f;
-    b2s[tid] = B2 ? bf16_to_f32(B2[tid].bits) : 0.f;
+    for (int i = tid; i < F; i += 256) b1s[i] = B1 ? ld(B1 + i) : 0.f;
+    b2s[tid] = B2 ? ld(B2 + tid) : 0.f;
 
     // the weights stream through two register buffers, a batch ahead of their use (load_batch / mma_batch of common.hpp)
     const int fs = F / 16;  // k steps per output-column tile of the packed W2
@@ -288,10 +312,10 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) acc1[a][t][i] = 0.f;
-            const bf16_t* w1p = w1_frag(r0);
-            const bf16_t* w2p = w2_frag(r0);
+            const T* w1p = w1_frag(r0);
+            const T* w2p = w2_frag(r0);
             mma_tile256(acc1, xs, bufa, bufb, w1p, (size_t)16 * 512, w2p, (size_t)fs * 512, nl, kg);
-            stage_tile256<true, true>(hs, acc1, b1s + r0, wave, nl, kg);
+            stage_tile256<true, true, T>(hs, acc1, b1s + r0, wave, nl, kg);
             __syncthreads();  // the whole 64 x 256 hidden chunk is in LDS
 
             // ---- phase 2: out[:, 64 wave ..] += h_chunk (64 x 256) W2[64 wave + ..][r0 .. r0 + 256)^T ------------------------
@@ -300,7 +324,7 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
         }
 
         // ---- epilogue: + b2 -> bf16 -> staging (the hidden-chunk buffer) -> whole-line stores ---------------------------------
-        stage_tile256<true, false>(hs, acc2, b2s, wave, nl, kg);
+        stage_tile256<true, false, T>(hs, acc2, b2s, wave, nl, kg);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -319,6 +343,7 @@ ffn256_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W1, const
 
 namespace alo {
 namespace {
+// (16-bit elements, moved as bits: bf16 and fp16 weights take the same kernel)
 // W (N, K) row-major -> fragments [N / 32][K / 16][64 lanes][8]: lane (kg, n) of fragment (t, s) holds W[32 t + n][16 s + 8 kg ..+8)
 __global__ void __launch_bounds__(256)
 pack_mfma_b_kernel(const bf16_t* __restrict__ W, bf16_t* __restrict__ P, int N, int K) {
@@ -335,10 +360,10 @@ pack_mfma_b_kernel(const bf16_t* __restrict__ W, bf16_t* __restrict__ P, int N, 
 }  // namespace alo
 
 extern "C" int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_pack_mfma_b: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(w && packed, ALO_ERR_INVALID_ARGUMENT, "alo_pack_mfma_b: null pointer argument");
     ALO_REQUIRE(N > 0 && K > 0 && N % 32 == 0 && K % 16 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_pack_mfma_b: N must be a multiple of 32 and K a multiple of 16 (N=%d K=%d)", N, K);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_pack_mfma_b: bf16 only (dtype %d)", dtype);
     long total = (long)N * K / 8;
     unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     void* args[] = {&w, &packed, &N, &K};
@@ -347,10 +372,10 @@ extern "C" int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dt
 
 extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y, long M,
                           int F, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_ffn256: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(x && w1 && w2 && y, ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: null pointer argument");
     ALO_REQUIRE(M > 0 && F > 0 && F % 256 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_ffn256: M must be positive and the hidden width a positive multiple of 256 (M=%ld F=%d)", M, F);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_ffn256: bf16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(x, w1, w2, y), ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: pointers must be 16-byte aligned");
     FfnDims dm;
     dm.M = M; dm.F = F; dm.tiles = (int)((M + kFfnRows - 1) / kFfnRows);
@@ -358,22 +383,28 @@ extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const v
     int gx = dm.tiles < 512 ? dm.tiles : 512;
     void* args[] = {&x, &w1, &b1, &w2, &b2, &y, &dm};
     if (lds > (size_t)kLdsLimit) return fail(ALO_ERR_UNSUPPORTED, "alo_ffn256: hidden width %d needs %zu bytes of LDS", F, lds);
-    return launch<ffn256_kernel>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
+    if (dtype == ALO_F16) return launch<ffn256_kernel<f16_t>>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
+    return launch<ffn256_kernel<bf16_t>>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
 }
 
 extern "C" int alo_value_proj_head_major(const void* x, const void* weight, const void* bias, const void* padding_mask,
                                          void* value_hm, int batch, int S, int heads, int K, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_value_proj_head_major: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(x && weight && value_hm, ALO_ERR_INVALID_ARGUMENT, "alo_value_proj_head_major: null pointer argument");
     ALO_REQUIRE(batch > 0 && S > 0 && heads > 0 && heads % 2 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_value_proj_head_major: batch, S must be positive and the head count even (batch=%d S=%d heads=%d)", batch, S,
                 heads);
     ALO_REQUIRE(K == 64 || K == 128 || K == 256, ALO_ERR_UNSUPPORTED, "alo_value_proj_head_major: K must be 64, 128 or 256, got %d", K);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_value_proj_head_major: bf16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(x, weight, value_hm), ALO_ERR_INVALID_ARGUMENT, "alo_value_proj_head_major: pointers must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long M = (long)batch * S;
     const int N = heads * 32;
-    if (K == 64) return launch_shortk<64, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-    if (K == 128) return launch_shortk<128, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-    return launch_shortk<256, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+    if (dtype == ALO_F16) {
+        if (K == 64) return launch_shortk<ShortK<f16_t, 64>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+        if (K == 128) return launch_shortk<ShortK<f16_t, 128>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+        return launch_shortk<ShortK<f16_t, 256>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+    }
+    if (K == 64) return launch_shortk<ShortK<bf16_t, 64>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+    if (K == 128) return launch_shortk<ShortK<bf16_t, 128>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+    return launch_shortk<ShortK<bf16_t, 256>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
 }

@@ -1,4 +1,5 @@
-// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias [+ R]), bf16 with fp32 accumulation, K a multiple of 256, N of 128: the backbone's 1x1
+// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias [+ R]), bf16 (or, for alo_linear_packed, fp16) with fp32 accumulation, K a multiple of
+// 256, N of 128: the backbone's 1x1
 // convolutions with many input channels (512 / 1024 / 2048; alonet/detr/backbone.py:19-47 + torchvision Bottleneck.conv1 / conv3 /
 // downsample) and the 1x1 input projections (alonet/deformable_detr/deformable_detr.py:75-84) over NHWC rows.
 //
@@ -14,16 +15,24 @@ namespace {
 
 constexpr int kOutStride = 64 * 2 + 16;   // LDS row stride of a wave's 64 x 64 output block
 
+// storage type and waves along the columns of a launch as ONE template argument (ALO_RELU_RES takes a single leading argument)
+template <typename T, int kWC>
+struct Packed {
+    using type = T;
+    static constexpr int WC = kWC;
+};
+
 struct PackedDims {
     long M;
     int N, K;
     RowGather g;
 };
 
-template <int WC, bool RELU, bool HAS_RES>
+// T: the 16-bit storage type (bf16_t / f16_t); the comments say bf16 for both
+template <typename T, int WC, bool RELU, bool HAS_RES>
 __global__ void __launch_bounds__(256, 2)
-linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, const bf16_t* __restrict__ bias,
-                     const bf16_t* __restrict__ R, bf16_t* __restrict__ Y, const PackedDims dm) {
+linear_packed_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const T* __restrict__ bias, const T* __restrict__ R,
+                     T* __restrict__ Y, const PackedDims dm) {
     constexpr int WR = 4 / WC;                 // waves along the rows
     constexpr int kRows = 64 * WR;             // rows of X per workgroup
     constexpr int KC = 256 / WR;               // columns of X staged at once
@@ -42,7 +51,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
     float* const bias_s = reinterpret_cast<float*>(smem + (kXBytes > kOBytes ? kXBytes : kOBytes));   // [WC][64], behind both uses of the buffer
     unsigned char* const obuf = smem + wave * (64 * kOutStride);              // aliases the X chunk after the K loop
 
-    bias_s[tid] = bias != nullptr ? bf16_to_f32(bias[blockIdx.y * (64 * WC) + (tid & (64 * WC - 1))].bits) : 0.f;
+    bias_s[tid] = bias != nullptr ? ld(&bias[blockIdx.y * (64 * WC) + (tid & (64 * WC - 1))]) : 0.f;
 
     auto fetch = [&](int chunk, u32x4 (&r)[kLoads]) {
 #pragma unroll
@@ -62,7 +71,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
     };
     const int ksteps = dm.K / 16;
     const size_t tile_stride = (size_t)ksteps * 512;   // elements between packed column tiles
-    const bf16_t* wfrag = Wp + (size_t)(col0 / 32) * tile_stride + lane * 8;
+    const T* wfrag = Wp + (size_t)(col0 / 32) * tile_stride + lane * 8;
     auto load_batch = [&](u32x4 (&buf)[2][KB], int gbatch) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -93,7 +102,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
-                    acc[a][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(buf[t][j]), as_bf16x8(af[a][j]), acc[a][t], 0, 0, 0);
+                    acc[a][t] = mfma_32x32x16<T>(buf[t][j], af[a][j], acc[a][t]);
         __builtin_amdgcn_sched_barrier(0);
     };
 
@@ -130,7 +139,7 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
                 float v0 = acc[a][t][4 * q] + bb[0], v1 = acc[a][t][4 * q + 1] + bb[1];
                 float v2 = acc[a][t][4 * q + 2] + bb[2], v3 = acc[a][t][4 * q + 3] + bb[3];
                 if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+                *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
             }
         }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -144,28 +153,31 @@ linear_packed_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp
         u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
         if (grow < dm.M) {
             if constexpr (HAS_RES) {   // + identity (same coordinates as y), then the activation
-                v = add_residual_bf16x8<RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
+                v = add_residual_x8<T, RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
             }
             *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
         }
     }
 }
 
-template <int WC, bool RELU, bool HAS_RES>
+template <class Cfg, bool RELU, bool HAS_RES>
 int launch_packed(const void* x, const void* w, const void* bias, const void* residual, void* y, const PackedDims& dm, hipStream_t stream) {
-    constexpr int WR = 4 / WC, kRows = 64 * WR, KC = 256 / WR;
+    constexpr int WC = Cfg::WC, WR = 4 / WC, kRows = 64 * WR, KC = 256 / WR;
     constexpr size_t xbytes = (size_t)kRows * (KC * 2 + 16), obytes = 4 * 64 * kOutStride;
     constexpr size_t lds = (xbytes > obytes ? xbytes : obytes) + 256 * sizeof(float);
     void* args[] = {&x, &w, &bias, &residual, &y, const_cast<PackedDims*>(&dm)};
     const dim3 grid((unsigned)((dm.M + kRows - 1) / kRows), (unsigned)(dm.N / (64 * WC)));
-    return launch<linear_packed_kernel<WC, RELU, HAS_RES>>(grid, 256, lds, stream, "alo_linear_packed", args);
+    return launch<linear_packed_kernel<typename Cfg::type, WC, RELU, HAS_RES>>(grid, 256, lds, stream, "alo_linear_packed", args);
 }
 
+template <typename T>
 int dispatch_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, const PackedDims& dm,
                     int relu, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dm.N % 256 == 0) return ALO_RELU_RES(launch_packed, 4, relu, residual, x, w_packed, bias, residual, y, dm, s);
-    return ALO_RELU_RES(launch_packed, 2, relu, residual, x, w_packed, bias, residual, y, dm, s);
+    using Wide = Packed<T, 4>;
+    using Square = Packed<T, 2>;
+    if (dm.N % 256 == 0) return ALO_RELU_RES(launch_packed, Wide, relu, residual, x, w_packed, bias, residual, y, dm, s);
+    return ALO_RELU_RES(launch_packed, Square, relu, residual, x, w_packed, bias, residual, y, dm, s);
 }
 
 }  // namespace
@@ -175,16 +187,17 @@ using namespace alo;
 
 extern "C" int alo_linear_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, long M,
                                  int N, int K, int relu, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_linear_packed: bf16 / fp16 only (dtype %d)", dtype);
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: null pointer argument");
     ALO_REQUIRE(M > 0 && N > 0 && K > 0, ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: sizes must be positive");
     ALO_REQUIRE(K % 256 == 0 && N % 128 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_linear_packed: K must be a multiple of 256 and N of 128 (K=%d N=%d)", K, N);
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_linear_packed: bf16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(x, w_packed, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: pointers must be 16-byte aligned");
     ALO_REQUIRE((M + 63) / 64 < (1L << 31), ALO_ERR_UNSUPPORTED, "alo_linear_packed: too many rows");
     PackedDims dm;
     dm.M = M; dm.N = N; dm.K = K; dm.g = row_gather();
-    return dispatch_packed(x, w_packed, bias, residual, y, dm, relu, stream);
+    if (dtype == ALO_F16) return dispatch_packed<f16_t>(x, w_packed, bias, residual, y, dm, relu, stream);
+    return dispatch_packed<bf16_t>(x, w_packed, bias, residual, y, dm, relu, stream);
 }
 
 extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual,
@@ -205,5 +218,5 @@ extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is
                 "alo_conv1x1_nhwc: packed weights need Cin %% 256 == 0 and Cout %% 128 == 0 (Cin=%d Cout=%d)", Cin, Cout);
     PackedDims dm;
     dm.M = M; dm.N = Cout; dm.K = Cin; dm.g = gather;
-    return dispatch_packed(x, weight, bias, residual, y, dm, relu, stream);
+    return dispatch_packed<bf16_t>(x, weight, bias, residual, y, dm, relu, stream);
 }

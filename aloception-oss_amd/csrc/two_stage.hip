@@ -147,7 +147,7 @@ constexpr int kEmbed = 512;   // 4 components x 128 features (num_pos_feats of :
 // One wave per query: lane t produces the 8 consecutive embedding values [8t, 8t + 8) = component t / 16, features
 // 8 (t % 16) ... + 7, i.e. four (sin, cos) pairs of frequencies k = 4 (t % 16) ... + 3.  All lanes read the same gathered row.
 // The angle is evaluated in double: near a zero crossing of sin / cos a float32 angle (error ~ 3e-7 at pi) is off by more than one
-// bf16 ulp of the (tiny) result.  2 400 waves x 12 double transcendentals per lane cost less than the launch.
+// bf16 / fp16 ulp of the (tiny) result.  2 400 waves x 12 double transcendentals per lane cost less than the launch.
 template <typename T>
 __global__ void __launch_bounds__(256)
 proposal_queries_kernel(const float* __restrict__ coords, const long long* __restrict__ topk, const float* __restrict__ dim_t,
@@ -235,8 +235,8 @@ extern "C" int alo_encoder_proposals(const unsigned char* mask_flatten, float* p
 extern "C" int alo_encoder_proposals_masked(const unsigned char* mask_flatten, float* proposals, unsigned char* keep, const void* memory,
                                             void* out, int B, int L, const int* level_shapes_host, int C, int dtype, void* stream) {
     const char* what = "alo_encoder_proposals_masked";
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "%s: dtype must be ALO_F32, ALO_BF16 or ALO_F16", what);
     ALO_REQUIRE(mask_flatten && proposals && keep && memory && out && level_shapes_host, ALO_ERR_INVALID_ARGUMENT, "%s: null pointer argument", what);
-    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "%s: dtype must be ALO_F32 or ALO_BF16", what);
     const long row_bytes = (long)C * (dtype == ALO_F32 ? 4 : 2);
     ALO_REQUIRE(C > 0 && row_bytes % 16 == 0, ALO_ERR_UNSUPPORTED, "%s: needs rows of a multiple of 16 bytes (C = %d)", what, C);
     ALO_REQUIRE(aligned16(proposals, memory, out), ALO_ERR_INVALID_ARGUMENT, "%s: proposals, memory and out must be 16-byte aligned", what);
@@ -249,8 +249,8 @@ extern "C" int alo_encoder_proposals_masked(const unsigned char* mask_flatten, f
 }
 
 extern "C" int alo_mask_rows(const void* memory, const unsigned char* keep, void* out, long rows, int C, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_mask_rows: dtype must be ALO_F32, ALO_BF16 or ALO_F16");
     ALO_REQUIRE(memory && keep && out, ALO_ERR_INVALID_ARGUMENT, "alo_mask_rows: null pointer argument");
-    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_mask_rows: dtype must be ALO_F32 or ALO_BF16");
     const long row_bytes = (long)C * (dtype == ALO_F32 ? 4 : 2);
     ALO_REQUIRE(rows > 0 && C > 0 && row_bytes % 16 == 0, ALO_ERR_UNSUPPORTED, "alo_mask_rows: needs rows >= 1 and rows of a multiple of 16 bytes (C = %d)", C);
     ALO_REQUIRE(aligned16(memory, out), ALO_ERR_INVALID_ARGUMENT, "alo_mask_rows: memory and out must be 16-byte aligned");
@@ -266,8 +266,8 @@ extern "C" int alo_mask_rows(const void* memory, const unsigned char* keep, void
 
 extern "C" int alo_proposal_queries(const float* coords_unact, const long long* topk, const float* dim_t, float* reference_points,
                                     void* embed, int B, int S, int K, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_proposal_queries: dtype must be ALO_F32, ALO_BF16 or ALO_F16");
     ALO_REQUIRE(coords_unact && topk && dim_t && reference_points && embed, ALO_ERR_INVALID_ARGUMENT, "alo_proposal_queries: null pointer argument");
-    ALO_REQUIRE(dtype == ALO_F32 || dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_proposal_queries: dtype must be ALO_F32 or ALO_BF16");
     ALO_REQUIRE(B > 0 && S > 0 && K > 0 && (long)B * K < (1l << 31) && (long)B * S < (1l << 31), ALO_ERR_INVALID_ARGUMENT,
                 "alo_proposal_queries: needs B, S, K >= 1 and B * K, B * S below 2^31");
     ALO_REQUIRE(aligned16(coords_unact, dim_t, reference_points, embed), ALO_ERR_INVALID_ARGUMENT, "alo_proposal_queries: coords_unact, dim_t, reference_points and embed must be 16-byte aligned");
@@ -278,6 +278,11 @@ extern "C" int alo_proposal_queries(const float* coords_unact, const long long* 
         float* e = static_cast<float*>(embed);
         void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};
         return launch<proposal_queries_kernel<float>>(blocks, 256, 0, s, "alo_proposal_queries", args);
+    }
+    if (dtype == ALO_F16) {
+        f16_t* e = static_cast<f16_t*>(embed);
+        void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};
+        return launch<proposal_queries_kernel<f16_t>>(blocks, 256, 0, s, "alo_proposal_queries", args);
     }
     bf16_t* e = static_cast<bf16_t*>(embed);
     void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};

@@ -46,7 +46,12 @@ typedef enum alo_status {
 
 /* Element types.  For MSDA the reference dispatches float and double (AT_DISPATCH_FLOATING_TYPES,
  * ms_deform_attn_cuda.cu:64,134); bf16 and fp16 storage with fp32 arithmetic are this library's addition.  ALO_F16 (IEEE binary16) is
- * accepted by the MSDA entry points and alo_value_head_major only; every other entry point that takes a dtype refuses it. */
+ * accepted by the MSDA entry points, alo_value_head_major and the transformer's layer kernels: alo_linear_shortk, alo_linear_packed,
+ * alo_ffn256, alo_value_proj_head_major, alo_pack_mfma_b, alo_add_layernorm, alo_bias_act, alo_pos_sine_flat (and the glue of
+ * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
+ * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
+ * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only.
+ * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
     ALO_F64 = 1,
@@ -307,7 +312,7 @@ int alo_corr_lookup_backward_coords(const float* const* levels, const float* coo
 /*
  * ---- Extensions: one-pass epilogues of the layers that call the attention op -------------------------------------------
  * The reference evaluates these as separate PyTorch ops; they have no counterpart in its native code.  Both read and
- * write every byte once; all pointers 16-byte aligned; dtype ALO_F32 or ALO_BF16 (arithmetic in fp32 either way).
+ * write every byte once; all pointers 16-byte aligned; dtype ALO_F32, ALO_BF16 or ALO_F16 (arithmetic in fp32 in all three).
  *
  * alo_add_layernorm: out = LayerNorm_C(x + residual) * gamma + beta, and optionally out_pos = out + pos
  *   replaces  `src = self.norm1(src + self.dropout1(src2))` (+ the next layer's `with_pos_embed(src, pos)`) at inference
@@ -327,10 +332,11 @@ int alo_bias_act(const void* x, const void* bias, const void* residual, void* y,
 
 /*
  * alo_linear_shortk: y (M, N) = act(x (M, K) @ weight (N, K)^T + bias [+ residual (M, N)]), K in {64, 128, 256}, N % 64 == 0,
- * bf16 with fp32 accumulation, act = ReLU when relu != 0 (residual: the bottleneck's identity, added before the activation).  The short-K nn.Linear layers next to the op — value_proj, sampling_offsets,
+ * bf16 or fp16 (ALO_BF16 / ALO_F16: every operand of that type) with fp32 accumulation, act = ReLU when relu != 0 (residual: the
+ * bottleneck's identity, added before the activation to x W^T + b rounded to the storage type).  The short-K nn.Linear layers next to the op — value_proj, sampling_offsets,
  * attention_weights, output_proj of MSDeformAttn (ms_deform_attn.py:56-59), the FFN's first layer — and the backbone's 1x1
  * convolutions with K input channels over NHWC rows: memory-bound products; the weights stay in registers, x streams
- * through once per 256 output columns, y is written in whole lines (v_mfma_f32_32x32x16_bf16).  bias (N,) bf16 or NULL.
+ * through once per 256 output columns, y is written in whole lines (v_mfma_f32_32x32x16_bf16 / _f16).  bias (N,) of `dtype` or NULL.
  * 16-byte aligned pointers.
  */
 int alo_linear_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N,
@@ -339,18 +345,20 @@ int alo_linear_shortk(const void* x, const void* weight, const void* bias, const
 /*
  * alo_value_proj_head_major: MSDeformAttn's value path in one kernel (ms_deform_attn.py:111-114): value_proj (a short-K
  * linear layer, as alo_linear_shortk), `masked_fill(input_padding_mask, 0)` and the head-major layout of
- * alo_value_head_major, all in the GEMM's epilogue.  x (batch * S, K) bf16, weight (heads * 32, K), bias (heads * 32,) or
+ * alo_value_head_major, all in the GEMM's epilogue.  x (batch * S, K) bf16 or fp16, weight (heads * 32, K), bias (heads * 32,) or
  * NULL, padding_mask (batch * S,) uint8 or NULL -> value_hm (batch, heads, S, 32).  Head dimension 32, even head count.
  */
 int alo_value_proj_head_major(const void* x, const void* weight, const void* bias, const void* padding_mask, void* value_hm,
                               int batch, int S, int heads, int K, int dtype, void* stream);
 
 /*
- * alo_ffn256: y (M, 256) = relu(x (M, 256) @ w1 (F, 256)^T + b1) @ w2 (256, F)^T + b2, bf16 with fp32 accumulation,
+ * alo_ffn256: y (M, 256) = relu(x (M, 256) @ w1 (F, 256)^T + b1) @ w2 (256, F)^T + b2, bf16 or fp16 with fp32 accumulation (the
+ * hidden activation is rounded to the storage type before the second product, as two launches would store it),
  * F % 256 == 0: `linear2(relu(linear1(x)))` of the transformer layers (deformable_transformer.py:336-338,470-478) in one
  * kernel — the (M, F) hidden activation lives 64 rows at a time in LDS and never reaches memory.  b1 / b2 may be NULL.
  * w1 and w2 are PACKED weights: alo_pack_mfma_b(w (N, K) row-major) -> [N / 32][K / 16][64][8], the lane order of the MFMA
- * B operand, so that the weight stream is read in whole lines (pack once per weight update).
+ * B operand, so that the weight stream is read in whole lines (pack once per weight update).  alo_pack_mfma_b moves 16-bit
+ * elements: ALO_BF16 and ALO_F16 take the same kernel.
  */
 int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dtype, void* stream);
 int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y, long M, int F,
@@ -358,7 +366,7 @@ int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, co
 
 /*
  * alo_linear_packed: y (M, N) = act(x (M, K) @ w (N, K)^T + bias [+ residual]) for the long-K 1x1 convolutions of the backbone and the
- * 1x1 input projections over NHWC rows (alonet/detr/backbone.py:19-47, deformable_detr.py:75-84): bf16, fp32 accumulation,
+ * 1x1 input projections over NHWC rows (alonet/detr/backbone.py:19-47, deformable_detr.py:75-84): bf16 or fp16, fp32 accumulation,
  * K % 256 == 0, N % 128 == 0.  w_packed = alo_pack_mfma_b(w).  residual (M, N) or NULL is added before the activation.
  */
 int alo_linear_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, long M, int N, int K,
@@ -369,7 +377,7 @@ int alo_linear_packed(const void* x, const void* w_packed, const void* bias, con
  * `downsample` convolutions of the bottlenecks (alonet/detr/backbone.py:84-92; torchvision Bottleneck) without a gathered copy of the
  * kept pixels — the tile loader of alo_linear_shortk (weight (Cout, Cin) row-major, weight_is_packed = 0, Cin in {64, 128, 256}) or
  * alo_linear_packed (weight = alo_pack_mfma_b(w), weight_is_packed = 1, Cin % 256 == 0, Cout % 128 == 0) addresses pixel
- * (n, stride * yo, stride * xo) itself.  Ho = (H - 1) / stride + 1.  residual (N, Ho, Wo, Cout) or NULL.
+ * (n, stride * yo, stride * xo) itself.  Ho = (H - 1) / stride + 1.  residual (N, Ho, Wo, Cout) or NULL.  bf16 only.
  */
 int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual, void* y, int N,
                      int H, int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream);
@@ -466,7 +474,8 @@ int alo_panoptic_onehot(const float* mask_logits, long long* onehot, int B, int 
  * `pos.flatten(2).transpose(1, 2) + level_embed[lvl]` / cat of DeformableTransformer.forward compute with ~15 PyTorch
  * kernels per level (alonet/transformers/position_encoding.py:29-72, deformable_transformer.py:562-577).
  *   padding_mask (B, S) uint8/bool (1 on padding), dim_t (F,) fp32 = temperature ** (2 * (i // 2) / F),
- *   level_embed (L, 2F) of `dtype` or NULL, out (B, S, 2F) of `dtype`, workspace B * S * 2 floats.  F % 4 == 0.
+ *   level_embed (L, 2F) of `dtype` or NULL, out (B, S, 2F) of `dtype` (ALO_F32, ALO_BF16 or ALO_F16), workspace B * S * 2 floats.
+ *   F % 4 == 0.
  */
 int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatial_shapes, const int32_t* level_start_index,
                       const float* dim_t, const void* level_embed, void* out, float* workspace, int B, int S, int L,

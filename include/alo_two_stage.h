@@ -39,7 +39,7 @@ int alo_encoder_proposals(const unsigned char* mask_flatten, float* proposals, u
 
 /*
  * output_memory = keep ? memory : 0 (the two masked_fill passes of :173-175 in one).
- *   memory, out   (rows, C) in `dtype` (ALO_F32 or ALO_BF16), 16-byte aligned, C * element size a multiple of 16 (C % 8 == 0
+ *   memory, out   (rows, C) in `dtype` (ALO_F32, ALO_BF16 or ALO_F16: bits are copied), 16-byte aligned, C * element size a multiple of 16 (C % 8 == 0
  *                 covers both types); `out` is fully overwritten and must not alias `memory`
  *   keep          (rows,) uint8
  * A dropped row is written as zeros without being read (NaN / inf there become 0); a kept row is copied bit for bit.
@@ -60,10 +60,10 @@ int alo_encoder_proposals_masked(const unsigned char* mask_flatten, float* propo
  *   dim_t             (64,) float32, 16-byte aligned: the frequency of each (sin, cos) pair, 10000^(k / 64) = 10000^(2 k / 128),
  *                     handed in so that kernel and torch formulation divide by the very same float32 values
  *   reference_points  (B, K, 4) float32: sigmoid of the gathered rows
- *   embed             (B, K, 512) in `dtype` (ALO_F32 or ALO_BF16), 16-byte aligned: for component c and i in [0, 128),
+ *   embed             (B, K, 512) in `dtype` (ALO_F32, ALO_BF16 or ALO_F16), 16-byte aligned: for component c and i in [0, 128),
  *                     embed[c * 128 + i] = sin(a) for even i, cos(a) for odd i, a = sigmoid(coord_c) * 2 pi / dim_t[floor(i / 2)].
  *                     Sigmoid and angle are evaluated in double and rounded once: near a zero crossing of sin / cos a float32
- *                     angle would be off by more than a bf16 ulp of the result
+ *                     angle would be off by more than a bf16 / fp16 ulp of the result
  */
 int alo_proposal_queries(const float* coords_unact, const long long* topk, const float* dim_t, float* reference_points, void* embed,
                          int B, int S, int K, int dtype, void* stream);

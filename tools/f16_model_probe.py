@@ -3,10 +3,12 @@
 
     python tools/f16_model_probe.py [--batch 8] [--steps 10] [--warmup 3] [--dtypes f16,bf16]
 
-In fp16 only the attention op runs on this library's kernels: every other layer kernel is gated on fp32 / bf16 and leaves fp16
-to the stock ops, so the frame rate is below the bf16 headline by construction.  The launch tags (``alo_hip.LaunchTimer``) say
-which library kernels ran; what is absent from the fp16 list next to the bf16 one is what runs on stock ops, and the per-step
-gap is the case for giving those layers fp16 next.  Prints one JSON line per dtype.
+In fp16 the transformer runs on this library's kernels as it does in bf16 (attention op, short-K linears, the one-kernel FFN,
+residual + LayerNorm, positional encoding), except that its encoder takes the separate launches instead of the bf16-only fused
+encoder block; the backbone and the input projections are gated on fp32 / bf16 and leave fp16 to the stock ops, so the frame rate
+stays below the bf16 headline by construction.  The launch tags (``alo_hip.LaunchTimer``) say which library kernels ran; what is
+absent from the fp16 list next to the bf16 one is what runs on stock ops or on separate launches, and the per-step gap is the case
+for giving the backbone kernels and the encoder block fp16 next.  Prints one JSON line per dtype.
 """
 import argparse
 import json
