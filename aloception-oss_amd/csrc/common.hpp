@@ -1,4 +1,5 @@
 // Shared helpers for the gfx950 kernels: error reporting, the launch path, buffer-resource loads, element conversion, MFMA operands.
+// What the GEMM-shaped kernels share around the MFMA (tiles, epilogues, weight streaming) is in mfma_tile.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,6 +68,21 @@ __device__ __forceinline__ unsigned xcd_contiguous_block(unsigned bid, unsigned 
     const unsigned xcd = bid % kNumXcd, k = bid / kNumXcd;
     const unsigned start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return start + k;
+}
+
+// Persistent workgroups over `ntiles` tiles, one CONTIGUOUS eighth of the tiles per XCD: XCD x (workgroup ids = x mod 8) walks tiles
+// [x * per_xcd, (x + 1) * per_xcd), so neighbouring tiles meet in the same L2.  A workgroup takes tiles first, first + step, .. below
+// end; xcd_grid is the matching grid size.
+static_assert(kNumXcd == 8, "the tile ranges below shift by 3");
+struct TileRange { int first, end, step; };
+__device__ __forceinline__ TileRange xcd_tile_range(int ntiles) {
+    const int per_xcd = (ntiles + 7) >> 3, xcd = blockIdx.x & 7;
+    const int end = (xcd + 1) * per_xcd < ntiles ? (xcd + 1) * per_xcd : ntiles;
+    return {(int)(xcd * per_xcd + (blockIdx.x >> 3)), end, (int)(gridDim.x >> 3)};
+}
+inline unsigned xcd_grid(int ntiles, int max_per_xcd) {
+    const int per_xcd = (ntiles + 7) / 8;
+    return 8u * (unsigned)(per_xcd < max_per_xcd ? per_xcd : max_per_xcd);
 }
 
 // msda_bwd_wide.hip: the 16x16-block backward.  msda_wide_plan is pure host logic: whether the path takes a launch (fp32 / bf16 values,
@@ -155,6 +171,20 @@ template <typename T>
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {
     if constexpr (std::is_same<T, f16_t>::value) return pack_f16x2(lo, hi);
     else return pack_bf16x2(lo, hi);
+}
+// four consecutive elements = one 8-byte access
+template <typename T>
+__device__ __forceinline__ void unpack4(const u32x2& x, float (&v)[4]) {
+    unpack2<T>(x.x, v[0], v[1]);
+    unpack2<T>(x.y, v[2], v[3]);
+}
+template <typename T>
+__device__ __forceinline__ u32x2 pack4(const float (&v)[4]) { return u32x2{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])}; }
+
+// Host side: f(bf16_t{}) or f(f16_t{}) for a dtype the caller has checked to be ALO_BF16 or ALO_F16 (f: a generic lambda, decltype(t))
+template <typename F>
+inline int with_storage_type(int dtype, F&& f) {
+    return dtype == ALO_F16 ? f(f16_t{}) : f(bf16_t{});
 }
 
 // the bf16 MFMA's operand type over the four registers a 16-byte load fills
@@ -330,110 +360,16 @@ __device__ __forceinline__ void store_vec(T* p, const CT (&v)[VEC]) {
     }
 }
 
+// A wave hands LDS data from some of its lanes to others.  LDS operations of one wave execute in order, so nothing has to be waited
+// for: the compiler alone must not move the reads above the writes.  The fence builtins at "wavefront" scope (wave_lds_fence of
+// mfma_tile.hpp) are NOT that: they lower to s_waitcnt vmcnt(0) lgkmcnt(0), which also waits for the wave's outstanding global traffic.
+#define ALO_WAVE_LDS_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
+
 // Sum over the 64 lanes of a wave, every lane gets it (the LayerNorm kernels: one wave per row).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// ---- 64 x 256 row tiles (16-bit storage T: bf16, the default, or fp16) in LDS against weights streamed in MFMA fragment order (ffn256_kernel, encoder_block_kernel) ----------
-// A workgroup of 4 waves owns 64 rows; wave w computes 64 output columns of them as [2 row tiles][2 column tiles] of 32 x 32.  The
-// products are computed transposed (weights = the MFMA's row operand), so a lane owns ONE row of the tile and four consecutive
-// columns per accumulator quad.
-constexpr int kTileRows = 64;
-constexpr int kTileStride = 256 * 2 + 16;  // LDS row stride: +16 B keeps the 16-byte fragment reads conflict-free
-constexpr int kTileKB = 2;                 // k-steps per weight batch
-constexpr int kTileBatches = 16 / kTileKB; // batches per 256-deep contraction
-
-// Weight fragments arrive in batches of kTileKB k-steps (2 column tiles x kTileKB x 16 B per lane) through two register buffers:
-// batch i+1 is requested before batch i is consumed (L2 latency ~ the MFMA time of one batch).  frag0 = this lane's 16 bytes of the
-// first fragment of column tile 0 (alo_pack_mfma_b order: a fragment is 64 lanes x 16 B contiguous), tile_stride = elements between
-// the two column tiles.  sched_barrier keeps the compiler from sinking the requests next to their first use.
-template <typename T>
-__device__ __forceinline__ void load_batch(u32x4 (&buf)[2][kTileKB], const T* frag0, size_t tile_stride, int batch) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < kTileKB; ++j)
-            buf[t][j] = *reinterpret_cast<const u32x4*>(frag0 + t * tile_stride + (size_t)(kTileKB * batch + j) * 512);
-    __builtin_amdgcn_sched_barrier(0);
-}
-// acc[row tile][column tile] += A (the LDS tile, k-steps kTileKB * batch ..) x the batch's weight fragments; nl = lane & 31, kg = lane >> 5
-template <typename T = bf16_t>
-__device__ __forceinline__ void mma_batch(f32x16 (&acc)[2][2], const unsigned char* a_lds, const u32x4 (&buf)[2][kTileKB], int batch,
-                                          int nl, int kg) {
-    u32x4 af[2][kTileKB];  // A fragments of the whole batch first: their LDS latency overlaps instead of preceding each MFMA group
-#pragma unroll
-    for (int j = 0; j < kTileKB; ++j) {
-        const int s = kTileKB * batch + j;
-        af[0][j] = *reinterpret_cast<const u32x4*>(a_lds + nl * kTileStride + (16 * s + 8 * kg) * 2);
-        af[1][j] = *reinterpret_cast<const u32x4*>(a_lds + (32 + nl) * kTileStride + (16 * s + 8 * kg) * 2);
-    }
-#pragma unroll
-    for (int j = 0; j < kTileKB; ++j) {
-        const u32x4 a0 = af[0][j], a1 = af[1][j];
-        acc[0][0] = mfma_32x32x16<T>(buf[0][j], a0, acc[0][0]);
-        acc[0][1] = mfma_32x32x16<T>(buf[1][j], a0, acc[0][1]);
-        acc[1][0] = mfma_32x32x16<T>(buf[0][j], a1, acc[1][0]);
-        acc[1][1] = mfma_32x32x16<T>(buf[1][j], a1, acc[1][1]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-}
-// One whole 256-deep contraction of the LDS tile against weights w (fragment pointer of k-step 0), through bufa / bufb.  bufa already
-// holds batch 0; on return it holds batch 0 of `next` (same tile stride) when next != nullptr.
-template <typename T>
-__device__ __forceinline__ void mma_tile256(f32x16 (&acc)[2][2], const unsigned char* a_lds, u32x4 (&bufa)[2][kTileKB],
-                                            u32x4 (&bufb)[2][kTileKB], const T* w, size_t tile_stride, const T* next,
-                                            size_t next_stride, int nl, int kg) {
-#pragma unroll
-    for (int bt = 0; bt < kTileBatches; bt += 2) {
-        load_batch(bufb, w, tile_stride, bt + 1);
-        mma_batch<T>(acc, a_lds, bufa, bt, nl, kg);
-        if (bt + 2 < kTileBatches) load_batch(bufa, w, tile_stride, bt + 2);
-        else if (next != nullptr) load_batch(bufa, next, next_stride, 0);
-        mma_batch<T>(acc, a_lds, bufb, bt + 1, nl, kg);
-    }
-}
-
-// The tile loader: rows [row0, row0 + 64) of a (M, 256) matrix of 16-bit elements, 8 pieces of 16 B per thread, rows contiguous across lanes.  Rows
-// past the end are read from the last row (never stored) so that all eight requests go out back to back, unpredicated.
-template <typename T>
-__device__ __forceinline__ void fetch_tile256(u32x4 (&v)[8], const T* X, long row0, long M, int tid) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int p = tid + 256 * j;
-        long row = row0 + (p >> 5);
-        row = row < M ? row : M - 1;
-        v[j] = *reinterpret_cast<const u32x4*>(X + row * 256 + (p & 31) * 8);
-    }
-}
-__device__ __forceinline__ void park_tile256(unsigned char* lds, const u32x4 (&v)[8], int tid) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int p = tid + 256 * j;
-        *reinterpret_cast<u32x4*>(lds + (p >> 5) * kTileStride + (p & 31) * 16) = v[j];
-    }
-}
-// this wave's accumulators (+ bias[column] when ADD_BIAS) -> T (one rounding to nearest even) -> the LDS tile, [row][column], as
-// 8-byte writes
-template <bool ADD_BIAS, bool RELU, typename T = bf16_t>
-__device__ __forceinline__ void stage_tile256(unsigned char* lds, const f32x16 (&acc)[2][2], const float* bias, int wave, int nl, int kg) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int col = 64 * wave + 32 * t + 8 * q + 4 * kg;  // registers 4 q .. 4 q + 3 = columns col .. col + 3
-            f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (ADD_BIAS) bb = *reinterpret_cast<const f32x4*>(bias + col);
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                float v0 = acc[a][t][4 * q], v1 = acc[a][t][4 * q + 1], v2 = acc[a][t][4 * q + 2], v3 = acc[a][t][4 * q + 3];
-                if constexpr (ADD_BIAS) { v0 += bb[0]; v1 += bb[1]; v2 += bb[2]; v3 += bb[3]; }
-                if constexpr (RELU) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                *reinterpret_cast<u32x2*>(lds + (32 * a + nl) * kTileStride + col * 2) = u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
-            }
-        }
 }
 
 }  // namespace alo

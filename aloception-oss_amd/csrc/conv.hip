@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace alo {
 namespace {
@@ -90,12 +90,10 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
         bias_s[tid] = (bias != nullptr && c < dm.Cout && (!KSPLIT || tid < 64)) ? bf16_to_f32(bias[c].bits) : 0.f;
     }
 
-    // Persistent workgroups.  Workgroup ids go round-robin over the 8 XCDs, so XCD x (ids = x mod 8) takes the x-th eighth of
-    // the tiles: neighbouring tiles — which share two of their three halo rows — meet in the same L2.
-    const int ntiles = dm.tiles_per_image * dm.N;
-    const int per_xcd = (ntiles + 7) >> 3, xcd = blockIdx.x & 7, lanes_per_xcd = gridDim.x >> 3;
-    const int tile_end = (xcd + 1) * per_xcd < ntiles ? (xcd + 1) * per_xcd : ntiles;
-    int tile = xcd * per_xcd + (blockIdx.x >> 3);
+    // persistent workgroups, one contiguous eighth of the tiles per XCD: neighbouring tiles share two of their three halo rows
+    const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
+    const int tile_end = range.end, lanes_per_xcd = range.step;
+    int tile = range.first;
     if (tile >= tile_end) return;
 
     const int ksteps_per_tap = dm.Cin / 16;
@@ -142,6 +140,8 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
             tapmask[a] = m;
         }
 
+        // zeroing, quad epilogue and row store stay this kernel's own: with zero_acc / stage_quads (mfma_tile.hpp) in their place the
+        // <1, false> instantiation (256 registers, 36 bytes of scratch) gains an instruction or 260 bytes of scratch
         f32x16 acc[2][2];  // [row tile][column tile]
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -173,8 +173,8 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
                     if (!ok1) a1 = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
                     for (int b = 0; b < 2; ++b) {
-                        acc[0][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(f.v[j][b]), as_bf16x8(a0), acc[0][b], 0, 0, 0);
-                        acc[1][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(f.v[j][b]), as_bf16x8(a1), acc[1][b], 0, 0, 0);
+                        acc[0][b] = mfma_32x32x16<bf16_t>(f.v[j][b], a0, acc[0][b]);
+                        acc[1][b] = mfma_32x32x16<bf16_t>(f.v[j][b], a1, acc[1][b]);
                     }
                 }
             };
@@ -260,9 +260,7 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
                         *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
                     }
                 }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             // 64 pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction
 #pragma unroll
             for (int pass = 0; pass < 8; ++pass) {
@@ -306,10 +304,9 @@ conv3x3_c64_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, 
     if (tid < 64) bias_s[tid] = bias != nullptr ? bf16_to_f32(bias[tid].bits) : 0.f;   // read after the tile's barriers
 
     // persistent workgroups, one contiguous eighth of the tiles per XCD (see conv3x3_kernel)
-    const int ntiles = dm.tiles_per_image * dm.N;
-    const int per_xcd = (ntiles + 7) >> 3, xcd = blockIdx.x & 7, lanes_per_xcd = gridDim.x >> 3;
-    const int tile_end = (xcd + 1) * per_xcd < ntiles ? (xcd + 1) * per_xcd : ntiles;
-    int tile = xcd * per_xcd + (blockIdx.x >> 3);
+    const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
+    const int tile_end = range.end, lanes_per_xcd = range.step;
+    int tile = range.first;
     if (tile >= tile_end) return;
 
     // batch half + 2 t of conv3x3_kernel's numbering: tap t, k-steps 2 half and 2 half + 1 of the tap's four; column tiles 0 and 1
@@ -379,10 +376,7 @@ conv3x3_c64_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, 
         if (tile + lanes_per_xcd < tile_end) load_halo(tile + lanes_per_xcd);
 
         f32x16 acc[2];   // [column tile]
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+        zero_acc(acc);
         // A fragments of tap t + 1 are read before the MFMAs of tap t: their LDS latency hides behind four MFMAs
         u32x4 a[2][2];
 #pragma unroll
@@ -400,7 +394,7 @@ conv3x3_c64_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, 
                 const u32x4 av = ok ? a[t & 1][j] : u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wreg[t][j][b]), as_bf16x8(av), acc[b], 0, 0, 0);
+                    acc[b] = mfma_32x32x16<bf16_t>(wreg[t][j][b], av, acc[b]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -419,21 +413,11 @@ conv3x3_c64_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, 
             for (int b = 0; b < 2; ++b) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[b][r] += red[(b * 16 + r) * 64];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int c = 32 * b + 8 * q + 4 * kg;
-                    const f32x4 bb = *reinterpret_cast<const f32x4*>(bias_s + c);
-                    float v0 = acc[b][4 * q] + bb[0], v1 = acc[b][4 * q + 1] + bb[1];
-                    float v2 = acc[b][4 * q + 2] + bb[2], v3 = acc[b][4 * q + 3] + bb[3];
-                    if (dm.relu) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                    *reinterpret_cast<u32x2*>(obuf + (32 * ph + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
-                }
+                stage_quads_tile<bf16_t, true>(obuf, kOutStride, acc, bias_s, dm.relu, 32 * ph + nl, 0, kg, b);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // this wave's 32 pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction
+            wave_lds_fence();
+            // this wave's 32 pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction (not store_rows: see there)
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
                 const int row = 32 * ph + pass * 8 + (lane >> 3);
@@ -487,17 +471,14 @@ int launch_conv(const void* x, const void* w, const void* bias, void* y, void* p
     constexpr int lds = Geo<STRIDE>::kLds + kThreads * 4;
     void* args[] = {&x, &w, &bias, &y, &partial, const_cast<ConvDims*>(&dm)};
     const unsigned gy = KSPLIT ? dm.Cout / 64 : (dm.Cout + 127) / 128;
-    const int ntiles = dm.tiles_per_image * dm.N;
-    int per_xcd = (ntiles + 7) / 8;
-    if (per_xcd > 128) per_xcd = 128;   // 32 CUs per XCD x up to 4 resident workgroups
-    return launch<conv3x3_kernel<STRIDE, KSPLIT>>(dim3((unsigned)(8 * per_xcd), gy, (unsigned)dm.zsplit), kThreads, lds, stream, "alo_conv3x3_nhwc", args);
+    const unsigned gx = xcd_grid(dm.tiles_per_image * dm.N, 128);   // 32 CUs per XCD x up to 4 resident workgroups
+    return launch<conv3x3_kernel<STRIDE, KSPLIT>>(dim3(gx, gy, (unsigned)dm.zsplit), kThreads, lds, stream, "alo_conv3x3_nhwc", args);
 }
 
 int launch_conv_c64(const void* x, const void* w, const void* bias, void* y, const ConvDims& dm, hipStream_t stream) {
     void* args[] = {&x, &w, &bias, &y, const_cast<ConvDims*>(&dm)};
-    int per_xcd = (dm.tiles_per_image * dm.N + 7) / 8;
-    if (per_xcd > 64) per_xcd = 64;     // 32 CUs per XCD x 2 resident workgroups (the weights take the registers of a third)
-    return launch<conv3x3_c64_kernel>(dim3((unsigned)(8 * per_xcd)), kC64Threads, kC64Lds, stream, "alo_conv3x3_nhwc", args);
+    const unsigned gx = xcd_grid(dm.tiles_per_image * dm.N, 64);   // 32 CUs per XCD x 2 resident workgroups (the weights take the registers of a third)
+    return launch<conv3x3_c64_kernel>(dim3(gx), kC64Threads, kC64Lds, stream, "alo_conv3x3_nhwc", args);
 }
 
 }  // namespace

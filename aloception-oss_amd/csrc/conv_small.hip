@@ -60,7 +60,7 @@ conv3x3_small_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wf
         for (int cs = 0; cs < CIN / 16; ++cs) {
             const u32x4 a = wf[(tap * (CIN / 16) + cs) * 64];
             const u32x4 b = *reinterpret_cast<const u32x4*>(src + cs * 32);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b), acc, 0, 0, 0);
+            acc = mfma_32x32x16<bf16_t>(a, b, acc);
         }
     }
     // ---- store: this lane's pixel, channels 8 j + 4 kg .. + 3 from registers 4 j .. 4 j + 3 ------------------------------------------

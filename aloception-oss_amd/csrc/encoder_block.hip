@@ -12,7 +12,7 @@
 // each LayerNorm reads B (+ its residual) one wave per row, a lane owning 4 consecutive columns as in add_layernorm_kernel, and leaves
 // the normalised rows in A for the next product.  Rounding points, operand roles and summation orders are those of the kernels this
 // stands in for, so the three outputs equal theirs bit for bit.
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 #include "../../include/alo_encoder_block.h"
 
@@ -36,12 +36,6 @@ struct EncBlockArgs {
     int S, F, tiles;
     float eps1, eps2;
 };
-
-__device__ __forceinline__ void unpack4(const u32x2& x, float (&v)[4]) {
-    v[0] = __uint_as_float(x.x << 16); v[1] = __uint_as_float(x.x & 0xffff0000u);
-    v[2] = __uint_as_float(x.y << 16); v[3] = __uint_as_float(x.y & 0xffff0000u);
-}
-__device__ __forceinline__ u32x2 pack4(const float (&v)[4]) { return u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}; }
 
 // LayerNorm of one 256-wide row spread over the wave, 4 consecutive columns per lane: add_layernorm_kernel's arithmetic
 __device__ __forceinline__ void layernorm_row(const float (&v)[4], const f32x4& g, const f32x4& b, float eps, float (&y)[4]) {
@@ -68,20 +62,6 @@ __device__ __forceinline__ void init_acc_bias(f32x16 (&acc)[2][2], const float* 
 #pragma unroll
             for (int i = 0; i < 4; ++i) { acc[0][t][4 * q + i] = bb[i]; acc[1][t][4 * q + i] = bb[i]; }
         }
-}
-__device__ __forceinline__ void zero_acc(f32x16 (&acc)[2][2]) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][t][i] = 0.f;
-}
-// a wave reads back what it staged itself
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // An opaque copy of a weight pointer, taken once per tile: without it the address of every weight load of the three short products (a
@@ -183,12 +163,12 @@ encoder_block_kernel(const EncBlockArgs p) {
 #pragma unroll
             for (int r = 0; r < kRowsPerWave; ++r) {
                 float v[4], t[4], y[4];
-                unpack4(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
-                unpack4(res[r], t);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                unpack4<bf16_t>(res[r], t);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] += t[i];
                 layernorm_row(v, g, b, p.eps1, y);
-                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4(y);
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4<bf16_t>(y);
             }
         } else {
             load_batch(bufa, k256_frag(p.w1, 0), kStride256, 0);
@@ -220,12 +200,12 @@ encoder_block_kernel(const EncBlockArgs p) {
 #pragma unroll
             for (int r = 0; r < kRowsPerWave; ++r) {
                 float v[4], t[4], y[4];
-                unpack4(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
-                unpack4(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), t);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), t);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] += t[i];
                 layernorm_row(v, g, b, p.eps2, y);
-                const u32x2 o = pack4(y);
+                const u32x2 o = pack4<bf16_t>(y);
                 *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = o;
                 const long row = row0 + wrow + r;
                 if (row < p.M) *reinterpret_cast<u32x2*>(p.out + row * 256 + 4 * lane) = o;
@@ -275,11 +255,11 @@ encoder_block_kernel(const EncBlockArgs p) {
 #pragma unroll
             for (int r = 0; r < kRowsPerWave; ++r) {
                 float y[4], t[4];
-                unpack4(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), y);
-                unpack4(posr[r], t);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), y);
+                unpack4<bf16_t>(posr[r], t);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) y[i] += t[i];
-                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4(y);
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4<bf16_t>(y);
             }
             __syncthreads();  // the query is in A; the value rows have left B
 

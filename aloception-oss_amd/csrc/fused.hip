@@ -475,6 +475,7 @@ extern "C" int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatia
     long n4 = (long)B * S * (2 * num_pos_feats) / 4;
     void* args[] = {&workspace, &dim_t, &level_embed, &level_start_index, &out, &n4, &S, &L, &num_pos_feats};
     if (dtype == ALO_F32) return launch<pos_generate_kernel<float>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
-    if (dtype == ALO_F16) return launch<pos_generate_kernel<f16_t>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
-    return launch<pos_generate_kernel<bf16_t>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
+    return with_storage_type(dtype, [&](auto t) {
+        return launch<pos_generate_kernel<decltype(t)>>(stream_blocks(n4), kThreads, 0, st, "alo_pos_sine_flat", args);
+    });
 }

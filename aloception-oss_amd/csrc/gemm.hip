@@ -13,7 +13,7 @@
 //     back as A fragments by all four waves;
 //   * Y leaves through LDS as well, so that every store instruction writes whole 128-byte lines (the MFMA accumulator
 //     layout has a lane own one column and 16 scattered rows).
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace alo {
 namespace {
@@ -80,13 +80,6 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
             r[j] = *reinterpret_cast<const u32x4*>(X + row * kK + (p % kPieces) * 8);
         }
     };
-    auto park = [&](const u32x4 (&r)[kLoads]) {
-#pragma unroll
-        for (int j = 0; j < kLoads; ++j) {
-            const int p = tid + 256 * j;
-            *reinterpret_cast<u32x4*>(xbuf + (p / kPieces) * kRowBytes + (p % kPieces) * 16) = r[j];
-        }
-    };
 
     int tile = blockIdx.x;
     if (tile >= dm.tiles) return;
@@ -94,7 +87,7 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
     fetch(tile, stage);
 
     for (;;) {
-        park(stage);
+        park_tile<kPieces>(xbuf, kRowBytes, stage, tid);
         __syncthreads();  // the tile is in LDS
         const int next = tile + gridDim.x;
         const bool more = next < dm.tiles;
@@ -119,20 +112,10 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
                     acc[0] = mfma_32x32x16<T>(wreg[0][s], a, acc[0]);
                     acc[1] = mfma_32x32x16<T>(wreg[1][s], a, acc[1]);
                 }
-                // lane = tile row 32 half + nl; registers 4 q .. 4 q + 3 = columns 32 t + 8 q + 4 kg .. + 3 -> bf16 -> LDS [row][col]
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float v0 = acc[t][4 * q], v1 = acc[t][4 * q + 1], v2 = acc[t][4 * q + 2], v3 = acc[t][4 * q + 3];
-                        if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                        *reinterpret_cast<u32x2*>(obuf + (32 * half + nl) * kOutStride + (32 * t + 8 * q + 4 * kg) * 2) =
-                            u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
-                    }
+                // lane = tile row 32 half + nl -> bf16 -> LDS [row][col]
+                stage_quads<T, false>(obuf, kOutStride, acc, nullptr, RELU && !HAS_RES, 32 * half + nl, 0, kg);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             if constexpr (HM) {
                 // per head (32 columns = 64 B per row): 4 lanes x 16 B per row, 16 consecutive rows = 1 KB per store instruction
                 const unsigned char* mask = reinterpret_cast<const unsigned char*>(R);
@@ -152,19 +135,8 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
                         }
                     }
                 }
-            } else
-            // rows leave as whole 128-byte lines: 8 lanes x 16 B per row, 8 rows per store instruction
-#pragma unroll
-            for (int pass = 0; pass < kRows / 8; ++pass) {
-                const int row = pass * 8 + (lane >> 3);
-                const long grow = (long)tile * kRows + row;
-                u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
-                if (grow < dm.M) {
-                    if constexpr (HAS_RES) {  // + identity (same coordinates as y), then the activation
-                        v = add_residual_x8<T, RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
-                    }
-                    *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
-                }
+            } else {
+                store_rows<T, RELU, HAS_RES>(Y, R, obuf, kOutStride, (long)tile * kRows, dm.M, dm.N, col0, lane);
             }
         }
         if (!more) break;
@@ -201,17 +173,23 @@ int launch_shortk(const void* x, const void* weight, const void* bias, const voi
     return launch<linear_shortk_kernel<typename Cfg::type, K, RELU, HAS_RES, HM>>(dim3(gx, cols), 256, lds, stream, "alo_linear_shortk", args);
 }
 
+// K -> f(ShortK<T, K>{}); the one K dispatch of the file (the entry points have checked K, alo_conv1x1_nhwc relies on this check)
+template <typename T, typename F>
+int with_shortk(int K, F&& f) {
+    if (K == 64) return f(ShortK<T, 64>{});
+    if (K == 128) return f(ShortK<T, 128>{});
+    if (K == 256) return f(ShortK<T, 256>{});
+    return fail(ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: the resident-weight kernel needs Cin in (64, 128, 256), got %d", K);
+}
+
 // K x relu x residual -> the launch, for storage type T
 template <typename T>
 int dispatch_shortk(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K, int relu,
                     const RowGather& gather, hipStream_t stream) {
-    using K64 = ShortK<T, 64>;
-    using K128 = ShortK<T, 128>;
-    using K256 = ShortK<T, 256>;
-    if (K == 64) return ALO_RELU_RES(launch_shortk, K64, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    if (K == 128) return ALO_RELU_RES(launch_shortk, K128, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    if (K == 256) return ALO_RELU_RES(launch_shortk, K256, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
-    return fail(ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: the resident-weight kernel needs Cin in (64, 128, 256), got %d", K);
+    return with_shortk<T>(K, [&](auto cfg) {
+        using Cfg = decltype(cfg);
+        return ALO_RELU_RES(launch_shortk, Cfg, relu, residual, x, weight, bias, residual, y, M, N, stream, 0, gather);
+    });
 }
 }  // namespace
 
@@ -224,8 +202,7 @@ extern "C" int alo_linear_shortk(const void* x, const void* weight, const void* 
     ALO_REQUIRE(K == 64 || K == 128 || K == 256, ALO_ERR_UNSUPPORTED, "alo_linear_shortk: K must be 64, 128 or 256, got %d", K);
     ALO_REQUIRE(aligned16(x, weight, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_shortk: pointers must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == ALO_F16) return dispatch_shortk<f16_t>(x, weight, bias, residual, y, M, N, K, relu, row_gather(), st);
-    return dispatch_shortk<bf16_t>(x, weight, bias, residual, y, M, N, K, relu, row_gather(), st);
+    return with_storage_type(dtype, [&](auto t) { return dispatch_shortk<decltype(t)>(x, weight, bias, residual, y, M, N, K, relu, row_gather(), st); });
 }
 
 // 1x1 convolution with a spatial stride over an NHWC map, resident-weight flavour: the kept pixels are addressed by the tile
@@ -278,7 +255,7 @@ ffn256_kernel(const T* __restrict__ X, const T* __restrict__ W1, const T* __rest
     for (int i = tid; i < F; i += 256) b1s[i] = B1 ? ld(B1 + i) : 0.f;
     b2s[tid] = B2 ? ld(B2 + tid) : 0.f;
 
-    // the weights stream through two register buffers, a batch ahead of their use (load_batch / mma_batch of common.hpp)
+    // the weights stream through two register buffers, a batch ahead of their use (load_batch / mma_batch of mfma_tile.hpp)
     const int fs = F / 16;  // k steps per output-column tile of the packed W2
     // packed fragment (row tile, k step) = 64 lanes x 16 B contiguous: a load instruction reads 8 whole lines
     auto w1_frag = [&](int r0) { return W1 + ((size_t)((r0 + 64 * wave) / 32) * 16 * 64 + lane) * 8; };  // tile stride 16 * 512
@@ -296,22 +273,12 @@ ffn256_kernel(const T* __restrict__ X, const T* __restrict__ W1, const T* __rest
         __syncthreads();
 
         f32x16 acc2[2][2];  // [row tile][column tile] of this wave's 64 output columns
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc2[a][t][i] = 0.f;
+        zero_acc(acc2);
 
         for (int r0 = 0; r0 < F; r0 += 256) {
             // ---- phase 1: this wave's 64 hidden units of the chunk: h = relu(x W1[r0 + 64 wave + ...]^T + b1) ----------------
             f32x16 acc1[2][2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc1[a][t][i] = 0.f;
+            zero_acc(acc1);
             const T* w1p = w1_frag(r0);
             const T* w2p = w2_frag(r0);
             mma_tile256(acc1, xs, bufa, bufb, w1p, (size_t)16 * 512, w2p, (size_t)fs * 512, nl, kg);
@@ -383,8 +350,9 @@ extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const v
     int gx = dm.tiles < 512 ? dm.tiles : 512;
     void* args[] = {&x, &w1, &b1, &w2, &b2, &y, &dm};
     if (lds > (size_t)kLdsLimit) return fail(ALO_ERR_UNSUPPORTED, "alo_ffn256: hidden width %d needs %zu bytes of LDS", F, lds);
-    if (dtype == ALO_F16) return launch<ffn256_kernel<f16_t>>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
-    return launch<ffn256_kernel<bf16_t>>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
+    return with_storage_type(dtype, [&](auto t) {
+        return launch<ffn256_kernel<decltype(t)>>(gx, 256, lds, static_cast<hipStream_t>(stream), "alo_ffn256", args);
+    });
 }
 
 extern "C" int alo_value_proj_head_major(const void* x, const void* weight, const void* bias, const void* padding_mask,
@@ -399,12 +367,9 @@ extern "C" int alo_value_proj_head_major(const void* x, const void* weight, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long M = (long)batch * S;
     const int N = heads * 32;
-    if (dtype == ALO_F16) {
-        if (K == 64) return launch_shortk<ShortK<f16_t, 64>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-        if (K == 128) return launch_shortk<ShortK<f16_t, 128>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-        return launch_shortk<ShortK<f16_t, 256>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-    }
-    if (K == 64) return launch_shortk<ShortK<bf16_t, 64>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-    if (K == 128) return launch_shortk<ShortK<bf16_t, 128>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
-    return launch_shortk<ShortK<bf16_t, 256>, false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+    return with_storage_type(dtype, [&](auto t) {
+        return with_shortk<decltype(t)>(K, [&](auto cfg) {
+            return launch_shortk<decltype(cfg), false, false, true>(x, weight, bias, padding_mask, value_hm, M, N, st, S);
+        });
+    });
 }

@@ -8,7 +8,7 @@
 // while X goes through LDS 256 (128) columns at a time, the next chunk being fetched into registers during the MFMAs of the
 // current one.  A wave owns a 64 x 64 block of Y (2 x 2 MFMA tiles, computed transposed so a lane holds one row); a workgroup
 // is 1 x 4 waves (64 rows x 256 columns) or, for N = 128, 2 x 2 (128 rows x 128 columns).
-#include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace alo {
 namespace {
@@ -62,32 +62,13 @@ linear_packed_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const T*
             r[j] = *reinterpret_cast<const u32x4*>(X + row * dm.K + chunk * KC + (p % kPieces) * 8);
         }
     };
-    auto park = [&](const u32x4 (&r)[kLoads]) {
-#pragma unroll
-        for (int j = 0; j < kLoads; ++j) {
-            const int p = tid + 256 * j;
-            *reinterpret_cast<u32x4*>(xs + (p / kPieces) * kStride + (p % kPieces) * 16) = r[j];
-        }
-    };
     const int ksteps = dm.K / 16;
     const size_t tile_stride = (size_t)ksteps * 512;   // elements between packed column tiles
     const T* wfrag = Wp + (size_t)(col0 / 32) * tile_stride + lane * 8;
-    auto load_batch = [&](u32x4 (&buf)[2][KB], int gbatch) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < KB; ++j)
-                buf[t][j] = *reinterpret_cast<const u32x4*>(wfrag + t * tile_stride + (size_t)(KB * gbatch + j) * 512);
-        __builtin_amdgcn_sched_barrier(0);
-    };
     f32x16 acc[2][2];   // [row tile][column tile]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][t][i] = 0.f;
+    zero_acc(acc);
     const unsigned char* a_lds = xs + (64 * wr) * kStride;
+    // mma_batch of mfma_tile.hpp with this kernel's stride; kept here (see there)
     auto mma_batch = [&](const u32x4 (&buf)[2][KB], int batch) {
         u32x4 af[2][KB];
 #pragma unroll
@@ -111,53 +92,26 @@ linear_packed_kernel(const T* __restrict__ X, const T* __restrict__ Wp, const T*
     u32x4 stage[kLoads];
     u32x4 bufa[2][KB], bufb[2][KB];
     fetch(0, stage);
-    load_batch(bufa, 0);
+    load_batch(bufa, wfrag, tile_stride, 0);
     for (int c = 0; c < nchunks; ++c) {
-        park(stage);
+        park_tile<kPieces>(xs, kStride, stage, tid);
         __syncthreads();
         if (c + 1 < nchunks) fetch(c + 1, stage);   // in flight during this chunk's MFMAs
         const int gb = c * NB;
 #pragma unroll
         for (int bt = 0; bt < NB; bt += 2) {
-            load_batch(bufb, gb + bt + 1);
+            load_batch(bufb, wfrag, tile_stride, gb + bt + 1);
             mma_batch(bufa, bt);
-            if (gb + bt + 2 < total_batches) load_batch(bufa, gb + bt + 2);
+            if (gb + bt + 2 < total_batches) load_batch(bufa, wfrag, tile_stride, gb + bt + 2);
             mma_batch(bufb, bt + 1);
         }
         __syncthreads();   // everyone is done with the chunk (and, after the last one, with the LDS it sits in)
     }
 
-    // ---- epilogue: lane = row 64 wr + 32 a + nl; registers 4 q .. 4 q + 3 = columns col0 + 32 t + 8 q + 4 kg .. + 3 ----------------
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = 32 * t + 8 * q + 4 * kg;
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(bias_s + wc * 64 + c);
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                float v0 = acc[a][t][4 * q] + bb[0], v1 = acc[a][t][4 * q + 1] + bb[1];
-                float v2 = acc[a][t][4 * q + 2] + bb[2], v3 = acc[a][t][4 * q + 3] + bb[3];
-                if (RELU && !HAS_RES) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
-                *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack2<T>(v0, v1), pack2<T>(v2, v3)};
-            }
-        }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // rows leave as whole 128-byte lines: 8 lanes x 16 B per row, 8 rows per store instruction
-#pragma unroll
-    for (int pass = 0; pass < 8; ++pass) {
-        const int row = pass * 8 + (lane >> 3);
-        const long grow = row0 + 64 * wr + row;
-        u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
-        if (grow < dm.M) {
-            if constexpr (HAS_RES) {   // + identity (same coordinates as y), then the activation
-                v = add_residual_x8<T, RELU>(v, *reinterpret_cast<const u32x4*>(R + grow * dm.N + col0 + (lane & 7) * 8));
-            }
-            *reinterpret_cast<u32x4*>(Y + grow * dm.N + col0 + (lane & 7) * 8) = v;
-        }
-    }
+    // ---- epilogue: + bias (-> ReLU) -> bf16 -> this wave's staging -> whole lines (+ residual -> ReLU) ----------------------------------
+    stage_quads<T, true>(obuf, kOutStride, acc, bias_s + wc * 64, RELU && !HAS_RES, nl, 0, kg);
+    wave_lds_fence();
+    store_rows<T, RELU, HAS_RES>(Y, R, obuf, kOutStride, row0 + 64 * wr, dm.M, dm.N, col0, lane);
 }
 
 template <class Cfg, bool RELU, bool HAS_RES>
@@ -196,8 +150,7 @@ extern "C" int alo_linear_packed(const void* x, const void* w_packed, const void
     ALO_REQUIRE((M + 63) / 64 < (1L << 31), ALO_ERR_UNSUPPORTED, "alo_linear_packed: too many rows");
     PackedDims dm;
     dm.M = M; dm.N = N; dm.K = K; dm.g = row_gather();
-    if (dtype == ALO_F16) return dispatch_packed<f16_t>(x, w_packed, bias, residual, y, dm, relu, stream);
-    return dispatch_packed<bf16_t>(x, w_packed, bias, residual, y, dm, relu, stream);
+    return with_storage_type(dtype, [&](auto t) { return dispatch_packed<decltype(t)>(x, w_packed, bias, residual, y, dm, relu, stream); });
 }
 
 extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual,

@@ -446,11 +446,8 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
-// LDS operations of ONE wave execute in order, so data handed from lane to lane of a wave through LDS needs no wait at all — only
-// the compiler must not move the reads above the writes.  The fence builtins at "wavefront" scope are NOT that: they lower to
-// s_waitcnt vmcnt(0) lgkmcnt(0), i.e. every hand-over also waited for the wave's outstanding global loads, stores and atomics
-// (the forward: its own output store and the next run's inputs; the tiled backward: all of a pass's row atomics).
-#define ALO_WAVE_LDS_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
+// Lane-to-lane hand-overs through LDS inside a wave use ALO_WAVE_LDS_ORDER (common.hpp): no wait, where a wavefront fence would also wait
+// for the forward's own output store and the next run's inputs, and for all of a pass's row atomics in the tiled backward.
 
 // One sampling point -> four corner byte offsets + four corner weights (already times the attention weight), the lean way the
 // wave kernels use (fp32, `W * row_bytes` and `H * W` below 2^23).  Same semantics as make_desc (cuh:285-291, :38-78):

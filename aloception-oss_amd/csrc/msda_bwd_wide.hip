@@ -187,8 +187,6 @@ __device__ __forceinline__ Tap make_tap_w(float x, float y, int Hl, int Wl, bool
     return t;
 }
 
-#define ALO_WAVE_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); asm volatile("" ::: "memory"); } while (0)
-
 template <typename T, int D>
 __global__ void __launch_bounds__(kWThreads, D == 32 ? 4 : 2)
 msda_bwd_wide_kernel(const T* __restrict__ value, const int32_t* __restrict__ shapes, const int32_t* __restrict__ lstart,

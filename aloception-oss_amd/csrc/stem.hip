@@ -138,10 +138,11 @@ stem_conv_pool_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W
                 else if (G % 3 == 2) { a.z &= 0x0000ffffu; a.w = 0u; }
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
-                    acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wreg[s][ct]), as_bf16x8(a), acc[ct], 0, 0, 0);
+                    acc[ct] = mfma_32x32x16<bf16_t>(wreg[s][ct], a, acc[ct]);
             }
             // ReLU -> bf16 into the convolution buffer, 4 consecutive channels per write; pixels outside the convolution's output
-            // are the pool's padding (0 is neutral for a max over ReLU outputs)
+            // are the pool's padding (0 is neutral for a max over ReLU outputs).  Not stage_quads of mfma_tile.hpp: the two masks
+            // (m_raw, ok) and the zeros written for masked pixels are this kernel's own.
             const int cy = cy0 + lr, cx = cx0 + lc;
             const bool ok = cy >= 0 && cy < dm.Hc && cx >= 0 && cx < dm.Wc;
             if (m_raw < kConvPix) {

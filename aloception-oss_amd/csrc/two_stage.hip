@@ -279,12 +279,10 @@ extern "C" int alo_proposal_queries(const float* coords_unact, const long long* 
         void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};
         return launch<proposal_queries_kernel<float>>(blocks, 256, 0, s, "alo_proposal_queries", args);
     }
-    if (dtype == ALO_F16) {
-        f16_t* e = static_cast<f16_t*>(embed);
+    return with_storage_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        T* e = static_cast<T*>(embed);
         void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};
-        return launch<proposal_queries_kernel<f16_t>>(blocks, 256, 0, s, "alo_proposal_queries", args);
-    }
-    bf16_t* e = static_cast<bf16_t*>(embed);
-    void* args[] = {&coords_unact, &topk, &dim_t, &reference_points, &e, &S, &K, const_cast<long*>(&queries)};
-    return launch<proposal_queries_kernel<bf16_t>>(blocks, 256, 0, s, "alo_proposal_queries", args);
+        return launch<proposal_queries_kernel<T>>(blocks, 256, 0, s, "alo_proposal_queries", args);
+    });
 }
