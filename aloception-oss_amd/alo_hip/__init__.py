@@ -381,6 +381,7 @@ def msda_forward_fused(value, spatial_shapes, level_start_index, sampling_offset
     """MSDeformAttn's prologue + gather in one launch (inference): raw offsets (N,Lq,M,L,P,2) and raw attention logits
     (N,Lq,M,L*P) in ``value``'s dtype (fp32, fp64, bf16 or fp16), reference points (N,Lq,L,2|4) in fp32 (fp64 for fp64 values)
     -> (N,Lq,M*D)."""
+    _no_autograd("msda_forward_fused", value, sampling_offsets, attn_logits, reference_points)
     if not value.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     N, S, M, D = value.shape
@@ -413,6 +414,7 @@ def head_major_supported(value, L, P):
 def value_head_major(value, padding_mask=None):
     """(N, S, M, D) bf16 / fp16 -> (N, M, S, D) with the rows of padded pixels zeroed: ``value.masked_fill(mask[..., None], 0)``
     and the re-layout for ``msda_forward_fused_hm`` in one pass."""
+    _no_autograd("value_head_major", value)
     _require_cuda_contiguous([("value", value)])
     N, S, M, D = value.shape
     if padding_mask is not None:
@@ -456,6 +458,7 @@ def msda_forward_fused_hm(value_hm, spatial_shapes, level_start_index, sampling_
     runs the plain kernel, whose bf16 output is bit-identical to ``msda_forward_fused``.  fp16 values never go resident (the
     resident kernel is bf16 only): no hint is passed and ``resident`` changes nothing; their output is within half an fp16 ulp of
     the exact result like ``msda_forward_fused``'s, not bit-identical to it (two-term weight split, see include/alo_hotpath.h)."""
+    _no_autograd("msda_forward_fused_hm", value_hm, sampling_offsets, attn_logits, reference_points)
     if not value_hm.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     N, M, S, D = value_hm.shape
@@ -669,14 +672,43 @@ def corr_alt_lookup(workspace, coords, channels, num_levels, radius=4):
     return out
 
 
-def fusable(*tensors, f16=False):
+def _grad_tensors(operands):
+    """The tensors an operand list stands for: a tensor for itself, an ``nn.Module`` for every parameter it holds (its sub-modules'
+    included), ``None`` (an absent bias, mask, residual) for nothing."""
+    for t in operands:
+        if isinstance(t, torch.nn.Module):
+            yield from t.parameters()
+        elif t is not None:
+            yield t
+
+
+def needs_autograd(*operands):
+    """True when autograd would record an op on these operands (tensors, modules, ``None``): grad mode is on and one of the tensors,
+    or one parameter of one of the modules, requires grad.  With grad mode off nothing is looked at."""
+    return torch.is_grad_enabled() and any(t.requires_grad for t in _grad_tensors(operands))
+
+
+def fusable(*operands, f16=False):
     """True when the fused epilogues may replace the stock ops: inference (no autograd graph), CUDA, fp32 or bf16 — and fp16 with
     ``f16=True``, which a caller passes when every kernel behind it serves fp16 (the transformer's layers do; the backbone, the
-    input projections, the mask head and RAFT's update block do not)."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+    input projections, the mask head and RAFT's update block do not).  The first operand is the activation (a tensor); the others
+    are whatever else the fast path consumes: tensors, ``None`` for an absent one, and modules, which stand for all their
+    parameters.  A call site names EVERYTHING its fast path reads — the kernels have no backward, so one trainable operand left out
+    loses its gradient (and that of everything upstream of the detached result) without an error."""
+    if needs_autograd(*operands):
         return False
-    first = tensors[0]
+    first = operands[0]
     return first.is_cuda and first.dtype in (torch.float32, *_half(f16))
+
+
+def _no_autograd(name, *operands):
+    """The wrappers' backstop, called first in every wrapper that writes through raw pointers outside an ``autograd.Function``:
+    what they return carries no ``grad_fn``, so an operand that requires grad under grad mode is a caller's gate that forgot it
+    (:func:`fusable`) — an error here instead of a silently missing or wrong gradient."""
+    if needs_autograd(*operands):
+        raise RuntimeError(f"alo_hip.{name} has no backward and an operand requires grad: call it under torch.no_grad() or with "
+                           f"every operand frozen / detached, and take the stock PyTorch ops otherwise (alo_hip.fusable answers "
+                           f"for a call site when given every tensor and module its fast path reads)")
 
 
 def add_layernorm_supported(x):
@@ -707,6 +739,7 @@ def add_layernorm(x, residual, weight, bias, eps=1e-5, pos=None):
     """``LayerNorm(x + residual)`` over the last dim in one pass; with ``pos`` also returns ``out + pos`` (the next
     layer's ``with_pos_embed``).  Replaces ``norm(src + dropout(src2))`` of the (de)formable transformer layers at
     inference.  -> out  |  (out, out_plus_pos)"""
+    _no_autograd("add_layernorm", x, residual, weight, bias, pos)
     C = x.shape[-1]
     rows = x.numel() // C
     x = x.contiguous()
@@ -727,6 +760,7 @@ def add_layernorm(x, residual, weight, bias, eps=1e-5, pos=None):
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on a channels-last activation ``x`` (N,C,H,W with NHWC strides) or a (rows, C) matrix:
     ``x = act(x + bias[c] (+ residual))``.  Replaces folded FrozenBatchNorm bias -> (+ identity) -> ReLU of the ResNet."""
+    _no_autograd("bias_act_", x, bias, residual)
     if x.dim() == 4:
         if not x.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError("bias_act_: 4-D input must be channels_last")
@@ -756,6 +790,7 @@ def _require_f32_nchw(name, t):
 
 def bias_act_nchw_(x, bias, relu=True):
     """In place: ``x = act(x + bias[None, :, None, None])`` — the bias MIOpen would add in a second kernel plus the ReLU."""
+    _no_autograd("bias_act_nchw_", x, bias)
     _require_f32_nchw("x", x)
     B, C, H, W = x.shape
     _launch("alo_bias_act_nchw", x.device, f"bias_act_nchw/C={C}", 8.0 * x.numel(), 0.0, x, bias.float().contiguous(), x, B, C, H * W,
@@ -765,6 +800,7 @@ def bias_act_nchw_(x, bias, relu=True):
 
 def gru_gate_(zr, bias_zr, hx, rhx, C):
     """``zr`` (B,2C,H,W): pre-activations [z | r].  z <- sigmoid(z + b) in place; ``rhx[:, :C] <- sigmoid(r + b) * hx[:, :C]``."""
+    _no_autograd("gru_gate_", zr, bias_zr, hx, rhx)
     _require_f32_nchw("zr", zr); _require_f32_nchw("hx", hx); _require_f32_nchw("rhx", rhx)
     B, C2, H, W = zr.shape
     if C2 != 2 * C or hx.shape != rhx.shape or hx.shape[0] != B or hx.shape[2:] != zr.shape[2:] or hx.shape[1] < C:
@@ -775,6 +811,7 @@ def gru_gate_(zr, bias_zr, hx, rhx, C):
 
 def gru_update_(q, bias_q, zr, hx, C, net=None):
     """``hx[:, :C] <- (1 - z) * hx[:, :C] + z * tanh(q + b)`` with z = ``zr[:, :C]``; ``net`` (B,C,H,W) also receives the result."""
+    _no_autograd("gru_update_", q, bias_q, zr, hx, net)
     _require_f32_nchw("q", q); _require_f32_nchw("zr", zr); _require_f32_nchw("hx", hx)
     B, Cq, H, W = q.shape
     if Cq != C or zr.shape != (B, 2 * C, H, W) or hx.shape[0] != B or hx.shape[2:] != q.shape[2:]:
@@ -789,6 +826,7 @@ def pos_sine_flat(mask_flatten, spatial_shapes, level_start_index, dim_t, level_
                   eps=1e-6):
     """Sine positional encoding of the flattened pyramid + level embedding -> (B, S, 2F) in ``dtype`` (two launches).
     ``mask_flatten`` (B, S) bool, ``dim_t`` (F,) fp32, ``level_embed`` (L, 2F) or None."""
+    _no_autograd("pos_sine_flat", level_embed)
     B, S = mask_flatten.shape
     L, F = spatial_shapes.shape[0], dim_t.numel()
     if mask_flatten.dtype != torch.bool or dim_t.dtype != torch.float32:
@@ -816,6 +854,7 @@ def linear_shortk_supported(x, weight, f16=False):
 def linear_shortk(x, weight, bias=None, relu=False, residual=None):
     """``act(x @ weight.T + bias [+ residual])`` over the last dim (64 / 128 / 256) of a bf16 / fp16 ``x``; weight (N, K), N % 64 == 0;
     ``residual`` has the shape of the result and is added before the activation."""
+    _no_autograd("linear_shortk", x, weight, bias, residual)
     if not linear_shortk_supported(x, weight, f16=True):
         raise RuntimeError("linear_shortk: needs bf16 / fp16 CUDA tensors of one dtype, K in (64, 128, 256) and N % 64 == 0")
     if bias is not None and bias.dtype != x.dtype:
@@ -848,6 +887,7 @@ def linear_packed_supported(x, weight, f16=False):
 def linear_packed(x, weight, bias=None, relu=False, residual=None):
     """``act(F.linear(x, weight, bias) [+ residual])`` with the weight streamed in MFMA fragment order (packed once per weight
     version, cached on the tensor)."""
+    _no_autograd("linear_packed", x, weight, bias, residual)
     if not linear_packed_supported(x, weight, f16=True):
         raise RuntimeError("linear_packed: needs bf16 / fp16 CUDA tensors of one dtype, K % 256 == 0, K >= 512, N % 128 == 0, no autograd")
     x2 = x.reshape(-1, x.shape[-1])
@@ -883,6 +923,7 @@ def conv1x1_strided_supported(x, weight2d):
 
 def conv1x1_strided(x, weight2d, bias, stride, relu=False):
     """``act(F.conv2d(x, weight2d[:, :, None, None], bias, stride))`` for a channels-last bf16 ``x``; returns channels-last."""
+    _no_autograd("conv1x1_strided", x, weight2d, bias)
     if not conv1x1_strided_supported(x, weight2d):
         raise RuntimeError("conv1x1_strided: unsupported dtype / layout / shape")
     n, cin, h, w_ = x.shape
@@ -901,6 +942,7 @@ def linear_auto(x, weight, bias=None, relu=False, residual=None):
     """Inference-time ``act(F.linear(x, weight, bias) [+ residual])``: the streaming MFMA kernels when the shape allows it
     (bf16 / fp16; K in {64, 128, 256} with N % 64 == 0, or K % 256 == 0 with N % 128 == 0), otherwise the stock GEMM with the bias /
     ReLU epilogue."""
+    _no_autograd("linear_auto", x, weight, bias, residual)
     if linear_shortk_supported(x, weight, f16=True) and (bias is None or bias.dtype == x.dtype):
         return linear_shortk(x, weight, bias, relu, residual=residual)
     if linear_packed_supported(x, weight, f16=True) and (bias is None or bias.dtype == x.dtype) and (
@@ -946,6 +988,7 @@ def _pack_mfma_b(w):
 def ffn256(x, w1, b1, w2, b2):
     """``relu(x @ w1.T + b1) @ w2.T + b2`` over the last dim (= 256) of a bf16 / fp16 ``x`` in one kernel (hidden width % 256 == 0);
     the hidden activation is rounded to ``x``'s dtype before the second product, as two launches would store it."""
+    _no_autograd("ffn256", x, w1, b1, w2, b2)
     if not ffn256_supported(x, w1, w2, f16=True):
         raise RuntimeError("ffn256: needs bf16 / fp16 CUDA tensors of one dtype, d_model = 256 and a hidden width that is a multiple of 256")
     x2 = x.reshape(-1, 256)
@@ -973,6 +1016,7 @@ def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1),
 def conv3x3(x, weight, bias=None, relu=False, stride=1):
     """``act(F.conv2d(x, weight, bias, stride, 1))`` for a channels-last bf16 ``x`` (N, Cin, H, W): implicit GEMM on MFMA with
     the bias and the ReLU in its epilogue.  Returns a channels-last (N, Cout, Ho, Wo) tensor."""
+    _no_autograd("conv3x3", x, weight, bias)
     stride = stride[0] if isinstance(stride, (tuple, list)) else stride
     if not conv3x3_supported(x, weight, (stride, stride)):
         raise RuntimeError("conv3x3: needs a channels-last bf16 CUDA activation, a (Cout, Cin, 3, 3) weight, Cin % 64 == 0, "
@@ -1001,6 +1045,7 @@ def stem_conv_pool_supported(x, weight):
 def stem_conv_pool(x, weight, bias=None):
     """``max_pool2d(relu(conv2d(x, weight, bias, stride=2, padding=3)), 3, 2, 1)`` — the ResNet stem — in one kernel.
     Returns a channels-last (N, 64, Hp, Wp) bf16 tensor."""
+    _no_autograd("stem_conv_pool", x, weight, bias)
     if not stem_conv_pool_supported(x, weight):
         raise RuntimeError("stem_conv_pool: needs a bf16 CUDA (N, 3, H, W) image, a (64, 3, 7, 7) bf16 weight, no autograd")
     n, _, h, w_ = x.shape
@@ -1042,6 +1087,7 @@ def groupnorm_nhwc_supported(x, norm):
 def groupnorm_nhwc(x, norm, relu=False):
     """``relu?(norm(x))`` for a channels-last bf16 map (N, C, H, W) and an ``nn.GroupNorm``; channels-last result.  ATen's GroupNorm
     works on NCHW: on a channels-last activation it costs a layout copy before and (for the next convolution) after."""
+    _no_autograd("groupnorm_nhwc", x, norm)
     if not groupnorm_nhwc_supported(x, norm):
         raise RuntimeError("groupnorm_nhwc: needs a channels-last bf16 CUDA map and 2, 4 or 8k channels per group, no autograd")
     n, c_, h, w_ = x.shape
@@ -1085,6 +1131,7 @@ def _small_conv_operands(conv):
 
 def conv3x3_small(x, conv):
     """``conv(x)`` for the few-channel 3x3 convolutions of the mask decoder (channels-last bf16 in and out)."""
+    _no_autograd("conv3x3_small", x, conv)
     if not conv3x3_small_supported(x, conv):
         raise RuntimeError("conv3x3_small: needs a channels-last bf16 CUDA map, a 3x3 / stride 1 / padding 1 convolution with Cin in "
                            "(16, 32, 64) and Cout = 1 or 4k <= 32, no autograd")
@@ -1108,6 +1155,7 @@ def upsample_add_supported(x_low, fpn):
 def upsample_add(x_low, fpn):
     """``fpn.repeat_interleave(Q, 0) + F.interpolate(x_low, size=fpn.shape[-2:], mode="nearest")`` in one pass (Q = x_low.shape[0]
     // fpn.shape[0]); channels-last bf16 in and out, bit-identical to the stock ops."""
+    _no_autograd("upsample_add", x_low, fpn)
     if not upsample_add_supported(x_low, fpn):
         raise RuntimeError("upsample_add: needs channels-last bf16 CUDA maps with C % 8 == 0 and x_low.shape[0] a multiple of fpn.shape[0]")
     bq, c_, h, w_ = x_low.shape
@@ -1122,6 +1170,7 @@ def upsample_add(x_low, fpn):
 def groupnorm_rows(x, weight, bias, groups, eps=1e-5, out=None):
     """``F.group_norm`` over channels-last rows: x (B, HW, C) contiguous -> out (B, HW, C), which may be a slice
     ``flat[:, start:start + HW]`` of a larger (B, S, C) buffer (rows contiguous, any batch stride)."""
+    _no_autograd("groupnorm_rows", x, weight, bias, out)
     if not groupnorm_rows_supported(x, weight, groups):
         raise RuntimeError("groupnorm_rows: needs bf16 CUDA rows (B, HW, C) with C / 8 and groups dividing 256, no autograd")
     x = x.contiguous()
@@ -1191,6 +1240,7 @@ def value_proj_head_major_supported(x, weight, heads, f16=False):
 def value_proj_head_major(x, weight, bias, padding_mask, heads):
     """``value_proj`` + ``masked_fill(padding_mask, 0)`` + head-major layout in one kernel: x (N, S, K) bf16 / fp16 ->
     (N, heads, S, 32) for ``msda_forward_fused_hm``."""
+    _no_autograd("value_proj_head_major", x, weight, bias)
     if not value_proj_head_major_supported(x, weight, heads, f16=True):
         raise RuntimeError("value_proj_head_major: needs bf16 / fp16 (N, S, K) input, K in (64, 128, 256), head dimension 32")
     if bias is not None and bias.dtype != x.dtype:
@@ -1236,6 +1286,7 @@ def encoder_block(src, w1, b1, w2, b2, norm2, tail=None, nxt=None):
     With ``nxt = (pos, padding_mask | None, wv, bv, wq, bq)`` also the next layer's ``value_proj_head_major(src', wv, bv,
     padding_mask, 8)`` and ``linear(src' + pos, wq, bq)`` for the merged (384, 256) offsets + logits weight.
     -> (src', value_hm | None, offsets_logits | None)"""
+    _no_autograd("encoder_block", src, w1, b1, w2, b2, *norm2[:2], *(tail or ())[:5], *(nxt or ()))
     if not encoder_block_supported(src, w1, w2, b1, b2, norm2[0], norm2[1]):
         raise RuntimeError("encoder_block: needs a bf16 CUDA (N, S, 256) src outside autograd, bf16 FFN weights with a hidden width "
                            "that is a multiple of 256, and every bias")
@@ -1330,6 +1381,7 @@ def encoder_proposals_masked_supported(mask_flatten, shapes, memory, f16=False):
 def encoder_proposals_masked(mask_flatten, shapes, memory):
     """:func:`encoder_proposals` and :func:`mask_rows` in one launch -> (proposals, keep, memory with the dropped rows zeroed):
     0.026 against 0.029 ms for the two launches at the headline size (docs/experiments.md)."""
+    _no_autograd("encoder_proposals_masked", memory)
     if not encoder_proposals_masked_supported(mask_flatten, shapes, memory, f16=True):
         raise RuntimeError("encoder_proposals_masked: needs what encoder_proposals and mask_rows need, memory (B, S, C) on the mask's device")
     B, S = mask_flatten.shape
@@ -1354,6 +1406,7 @@ def mask_rows_supported(memory, keep, f16=False):
 
 def mask_rows(memory, keep):
     """``memory.masked_fill(~keep[..., None], 0)`` in one pass of 16-byte vectors; dropped rows are written, not read."""
+    _no_autograd("mask_rows", memory)
     if not mask_rows_supported(memory, keep, f16=True):
         raise RuntimeError("mask_rows: needs contiguous CUDA fp32 / bf16 / fp16 rows with C % 8 == 0 and one bool / uint8 `keep` per row")
     C = memory.shape[-1]
@@ -1386,6 +1439,7 @@ def proposal_queries(coords_unact, topk, dtype, owner=None):
     (reference_points (B, K, 4) float32 = sigmoid of the gathered rows, embed (B, K, 512) ``dtype`` = their sine embedding,
     ``get_proposal_pos_embed``).  ``owner``: the weight the embedding feeds (``pos_trans.weight``), which keeps the 64 frequencies
     (:func:`proposal_dim_t`); without one they are computed per call."""
+    _no_autograd("proposal_queries", coords_unact)
     if not proposal_queries_supported(coords_unact, topk, dtype, f16=True):
         raise RuntimeError("proposal_queries: needs contiguous CUDA (B, S, 4) float32 coordinates, (B, K) int64 indices, fp32 / bf16 / fp16 output")
     B, S, _ = coords_unact.shape

@@ -202,7 +202,8 @@ class DeformableDETR(nn.Module):
     def _project_fast(self, lvl, x):
         """Which fast path covers ``input_proj[lvl]`` on ``x``: "gemm" (1x1), "conv3x3" or None."""
         conv = self.input_proj[lvl][0]
-        if (alo_hip.fusable(x, conv.weight) and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+        # the projection as a whole: the convolution's weight AND bias, and the GroupNorm whose affine alo_groupnorm_rows reads
+        if (alo_hip.fusable(x, self.input_proj[lvl]) and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
                 and conv.groups == 1 and conv.dilation == (1, 1) and conv.padding_mode == "zeros"):
             if conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.out_channels % 4 == 0:
                 return "gemm"

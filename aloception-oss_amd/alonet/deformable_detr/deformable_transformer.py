@@ -42,11 +42,13 @@ def _level_geometry(shapes, device):
     return _GEOMETRY[key]
 
 
-def _fused_ok(module, kwargs, *tensors):
+def _fused_ok(module, kwargs, *operands):
     """The one-pass HIP epilogues (alo_add_layernorm) stand in for ``norm(x + dropout(y))`` when nothing is lost: eval mode
-    (dropout is the identity), no autograd graph, CUDA, fp32 / bf16 / fp16, and not the pure-torch export branch."""
-    return (not module.training and "is_tracing" not in kwargs and alo_hip.fusable(*tensors, f16=True)
-            and alo_hip.add_layernorm_supported(tensors[0]))
+    (dropout is the identity), no autograd graph, CUDA, fp32 / bf16 / fp16, and not the pure-torch export branch.  ``operands``:
+    the activation first, then every tensor and module the fast path behind this gate reads (alo_hip.fusable) — the kernels detach
+    their result, so a trainable parameter or an upstream tensor that requires grad sends the whole route to the stock ops."""
+    return (not module.training and "is_tracing" not in kwargs and alo_hip.fusable(*operands, f16=True)
+            and alo_hip.add_layernorm_supported(operands[0]))
 
 
 def _add_norm(norm, x, residual, pos=None):
@@ -221,7 +223,7 @@ class DeformableTransformerEncoder(nn.Module):
         per_level = []
         host_shapes = getattr(spatial_shapes, "_alo_shapes", None)  # python copy set by DeformableTransformer: no device sync
         if (host_shapes is not None and valid_ratios.is_cuda and valid_ratios.dtype == torch.float32
-                and not (torch.is_grad_enabled() and valid_ratios.requires_grad) and "is_tracing" not in kwargs):
+                and not alo_hip.needs_autograd(valid_ratios) and "is_tracing" not in kwargs):
             return alo_hip.encoder_reference_points(valid_ratios, host_shapes)   # one kernel instead of ~10 per level
         for lvl in range(spatial_shapes.shape[0]):
             h, w = host_shapes[lvl] if host_shapes is not None else (int(spatial_shapes[lvl, 0]), int(spatial_shapes[lvl, 1]))
@@ -237,7 +239,7 @@ class DeformableTransformerEncoder(nn.Module):
     def forward(self, src, spatial_shapes, level_start_index, valid_ratios, pos=None, padding_mask=None, **kwargs):
         output = src
         reference_points = self.get_reference_points(spatial_shapes, valid_ratios, device=src.device, **kwargs)
-        if _fused_ok(self, kwargs, output, pos) and all(hasattr(layer, "forward_fused") for layer in self.layers):
+        if _fused_ok(self, kwargs, output, pos, self) and all(hasattr(layer, "forward_fused") for layer in self.layers):
             query = output if pos is None else output + pos
             if (pos is not None and alo_hip.encoder_block_enabled()
                     and all(hasattr(layer, "forward_block") and layer.block_supported(output, query) for layer in self.layers)):
@@ -295,12 +297,16 @@ class DeformableTransformerDecoderLayer(nn.Module):
             q = k = carried[1]
         else:
             q = k = self.with_pos_embed(tgt, query_pos)  # self-attention among the queries (sequence-first API)
-        if _fused_ok(self, kwargs, tgt, query_pos) and tgt_key_padding_mask is None and self.self_attn._qkv_same_embed_dim:
+        # the fused route reads every parameter of this layer, and its LayerNorm kernels detach what the cross-attention made of
+        # ``src`` / ``reference_points``: all of them are asked
+        if (_fused_ok(self, kwargs, tgt, query_pos, src, reference_points, self) and tgt_key_padding_mask is None
+                and self.self_attn._qkv_same_embed_dim):
             tgt2 = _self_attention(self.self_attn, q, tgt)
         else:
             tgt2 = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1),
                                   key_padding_mask=tgt_key_padding_mask)[0].transpose(0, 1)
-        if _fused_ok(self, kwargs, tgt, tgt2, query_pos):  # inference: residual + LayerNorm (+ query_pos) in one pass each
+        # inference: residual + LayerNorm (+ query_pos) in one pass each
+        if _fused_ok(self, kwargs, tgt, tgt2, query_pos, src, reference_points, self):
             if query_pos is None:
                 tgt = query = _add_norm(self.norm2, tgt2, tgt)
             else:
@@ -473,13 +479,15 @@ class DeformableTransformer(nn.Module):
         channel 0 and derive the decoder's inputs from their (detached) boxes.
         -> (query_pos, tgt, reference_points (B, K, 4), enc_outputs_class, enc_outputs_coord_unact)"""
         class_head, box_head = self._proposal_heads()
-        fused = _fused_ok(self, kwargs, memory, self.enc_output.weight, self.pos_trans.weight)
+        fused = _fused_ok(self, kwargs, memory, self.enc_output, self.enc_output_norm, self.pos_trans, self.pos_trans_norm)
         output_memory, output_proposals = self.gen_encoder_output_proposals(memory, mask_flatten, shapes, fused=fused)
         enc_outputs_class = class_head(output_memory)
         enc_outputs_coord_unact = box_head(output_memory) + output_proposals
         topk = torch.topk(enc_outputs_class[..., 0], self.two_stage_num_proposals, dim=1)[1]
         if fused and alo_hip.proposal_queries_supported(enc_outputs_coord_unact, topk, memory.dtype, f16=True):
-            reference_points, embed = alo_hip.proposal_queries(enc_outputs_coord_unact, topk, memory.dtype, owner=self.pos_trans.weight)
+            # detached as in the stock branch below (reference :258): the proposals are the decoder's inputs, not a route for gradients
+            reference_points, embed = alo_hip.proposal_queries(enc_outputs_coord_unact.detach(), topk, memory.dtype,
+                                                               owner=self.pos_trans.weight)
         else:
             coords = torch.gather(enc_outputs_coord_unact, 1, topk.unsqueeze(-1).expand(-1, -1, 4)).detach()
             reference_points = coords.sigmoid()

@@ -85,7 +85,7 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
     """
     if isinstance(bn, FrozenBatchNorm2d) and conv.bias is None:
         w, b = folded_conv_bn(conv, bn)
-        if alo_hip.fusable(x, w) and x.is_contiguous(memory_format=torch.channels_last):
+        if alo_hip.fusable(x, w, b, residual) and x.is_contiguous(memory_format=torch.channels_last):
             # inference on the GPU, NHWC activations
             if conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and w.shape[0] % 4 == 0:
                 # a 1x1 convolution over NHWC rows IS a matrix product: hipBLASLt runs it 1.5-6x faster than MIOpen's

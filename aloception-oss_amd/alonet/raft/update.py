@@ -11,11 +11,13 @@ from torch import nn
 import alo_hip
 
 
-def _fusable(*tensors):
+def _fusable(*operands):
     """Inference on the GPU in fp32 with H*W a multiple of 4: the elementwise glue between MIOpen's convolutions (bias,
-    ReLU, the GRU gates) runs as one HIP pass per stage instead of one PyTorch kernel per operation."""
-    t = tensors[0]
-    return alo_hip.fusable(*tensors) and t.dtype == torch.float32 and (t.shape[-1] * t.shape[-2]) % 4 == 0
+    ReLU, the GRU gates) runs as one HIP pass per stage instead of one PyTorch kernel per operation.  ``operands``: the
+    activation, then every other tensor and every module the fused stage reads (alo_hip.fusable) — the passes work in place
+    and have no backward, in ``train()`` mode as in ``eval()``."""
+    t = operands[0]
+    return alo_hip.fusable(*operands) and t.dtype == torch.float32 and (t.shape[-1] * t.shape[-2]) % 4 == 0
 
 
 def _conv_act(conv, x, relu=True):
@@ -70,7 +72,7 @@ class SepConvGRU(nn.Module):
         self.convq2 = nn.Conv2d(c, hidden_dim, (5, 1), padding=(2, 0))
 
     def forward(self, h, x):
-        if _fusable(h, x, self.convz1.weight):
+        if _fusable(h, x, self):
             return self._forward_fused(h, x)
         h = _gru_step(h, x, self.convz1, self.convr1, self.convq1)
         return _gru_step(h, x, self.convz2, self.convr2, self.convq2)
@@ -125,7 +127,7 @@ class BasicMotionEncoder(nn.Module):
         self.conv = nn.Conv2d(64 + 192, 128 - out_planes, 3, padding=1)
 
     def forward(self, flow, corr):
-        if _fusable(flow, corr, self.convc1.weight):
+        if _fusable(flow, corr, self):
             cor = _conv_act(self.convc2, _conv_act(self.convc1, corr))
             flo = _conv_act(self.convf2, _conv_act(self.convf1, flow))
             out = _conv_act(self.conv, torch.cat([cor, flo], dim=1))
@@ -160,7 +162,7 @@ class BasicUpdateBlock(nn.Module):
     def forward(self, net, inp, corr, flow, upsample=True):
         inp = torch.cat([inp, self.encoder(flow, corr)], dim=1)
         net = self.gru(net, inp)
-        if _fusable(net, self.mask[0].weight):
+        if _fusable(net, self.flow_head, self.mask):
             fh, m0, m2 = self.flow_head, self.mask[0], self.mask[2]
             delta_flow = fh.conv2(_conv_act(fh.conv1, net))
             # the 0.25 of the original RAFT (gradient balancing) is folded into the last convolution's weight and bias

@@ -13,7 +13,7 @@ class MLP(nn.Module):
         self.layers = nn.ModuleList(nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:]))
 
     def forward(self, x):
-        if alo_hip.fusable(x, self.layers[0].weight, f16=True):
+        if alo_hip.fusable(x, *self.layers[:-1], f16=True):   # every layer the fused GEMMs stand in for, weight and bias
             # inference on the GPU: the ReLU rides in the GEMM epilogue (streaming MFMA kernel or hipBLASLt)
             for layer in self.layers[:-1]:
                 x = alo_hip.linear_auto(x, layer.weight, layer.bias, relu=True)

@@ -637,3 +637,59 @@ def test_model_with_graph_wrappers_still_pickles_and_deep_copies():
 
     gc.collect()
     assert set(hip_graph._wrappers_of(model)) == {b}
+
+
+def test_fusable_counts_every_parameter_of_a_module_operand():
+    """The predicate behind every fast-path gate: tensors, ``None`` and modules (all their parameters, sub-modules' included) in any
+    mix; grad mode off answers without looking at a flag.  CPU tensors: only the autograd half of the answer is the subject."""
+    import alo_hip
+
+    x = torch.zeros(2, 4)
+    frozen = torch.nn.Sequential(torch.nn.Linear(4, 4), torch.nn.LayerNorm(4)).requires_grad_(False)
+    assert not alo_hip.needs_autograd(x) and not alo_hip.needs_autograd(x, None, frozen, None)
+    for name, p in frozen.named_parameters():   # one trainable parameter anywhere in the module counts, alone
+        p.requires_grad_(True)
+        assert alo_hip.needs_autograd(x, frozen) and alo_hip.needs_autograd(frozen) and alo_hip.needs_autograd(x, None, frozen[0], frozen[1]), name
+        assert not alo_hip.needs_autograd(x, frozen[1 if name.startswith("0.") else 0])
+        assert not alo_hip.fusable(x, frozen)
+        with torch.no_grad():
+            assert not alo_hip.needs_autograd(x, frozen)
+        p.requires_grad_(False)
+    leaf = torch.zeros(3, requires_grad=True)
+    assert alo_hip.needs_autograd(x, frozen, leaf) and alo_hip.needs_autograd(leaf * 2) and not alo_hip.needs_autograd(leaf.detach())
+    # the device / dtype half looks at the first operand only, as before; modules do not change it
+    assert not alo_hip.fusable(x, frozen) and not alo_hip.fusable(x)   # CPU
+    # the wrappers' backstop is the same predicate, with the wrapper's name in the message
+    alo_hip._no_autograd("some_wrapper", x, None, frozen)
+    with pytest.raises(RuntimeError, match=r"alo_hip\.some_wrapper has no backward"):
+        alo_hip._no_autograd("some_wrapper", x, leaf)
+    with torch.no_grad():
+        alo_hip._no_autograd("some_wrapper", x, leaf)
+    # and it comes first: a CPU tensor that requires grad is refused for that, not for its device
+    with pytest.raises(RuntimeError, match=r"alo_hip\.add_layernorm has no backward"):
+        alo_hip.add_layernorm(x, None, leaf.new_ones(4).requires_grad_(), torch.zeros(4))
+
+
+def test_call_site_gates_name_everything_their_fast_path_reads(monkeypatch):
+    """Each gate hands ``alo_hip.fusable`` the modules and tensors its fast path consumes (recorded here on the CPU, where the answer
+    is False anyway and the stock ops run)."""
+    import alo_hip
+    from alonet.detr.backbone import Bottleneck, FrozenBatchNorm2d
+    from alonet.raft.update import BasicUpdateBlock
+    from alonet.transformers.mlp import MLP
+
+    seen = []
+    real = alo_hip.fusable
+    monkeypatch.setattr(alo_hip, "fusable", lambda *ops, **kw: seen.append(ops) or real(*ops, **kw))
+    mlp = MLP(8, 8, 2, 3)
+    mlp(torch.zeros(1, 8))
+    assert [id(o) for o in seen[-1][1:]] == [id(mlp.layers[0]), id(mlp.layers[1])]
+    block = Bottleneck(8, 4, downsample=torch.nn.Sequential(torch.nn.Conv2d(8, 16, 1, bias=False), FrozenBatchNorm2d(16)))
+    seen.clear()
+    block(torch.zeros(1, 8, 4, 4))
+    assert len(seen) == 4 and seen[-1][3] is not None and seen[-1][3].shape == (1, 16, 4, 4)   # conv3's gate sees the identity
+    raft = BasicUpdateBlock(corr_levels=1, corr_radius=1)
+    seen.clear()
+    raft(torch.zeros(1, 128, 4, 4), torch.zeros(1, 128, 4, 4), torch.zeros(1, 9, 4, 4), torch.zeros(1, 2, 4, 4))
+    owners = [[o for o in ops if isinstance(o, torch.nn.Module)] for ops in seen]
+    assert owners == [[raft.encoder], [raft.gru], [raft.flow_head, raft.mask]]
