@@ -24,7 +24,8 @@ ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
 # fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
 # value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
-# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only.  fp16 is opt-in per call site: `fusable`
+# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32 is alo_conv3x3_nhwc's fp32
+# flavour, behind a gate of its own).  fp16 is opt-in per call site: `fusable`
 # and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
 # fp16 kernels do (the transformer's layers), so an fp16 tensor never reaches a kernel that lacks it
 _DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
@@ -1033,6 +1034,59 @@ def conv3x3(x, weight, bias=None, relu=False, stride=1):
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
     _launch("alo_conv3x3_nhwc", x.device, f"conv3x3/C={cin}/s={stride}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
             x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16)
+    return y
+
+
+def conv3x3_f32_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
+    """The shape rules of :func:`conv3x3_supported` for a channels-last fp32 CUDA activation and an fp32 weight."""
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and weight.dim() == 4
+            and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) in ((1, 1), (2, 2)) and tuple(padding) == (1, 1)
+            and tuple(dilation) == (1, 1) and groups == 1 and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0
+            and weight.shape[0] % 64 == 0 and x.is_contiguous(memory_format=torch.channels_last)
+            and not torch.is_grad_enabled())
+
+
+def split_exponent(absmax):
+    """``split_exponent`` of csrc/split_f16.hpp on a tensor of non-negative fp32 magnitudes: the power of two that brings each into
+    [2^14, 2^15); 0 for zero, subnormal and non-finite entries.  -> int32"""
+    e = absmax.contiguous().view(torch.int32) >> 23
+    return torch.where((e == 0) | (e == 255), torch.zeros_like(e), (e - 141).clamp(-110, 110))
+
+
+def _split_conv3x3_weight(weight):
+    """``w_packed`` of an ALO_F32 ``alo_conv3x3_nhwc`` call (include/alo_hotpath.h) as one uint8 tensor: the packed high terms, the
+    packed low terms, the output channels' exponents."""
+    cout, cin = weight.shape[:2]
+    rows = weight.permute(0, 2, 3, 1).reshape(cout, 9 * cin)     # as conv3x3 lays the matrix out
+    mag = rows.abs()
+    k = split_exponent(torch.where(torch.isfinite(mag), mag, torch.zeros_like(mag)).amax(1))
+    scaled = torch.ldexp(rows, -k[:, None])                      # exact
+    hi = scaled.half()
+    lo = (scaled - hi.float()).half()                            # the difference is exact in fp32
+    return torch.cat([_pack_mfma_b(hi.contiguous()).view(torch.uint8).flatten(), _pack_mfma_b(lo.contiguous()).view(torch.uint8).flatten(),
+                      k.view(torch.uint8).flatten()])
+
+
+def conv3x3_f32(x, weight, bias=None, relu=False, stride=1):
+    """``act(F.conv2d(x, weight, bias, stride, 1))`` for a channels-last fp32 ``x`` (N, Cin, H, W) and an fp32 weight, on the fp16
+    matrix cores at fp32-class accuracy (csrc/conv_f32.hip: two-term split of both operands, a power of two per image and per
+    output channel, fp32 accumulation).  Returns a channels-last fp32 (N, Cout, Ho, Wo) tensor."""
+    _no_autograd("conv3x3_f32", x, weight, bias)
+    stride = stride[0] if isinstance(stride, (tuple, list)) else stride
+    if not conv3x3_f32_supported(x, weight, (stride, stride)):
+        raise RuntimeError("conv3x3_f32: needs a channels-last fp32 CUDA activation, an fp32 (Cout, Cin, 3, 3) weight, Cin % 64 == 0, "
+                           "Cout % 64 == 0, stride 1 or 2, no autograd")
+    n, cin, h, w_ = x.shape
+    cout = weight.shape[0]
+    packed = derived(weight, "conv3x3_f32_b", (weight,), lambda: _split_conv3x3_weight(weight))
+    ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
+    y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    bias_c = None if bias is None else bias.float().contiguous()
+    # the split-K bytes of the bf16 call (unused by this kernel) + the per-image magnitudes, rounded up to 256 bytes
+    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, stride) + (4 * n + 255) // 256 * 256
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3_f32/C={cin}/s={stride}", 4.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
+            x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_F32)
     return y
 
 

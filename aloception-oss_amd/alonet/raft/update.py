@@ -4,6 +4,8 @@ Module names follow alonet/raft/update.py (``encoder.{convc1,convc2,convf1,convf
 ``flow_head.{conv1,conv2}``, ``mask.{0,2}``).  ``convc1`` consumes the (B, 324, H/8, W/8) output of the correlation
 lookup kernel.
 """
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -26,6 +28,37 @@ def _conv_act(conv, x, relu=True):
     if not out.is_contiguous():
         out = out.contiguous()
     return alo_hip.bias_act_nchw_(out, conv.bias, relu)
+
+
+def _split_route():
+    """``ALO_RAFT_CONV3X3=split``: the update block's 3x3 convolutions that ``alo_hip.conv3x3_f32`` (fp32 on the fp16 matrix cores,
+    channels-last) runs faster than MIOpen — encoder.convc2, encoder.conv, flow_head.conv1, mask.0 — take it.  Opt-in; read per
+    call, so a test or a benchmark run flips it in-process."""
+    return os.environ.get("ALO_RAFT_CONV3X3") == "split"
+
+
+_CL = torch.channels_last
+
+
+def _conv3x3_split(conv, x, relu, pad_to=None):
+    """``act(conv(x))`` of a 3x3 / padding-1 ``conv`` on a channels-last fp32 ``x`` -> channels-last, bias and ReLU in the kernel's
+    epilogue.  ``pad_to``: the output channels are zero-padded to that many (a multiple of 64; the padded weight and bias are
+    derived once per weight version); the caller slices."""
+    w, b = conv.weight, conv.bias
+    if pad_to is not None and pad_to != w.shape[0]:
+        w, b = alo_hip.derived(conv, f"pad{pad_to}", (conv.weight, conv.bias),
+                               lambda: (F.pad(conv.weight, (0, 0, 0, 0, 0, 0, 0, pad_to - conv.weight.shape[0])).contiguous(),
+                                        F.pad(conv.bias, (0, pad_to - conv.bias.shape[0])).contiguous()))
+    return alo_hip.conv3x3_f32(x, w, b, relu=relu, stride=1)
+
+
+def _conv1x1_to_nhwc(conv, x):
+    """``relu(conv(x))`` of a 1x1 ``conv`` on an NCHW ``x`` -> channels-last: the GEMM reads x transposed instead of a copy."""
+    B, C, H, W = x.shape
+    w2 = conv.weight.view(conv.weight.shape[0], C)
+    rows = torch.matmul(x.view(B, C, H * W).transpose(1, 2), w2.t())                     # (B, HW, Cout) = NHWC
+    alo_hip.bias_act_(rows.view(B * H * W, -1), conv.bias, relu=True)
+    return rows.view(B, H, W, -1).permute(0, 3, 1, 2)
 
 
 class FlowHead(nn.Module):
@@ -126,8 +159,27 @@ class BasicMotionEncoder(nn.Module):
         self.convf2 = nn.Conv2d(128, 64, 3, padding=1)
         self.conv = nn.Conv2d(64 + 192, 128 - out_planes, 3, padding=1)
 
+    def _forward_split(self, flow, corr):
+        """The fused route with convc2 and conv on conv3x3_f32: channels-last from convc1's GEMM (which reads the NCHW lookup
+        transposed) to conv's output.  convf2 stays on MIOpen (a tie at this shape, docs/experiments.md, and its input is NCHW):
+        its output turns channels-last inside the concatenation, and conv's turns NCHW inside the one with the flow."""
+        B, _, H, W = flow.shape
+        cor = _conv3x3_split(self.convc2, _conv1x1_to_nhwc(self.convc1, corr), True)
+        flo = _conv_act(self.convf2, _conv_act(self.convf1, flow))
+        x = torch.empty((B, cor.shape[1] + flo.shape[1], H, W), dtype=flow.dtype, device=flow.device, memory_format=_CL)
+        x[:, :cor.shape[1]].copy_(cor)
+        x[:, cor.shape[1]:].copy_(flo)
+        out = _conv3x3_split(self.conv, x, True, pad_to=128)  # 126 -> 128 output channels
+        k = self.conv.weight.shape[0]
+        enc = torch.empty((B, k + flow.shape[1], H, W), dtype=flow.dtype, device=flow.device)
+        enc[:, :k].copy_(out[:, :k])
+        enc[:, k:].copy_(flow)
+        return enc
+
     def forward(self, flow, corr):
         if _fusable(flow, corr, self):
+            if _split_route() and corr.is_contiguous() and flow.is_contiguous():
+                return self._forward_split(flow, corr)
             cor = _conv_act(self.convc2, _conv_act(self.convc1, corr))
             flo = _conv_act(self.convf2, _conv_act(self.convf1, flow))
             out = _conv_act(self.conv, torch.cat([cor, flo], dim=1))
@@ -164,9 +216,21 @@ class BasicUpdateBlock(nn.Module):
         net = self.gru(net, inp)
         if _fusable(net, self.flow_head, self.mask):
             fh, m0, m2 = self.flow_head, self.mask[0], self.mask[2]
-            delta_flow = fh.conv2(_conv_act(fh.conv1, net))
             # the 0.25 of the original RAFT (gradient balancing) is folded into the last convolution's weight and bias
-            w2, b2 = alo_hip.derived(self, "mask_quarter", (m2.weight, m2.bias), lambda: (0.25 * m2.weight, 0.25 * m2.bias))
+            quarter = lambda: alo_hip.derived(self, "mask_quarter", (m2.weight, m2.bias), lambda: (0.25 * m2.weight, 0.25 * m2.bias))  # noqa: E731
+            if _split_route() and net.is_contiguous():
+                # net goes channels-last once for both heads; flow_head.conv2 (256 -> 2: the kernel would run 64 output channels for
+                # 2 and is slower than MIOpen there, docs/experiments.md) stays on F.conv2d behind one copy back to NCHW; mask.2 (1x1)
+                # reads the channels-last map as the GEMM's transposed operand and writes NCHW
+                B, _, H, W = net.shape
+                net_cl = net.contiguous(memory_format=_CL)
+                delta_flow = fh.conv2(_conv3x3_split(fh.conv1, net_cl, True).contiguous())
+                m = _conv3x3_split(m0, net_cl, True).permute(0, 2, 3, 1).reshape(B, H * W, -1)          # (B, HW, 256): a view
+                w2, b2 = quarter()
+                up_mask = torch.baddbmm(b2.view(1, -1, 1), w2.view(1, w2.shape[0], -1).expand(B, -1, -1), m.transpose(1, 2))
+                return net, up_mask.view(B, -1, H, W), delta_flow
+            delta_flow = fh.conv2(_conv_act(fh.conv1, net))
+            w2, b2 = quarter()
             up_mask = F.conv2d(_conv_act(m0, net), w2, b2, m2.stride, m2.padding)
             return net, up_mask, delta_flow
         delta_flow = self.flow_head(net)

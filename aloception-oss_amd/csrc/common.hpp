@@ -107,6 +107,10 @@ inline RowGather row_gather(int stride = 1, int Ho = 1, int Wo = 1, int H = 1, i
 int linear_shortk_gather(const void* x, const void* weight, const void* bias, const void* residual, void* y, long M, int N, int K,
                          int relu, const RowGather& gather, hipStream_t stream);
 
+// conv_f32.hip: the fp32 flavour of alo_conv3x3_nhwc on checked arguments (w_split and image_mag: alo_hotpath.h); image_mag holds N words.
+int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,
+                int stride, int relu, hipStream_t stream);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

@@ -50,7 +50,8 @@ typedef enum alo_status {
  * alo_ffn256, alo_value_proj_head_major, alo_pack_mfma_b, alo_add_layernorm, alo_bias_act, alo_pos_sine_flat (and the glue of
  * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
- * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only.
+ * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
+ * (alo_conv3x3_nhwc also serves ALO_F32: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -400,6 +401,13 @@ int alo_conv3x3_small_nhwc(const void* x, const void* w_frag, const void* bias32
  * Cin % 64 == 0, Cout % 64 == 0; bias may be NULL.  When the output has too few tiles to fill the chip (the 2048 -> 256 input
  * projection, alonet/deformable_detr/deformable_detr.py:75-84) the reduction is split over the input channels: workspace is then
  * alo_conv3x3_workspace_bytes(...) bytes (0 = not needed; NULL = never split) of fp32 partial sums, added up in a fixed order.
+ *
+ * dtype = ALO_F32: x, bias and y are fp32 and the product runs on the fp16 matrix cores at fp32-class accuracy (the two-term split of
+ * alo_corr_build: a power of two per image, found by a pre-pass inside this call, and one per output channel; three cross products,
+ * fp32 accumulation).  w_packed is then ONE buffer: alo_pack_mfma_b (ALO_F16) of the (Cout, 9 * Cin) matrix of high terms
+ * hi = fp16(w 2^-k_o), the same of the low terms lo = fp16(w 2^-k_o - hi), then the Cout exponents k_o as int32 (k_o brings row o's
+ * largest magnitude into [2^14, 2^15)).  A workspace is REQUIRED: alo_conv3x3_workspace_bytes(...) + 4 * N rounded up to a multiple of
+ * 256 bytes; the extra bytes, behind the others, hold the per-image magnitudes the exponents come from.  Same shape rules, same checks.
  */
 size_t alo_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride);
 int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void* bias, void* y, void* workspace, int N, int H, int W, int Cin,
