@@ -42,6 +42,9 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
     constexpr int kPieces = kK / 8;         // 16-byte pieces per row
     constexpr int kLoads = kRows * kPieces / 256;
     static_assert(kRows * kPieces % 256 == 0, "the tile loader gives every thread the same number of pieces");
+    // The identity is requested ahead of the product at K = 64 and 128.  At K = 256 its 8 x u32x4 beside 128 VGPRs of weights spill
+    // into the tile loop, and warming the lines with one dword each made the launch slower (docs/experiments.md): store_rows loads it.
+    constexpr bool kAhead = HAS_RES && !HM && kK <= 128;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const xbuf = smem;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -91,6 +94,11 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
         __syncthreads();  // the tile is in LDS
         const int next = tile + gridDim.x;
         const bool more = next < dm.tiles;
+        // the identity of THIS tile, in store order: requested here, wanted after the product (fetch_identity of mfma_tile.hpp)
+        u32x4 idn[8];
+        if constexpr (kAhead) {
+            if (has_cols) fetch_identity(idn, R, (long)tile * kRows, dm.M, dm.N, col0, lane);
+        }
         if (more) fetch(next, stage);  // in flight during the MFMAs and the stores below
 
         if (has_cols) {
@@ -135,6 +143,8 @@ linear_shortk_kernel(const T* __restrict__ X, const T* __restrict__ W, const T* 
                         }
                     }
                 }
+            } else if constexpr (kAhead) {
+                store_rows_fetched<T, RELU>(Y, idn, obuf, kOutStride, (long)tile * kRows, dm.M, dm.N, col0, lane);
             } else {
                 store_rows<T, RELU, HAS_RES>(Y, R, obuf, kOutStride, (long)tile * kRows, dm.M, dm.N, col0, lane);
             }

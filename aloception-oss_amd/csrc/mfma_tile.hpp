@@ -90,6 +90,34 @@ __device__ __forceinline__ void store_rows(T* Y, const T* R, const unsigned char
     }
 }
 
+// The same store with the identity fetched AHEAD of the product (linear_shortk_kernel with HAS_RES at K = 64 and 128): inside
+// store_rows the identity loads go out after the tile's MFMAs and the staging fence, one exposed memory round trip per tile and wave.
+// fetch_identity issues them in store_rows' lane order (pass p of lane l = row 8 p + l / 8, 16-byte piece l % 8), rows past the end
+// read from the last row and never stored; the values ride in registers (8 x u32x4) through the product; store_rows_fetched is
+// store_rows' arithmetic on them: add_residual_x8 on the staged, already rounded product, then the activation, one rounding.
+// sched_barrier keeps the compiler from sinking the requests next to their use.
+template <typename T>
+__device__ __forceinline__ void fetch_identity(u32x4 (&idn)[8], const T* R, long grow0, long M, int N, int col0, int lane) {
+#pragma unroll
+    for (int pass = 0; pass < 8; ++pass) {
+        long grow = grow0 + pass * 8 + (lane >> 3);
+        grow = grow < M ? grow : M - 1;
+        idn[pass] = *reinterpret_cast<const u32x4*>(R + grow * N + col0 + (lane & 7) * 8);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <typename T, bool RELU>
+__device__ __forceinline__ void store_rows_fetched(T* Y, const u32x4 (&idn)[8], const unsigned char* obuf, int stride, long grow0, long M,
+                                                   int N, int col0, int lane) {
+#pragma unroll
+    for (int pass = 0; pass < 8; ++pass) {
+        const int row = pass * 8 + (lane >> 3);
+        const long grow = grow0 + row;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(obuf + row * stride + (lane & 7) * 16);
+        if (grow < M) *reinterpret_cast<u32x4*>(Y + grow * N + col0 + (lane & 7) * 8) = add_residual_x8<T, RELU>(v, idn[pass]);
+    }
+}
+
 // ---- weights streamed in MFMA fragment order against an A tile in LDS -------------------------------------------------------------------
 // Weight fragments arrive in batches of KB k-steps (2 column tiles x KB x 16 B per lane) through two register buffers: batch i+1 is
 // requested before batch i is consumed (L2 latency ~ the MFMA time of one batch).  frag0 = this lane's 16 bytes of the first fragment

@@ -360,6 +360,39 @@ def bench_epilogues(N, dtype, reps):
     return out
 
 
+# the launches that end a ResNet bottleneck at the headline's sizes (8 x 800 x 1333): (rows, K, N) of conv3 in layer1 .. layer4
+BOTTLENECK_CONV3 = [(534400, 64, 256), (133600, 128, 512), (33400, 256, 1024), (8350, 512, 2048)]
+
+
+def bench_residual_gemms(reps):
+    """The streaming 1x1 GEMMs with the identity in their epilogue and without it (same x, W, bias and ReLU), every launch timed by its
+    own pair of events: mean and launch-to-launch standard deviation, algorithmic bytes (x + y [+ identity]) and time per byte."""
+    out = []
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for m, k, n in BOTTLENECK_CONV3:
+        x = torch.randn(m, k, device=DEV, generator=g).bfloat16()
+        w = (torch.randn(n, k, device=DEV, generator=g) / k ** 0.5).bfloat16()
+        b = torch.randn(n, device=DEV, generator=g).bfloat16()
+        r = torch.randn(m, n, device=DEV, generator=g).bfloat16()
+        fn = alo_hip.linear_shortk if k <= 256 else alo_hip.linear_packed
+        for res in (None, r):
+            with torch.no_grad():
+                run = lambda: fn(x, w, b, True, residual=res)  # noqa: E731
+                time_launches(run, 1)  # warm-up: clocks, the packed weight
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+                for a, z in ev:
+                    a.record()
+                    run()
+                    z.record()
+                torch.cuda.synchronize()
+            us = torch.tensor([a.elapsed_time(z) * 1e3 for a, z in ev], dtype=torch.float64)
+            nbytes = 2 * (m * k + m * n * (1 if res is None else 2))
+            out.append(dict(kernel=fn.__name__, M=m, K=k, N=n, identity=res is not None, us_mean=us.mean().item(), us_std=us.std().item(),
+                            us_min=us.min().item(), alg_bytes=nbytes, ps_per_byte=us.mean().item() * 1e6 / nbytes,
+                            GBps=nbytes / us.mean().item() / 1e3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="msda_enc,msda_dec,msda_rand,msda_bwd,corr_build,corr_lookup")
@@ -410,6 +443,8 @@ def main():
             res = [bench_corr_lookup(a.B, a.reps)]
         elif w == "alt_corr_lookup":
             res = bench_alt_corr_lookup(a.B, a.reps)
+        elif w == "residual_gemms":   # conv3 of the four ResNet stages with and without the identity
+            res = bench_residual_gemms(max(a.reps, 50))
         elif w == "epilogues":
             res = [r for dt in dts for r in bench_epilogues(a.N, dt, a.reps)]
         for r in res:
