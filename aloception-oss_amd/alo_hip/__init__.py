@@ -298,15 +298,21 @@ class _timed:
                 _timer.relaunch[self.tag] = self.relaunch
 
 
+def _pointers(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 def _launch(symbol, device, tag, nbytes, flops, *args, relaunch=False):
     """Enqueue entry point ``symbol`` on ``device``'s current torch stream: what ``alo::launch`` is to csrc.  A tensor in ``args``
-    stands for its device pointer (it is alive for the call), ``None`` for a null pointer, everything else is passed as it is; the
-    stream goes last.  The call is timed under ``tag`` (``None``: untimed) with its algorithmic ``nbytes`` / ``flops``; with
+    stands for its device pointer (it is alive for the call), a list of tensors for a host array of their device pointers (built for
+    the call), ``None`` for a null pointer, everything else is passed as it is (ctypes arrays are host data); the stream goes last.
+    The call is timed under ``tag`` (``None``: untimed) with its algorithmic ``nbytes`` / ``flops``; with
     ``relaunch`` a running :class:`LaunchTimer` also gets a closure that repeats the call and keeps ``args`` alive for that."""
     fn = getattr(lib(), symbol)
 
     def call():
-        _check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], _stream(device)))
+        _check(fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else _pointers(a) if isinstance(a, list) else a for a in args],
+                  _stream(device)))
 
     with torch.cuda.device(device), _timed(tag, nbytes, flops, relaunch=call if relaunch and _timer else None):
         call()
@@ -567,17 +573,16 @@ def corr_build(fmap1, fmap2, num_levels=4):
     levels = [torch.empty((B * H * W, 1, h, w), dtype=torch.float32, device=fmap1.device) for h, w in shapes]
     nbytes = lib().alo_corr_build_workspace_bytes(B, C, H, W, num_levels)
     ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=fmap1.device)
-    ptrs = (ctypes.c_void_p * num_levels)(*[t.data_ptr() for t in levels])
     ncols = sum(h * w for h, w in shapes)
     # relaunch: the closure keeps the feature maps and the workspace alive for LaunchTimer.replay_samples
     _launch("alo_corr_build", fmap1.device, "corr_build", 4.0 * (2 * B * C * H * W + B * H * W * ncols), 2.0 * B * (H * W) * (H * W) * C,
-            fmap1, fmap2, ptrs, ws, nbytes, B, C, H, W, num_levels, relaunch=True)
+            fmap1, fmap2, levels, ws, nbytes, B, C, H, W, num_levels, relaunch=True)
     # ws may be released now: the caching allocator keeps the block bound to this stream until the kernels retire
     return levels
 
 
 def _corr_lookup_args(levels, levels_name, coords, radius, grad_out=None, fn=None):
-    """What the three lookup entry points check alike -> (coords, grad_out) contiguous, the level pointers, (B, H, W, L).
+    """What the three lookup entry points check alike -> (coords, grad_out) contiguous, the levels as a list, (B, H, W, L).
     ``fn``: the name the backward entry points put before their message on coords / grad_out."""
     _require_f32_cuda("coords", coords, 4)
     coords = coords.contiguous()
@@ -595,16 +600,16 @@ def _corr_lookup_args(levels, levels_name, coords, radius, grad_out=None, fn=Non
         _require_f32_cuda(f"{levels_name}[{lvl}]", t, 4)
         if not t.is_contiguous() or t.shape[0] != B * H * W:
             raise RuntimeError(f"{levels_name}[{lvl}] must be a contiguous (B*H*W,1,h,w) tensor")
-    return coords, grad_out, (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels]), (B, H, W, L)
+    return coords, grad_out, list(levels), (B, H, W, L)
 
 
 def corr_lookup(levels, coords, radius=4):
     """levels from :func:`corr_build`, coords (B,2,H,W) -> (B, L*(2r+1)^2, H, W) float32  (corr.py:29-50)."""
-    coords, _, ptrs, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius)
+    coords, _, levels, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius)
     out = torch.empty((B, L * (2 * radius + 1) ** 2, H, W), dtype=torch.float32, device=coords.device)
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2)
-    _launch("alo_corr_lookup", coords.device, "corr_lookup", nbytes, 0.0, ptrs, coords, out, B, H, W, radius, L)
+    _launch("alo_corr_lookup", coords.device, "corr_lookup", nbytes, 0.0, levels, coords, out, B, H, W, radius, L)
     return out
 
 
@@ -612,23 +617,23 @@ def corr_lookup_backward(grad_levels, coords, grad_out, radius=4):
     """Adds the pyramid gradients of ONE lookup to ``grad_levels`` (tensors shaped like the pyramid, zeroed by the caller before the
     first lookup whose gradients are to be summed): the adjoint of :func:`corr_lookup` with respect to the levels (autograd through
     the reference's bilinear_sampler, corr.py:29-50).  In place; returns ``grad_levels``."""
-    coords, grad_out, ptrs, (B, H, W, L) = _corr_lookup_args(grad_levels, "grad_levels", coords, radius, grad_out,
+    coords, grad_out, maps, (B, H, W, L) = _corr_lookup_args(grad_levels, "grad_levels", coords, radius, grad_out,
                                                              "corr_lookup_backward")
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + 2 * L * taps + 2)
-    _launch("alo_corr_lookup_backward", coords.device, "corr_lookup_backward", nbytes, 0.0, ptrs, coords, grad_out, B, H, W, radius, L)
+    _launch("alo_corr_lookup_backward", coords.device, "corr_lookup_backward", nbytes, 0.0, maps, coords, grad_out, B, H, W, radius, L)
     return grad_levels
 
 
 def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
     """Gradient of :func:`corr_lookup` with respect to ``coords`` -> (B, 2, H, W): grid_sample's gradient with respect to the grid
     chained through the reference's coordinate arithmetic (corr.py:29-50); per-level maps from the kernel, added here."""
-    coords, grad_out, ptrs, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius, grad_out,
+    coords, grad_out, levels, (B, H, W, L) = _corr_lookup_args(levels, "corr_pyramid", coords, radius, grad_out,
                                                              "corr_lookup_backward_coords")
     per_level = torch.empty((B, L, 2, H, W), dtype=torch.float32, device=coords.device)
     taps = (2 * radius + 2) ** 2
     nbytes = 4.0 * B * H * W * (L * (2 * radius + 1) ** 2 + L * taps + 2 + 2 * L)
-    _launch("alo_corr_lookup_backward_coords", coords.device, "corr_lookup_backward_coords", nbytes, 0.0, ptrs, coords, grad_out,
+    _launch("alo_corr_lookup_backward_coords", coords.device, "corr_lookup_backward_coords", nbytes, 0.0, levels, coords, grad_out,
             per_level, B, H, W, radius, L)
     return per_level.sum(1)
 
@@ -648,9 +653,8 @@ def corr_alt_prepare(fmap1, fmap2_levels):
     levels = [t.contiguous() for t in fmap2_levels]
     nbytes = lib().alo_corr_alt_workspace_bytes(B, C, H, W, L)   # 0 past the limits: the call below says which
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=fmap1.device)
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in levels])
     moved = 4.0 * 2 * (fmap1.numel() + sum(t.numel() for t in levels))
-    _launch("alo_corr_alt_prepare", fmap1.device, "corr_alt_prepare", moved, 0.0, fmap1, ptrs, ws, nbytes, B, C, H, W, L)
+    _launch("alo_corr_alt_prepare", fmap1.device, "corr_alt_prepare", moved, 0.0, fmap1, levels, ws, nbytes, B, C, H, W, L)
     return ws
 
 
