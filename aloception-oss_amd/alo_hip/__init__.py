@@ -24,8 +24,8 @@ ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
 # fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
 # value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
-# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32 is alo_conv3x3_nhwc's fp32
-# flavour, behind a gate of its own).  fp16 is opt-in per call site: `fusable`
+# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32, linear_f32 and
+# conv1x1_strided_f32 are the fp32 flavours of three of them, each behind a gate of its own).  fp16 is opt-in per call site: `fusable`
 # and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
 # fp16 kernels do (the transformer's layers), so an fp16 tensor never reaches a kernel that lacks it
 _DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
@@ -943,10 +943,108 @@ def conv1x1_strided(x, weight2d, bias, stride, relu=False):
     return y
 
 
+# ---- fp32 linear layers and 1x1 convolutions on the fp16 matrix cores (alo_linear_packed / alo_conv1x1_nhwc with ALO_F32) -----------
+def f32_layers_split():
+    """``ALO_F32_LAYERS=split``: at inference the fp32 linear layers, 1x1 and 3x3 convolutions that the split kernels serve
+    (:func:`linear_f32`, :func:`conv1x1_strided_f32`, :func:`conv3x3_f32`: fp32 on the fp16 matrix cores, two-term splits of both
+    operands) take them instead of hipBLASLt / MIOpen.  Read per call; unset, every route is what it was."""
+    return os.environ.get("ALO_F32_LAYERS") == "split"
+
+
+# (K, N) -> the rows M at which linear_f32 beat hipBLASLt by more than both spreads (tools/gemmbench_f32.py on MI355X at the fp32
+# headline's shapes; docs/experiments.md, section "`linear_f32`"), kernel / stock medians in the comments.  An M that was not measured
+# goes by the nearest one that was.  Off the route because they lost or tied, K-N at M: 256-64 at 534400 (1.16), 256-128 at 534400
+# (0.96, inside the spreads), 256-256 at 177784 (1.09), 256-1024 at 2400 (1.01), 512-256 at 133600 (1.13), 1024-256 at 33600 / 177784 /
+# 2400 (1.41 / 1.33 / 2.45), 1024-512 at 33600 (1.00), 2048-256 at 8400 (1.89), 2048-512 at 8400 (1.15): the kernel streams its weights
+# once per 64 rows, and hipBLASLt's fp32 GEMM is within a sixth of the fp32 peak at long K.
+_F32_ROUTED = {
+    (64, 64): (0, None),          # 0.73 at 534400
+    (64, 256): (0, None),         # 0.90 at 534400
+    (256, 128): (0, 1 << 18),     # 0.91 at 177784
+    (256, 256): (0, 1 << 14),     # 0.84 at 2400
+    (256, 384): (0, None),        # 0.95 at 177784
+    (256, 512): (0, None),        # 0.86 at 2400
+    (256, 1024): (1 << 14, None), # 0.96 at 177784
+    (512, 128): (0, None),        # 0.98 at 133600
+}
+
+
+def _f32_gemm_routed(M, K, N, identity):
+    """Whether ``ALO_F32_LAYERS=split`` sends a (M, K) x (N, K) product to :func:`linear_f32`.  With an identity to add the kernel won
+    everywhere it was measured (K = 64, 128, 256, 512: 0.65, 0.64, 0.71, 0.74 of hipBLASLt + the separate add / ReLU pass); without
+    one the table above decides."""
+    if identity:
+        return K <= 512
+    lo, hi = _F32_ROUTED.get((K, N), (0, 0))
+    return M >= lo and (hi is None or M < hi)
+
+
+def linear_f32_supported(x, weight):
+    """fp32 CUDA input and fp32 (N, K) weight, K % 64 == 0, N % 64 == 0, no autograd on either."""
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2 and x.dim() >= 1
+            and x.shape[-1] == weight.shape[1] and weight.shape[1] % 64 == 0 and weight.shape[0] % 64 == 0 and weight.shape[0] > 0
+            and weight.shape[1] > 0 and not needs_autograd(x, weight))
+
+
+def linear_f32_routed(x, weight, identity=False):
+    """Whether :func:`linear_auto` sends this product to :func:`linear_f32`: the switch is set, the kernel serves the operands and
+    the shape is one it was measured to win at."""
+    return (f32_layers_split() and linear_f32_supported(x, weight)
+            and _f32_gemm_routed(x.numel() // max(x.shape[-1], 1), weight.shape[1], weight.shape[0], identity))
+
+
+def _split_weight_of(weight):
+    """The split copy of an fp32 (N, K) weight, riding on the weight (:func:`derived`): split once per weight version."""
+    return derived(weight, "linear_f32_b", (weight,), lambda: _split_weight(weight))
+
+
+def linear_f32(x, weight, bias=None, relu=False, residual=None):
+    """``act(F.linear(x, weight, bias) [+ residual])`` for fp32 tensors on the fp16 matrix cores at fp32-class accuracy
+    (csrc/gemm_f32.hip: two-term split of both operands, a power of two per row of ``x`` and per output channel, fp32
+    accumulation); ``residual`` has the shape of the result and is added before the activation."""
+    _no_autograd("linear_f32", x, weight, bias, residual)
+    if not linear_f32_supported(x, weight):
+        raise RuntimeError("linear_f32: needs fp32 CUDA tensors, a (N, K) weight, K % 64 == 0, N % 64 == 0, no autograd")
+    N, K = weight.shape
+    x2 = x.reshape(-1, K)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    M = x2.shape[0]
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    if residual is not None:
+        residual = residual.reshape(M, N)
+        if residual.dtype != x.dtype or not residual.is_contiguous():
+            raise RuntimeError("linear_f32: residual must be a contiguous (M, N) fp32 tensor")
+    if M:
+        bias_c = None if bias is None else bias.float().contiguous()
+        _launch("alo_linear_packed", x.device, f"linear_f32/K={K}/N={N}", 4.0 * (M * K + M * N * (2 if residual is not None else 1)),
+                2.0 * M * N * K, x2, _split_weight_of(weight), bias_c, residual, y, M, N, K, 1 if relu else 0, ALO_F32)
+    return y.view(*x.shape[:-1], N)
+
+
+def conv1x1_strided_f32(x, weight2d, bias, stride, relu=False):
+    """``act(F.conv2d(x, weight2d[:, :, None, None], bias, stride))`` for a channels-last fp32 ``x`` on :func:`linear_f32`'s kernel,
+    which addresses the kept pixels itself; returns channels-last."""
+    _no_autograd("conv1x1_strided_f32", x, weight2d, bias)
+    if not (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and stride >= 1
+            and linear_f32_supported(x.permute(0, 2, 3, 1), weight2d)):
+        raise RuntimeError("conv1x1_strided_f32: needs a channels-last fp32 CUDA activation, an fp32 (Cout, Cin) weight, Cin % 64 == 0, "
+                           "Cout % 64 == 0, no autograd")
+    n, cin, h, w_ = x.shape
+    cout = weight2d.shape[0]
+    ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
+    y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if y.numel():
+        bias_c = None if bias is None else bias.float().contiguous()
+        _launch("alo_conv1x1_nhwc", x.device, f"conv1x1_strided_f32/K={cin}/N={cout}", 4.0 * (y.numel() // cout * cin + y.numel()),
+                2.0 * y.numel() * cin, x, _split_weight_of(weight2d), 1, bias_c, None, y, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_F32)
+    return y
+
+
 def linear_auto(x, weight, bias=None, relu=False, residual=None):
     """Inference-time ``act(F.linear(x, weight, bias) [+ residual])``: the streaming MFMA kernels when the shape allows it
     (bf16 / fp16; K in {64, 128, 256} with N % 64 == 0, or K % 256 == 0 with N % 128 == 0), otherwise the stock GEMM with the bias /
-    ReLU epilogue."""
+    ReLU epilogue — or, for fp32 operands under ``ALO_F32_LAYERS=split``, :func:`linear_f32`."""
     _no_autograd("linear_auto", x, weight, bias, residual)
     if linear_shortk_supported(x, weight, f16=True) and (bias is None or bias.dtype == x.dtype):
         return linear_shortk(x, weight, bias, relu, residual=residual)
@@ -955,6 +1053,8 @@ def linear_auto(x, weight, bias=None, relu=False, residual=None):
         # measured on MI355X at the backbone's shapes: the streaming kernel wins with many output columns, with the identity
         # fused in, and at (N, K) = (128, 512); hipBLASLt wins the rest
         return linear_packed(x, weight, bias, relu, residual=residual)
+    if linear_f32_routed(x, weight, residual is not None):
+        return linear_f32(x, weight, bias, relu, residual=residual)
     x2 = x.reshape(-1, x.shape[-1])
     fused_act = relu and residual is None
     if bias is not None:
@@ -1057,14 +1157,17 @@ def split_exponent(absmax):
     return torch.where((e == 0) | (e == 255), torch.zeros_like(e), (e - 141).clamp(-110, 110))
 
 
-def _split_conv3x3_weight(weight):
-    """``w_packed`` of an ALO_F32 ``alo_conv3x3_nhwc`` call (include/alo_hotpath.h) as one uint8 tensor: the packed high terms, the
-    packed low terms, the output channels' exponents."""
-    cout, cin = weight.shape[:2]
-    rows = weight.permute(0, 2, 3, 1).reshape(cout, 9 * cin)     # as conv3x3 lays the matrix out
+def _split_weight(weight):
+    """``w_packed`` of an ALO_F32 call of ``alo_conv3x3_nhwc`` (a (Cout, Cin, 3, 3) weight), ``alo_linear_packed`` or
+    ``alo_conv1x1_nhwc`` (a (N, K) weight) as one uint8 tensor (include/alo_hotpath.h): the packed high terms, the packed low terms,
+    the output channels' exponents."""
+    if weight.dim() == 4:
+        weight = weight.permute(0, 2, 3, 1).reshape(weight.shape[0], -1)   # as conv3x3 lays the matrix out
+    rows = weight.float()
     mag = rows.abs()
     k = split_exponent(torch.where(torch.isfinite(mag), mag, torch.zeros_like(mag)).amax(1))
-    scaled = torch.ldexp(rows, -k[:, None])                      # exact
+    scaled = rows * ((127 - k) << 23).view(torch.float32)[:, None]   # 2^-k built from its bits: exact (torch.ldexp on the GPU multiplies
+                                                                     # by a computed power, and is off by an ulp on most elements)
     hi = scaled.half()
     lo = (scaled - hi.float()).half()                            # the difference is exact in fp32
     return torch.cat([_pack_mfma_b(hi.contiguous()).view(torch.uint8).flatten(), _pack_mfma_b(lo.contiguous()).view(torch.uint8).flatten(),
@@ -1082,7 +1185,7 @@ def conv3x3_f32(x, weight, bias=None, relu=False, stride=1):
                            "Cout % 64 == 0, stride 1 or 2, no autograd")
     n, cin, h, w_ = x.shape
     cout = weight.shape[0]
-    packed = derived(weight, "conv3x3_f32_b", (weight,), lambda: _split_conv3x3_weight(weight))
+    packed = derived(weight, "conv3x3_f32_b", (weight,), lambda: _split_weight(weight))
     ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.float().contiguous()

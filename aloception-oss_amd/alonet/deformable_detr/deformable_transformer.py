@@ -62,8 +62,10 @@ def _self_attention(mha, qk_in, v_in):
     B, L, E = qk_in.shape
     H = mha.num_heads
     w, b = mha.in_proj_weight, mha.in_proj_bias
-    qk = alo_hip.linear_auto(qk_in, w[: 2 * E], None if b is None else b[: 2 * E])
-    v = alo_hip.linear_auto(v_in, w[2 * E:], None if b is None else b[2 * E:])
+    # the SAME row slices every call (inference only: _fused_ok): what linear_auto derives from a weight rides on the tensor object
+    w_qk, w_v = alo_hip.derived(mha, "in_proj_rows", (w,), lambda: (w[: 2 * E], w[2 * E:]))
+    qk = alo_hip.linear_auto(qk_in, w_qk, None if b is None else b[: 2 * E])
+    v = alo_hip.linear_auto(v_in, w_v, None if b is None else b[2 * E:])
     q, k = qk[..., :E], qk[..., E:]
     heads = lambda t: t.reshape(B, L, H, E // H).transpose(1, 2)  # (B, H, L, E/H)
     out = F.scaled_dot_product_attention(heads(q), heads(k), heads(v))

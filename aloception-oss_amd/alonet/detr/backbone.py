@@ -52,6 +52,11 @@ def conv1x1_as_gemm(x, weight, bias, stride=(1, 1), relu=False, residual=None):
                 and alo_hip.conv1x1_strided_supported(x, _weight_2d(weight))):
             # the streaming GEMM addresses the kept pixels itself: no gathered copy of a quarter of the map
             return alo_hip.conv1x1_strided(x, _weight_2d(weight), bias, stride[0], relu)
+        if (stride[0] == stride[1] and residual is None and alo_hip.f32_layers_split() and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last)
+                and alo_hip.linear_f32_supported(x.permute(0, 2, 3, 1), _weight_2d(weight)) and not alo_hip.needs_autograd(bias)):
+            # ALO_F32_LAYERS=split: the same, in fp32 on the split kernel
+            return alo_hip.conv1x1_strided_f32(x, _weight_2d(weight), bias, stride[0], relu)
         x = x[:, :, ::stride[0], ::stride[1]]
     n, cin, h, w_ = x.shape
     rows = x.permute(0, 2, 3, 1).reshape(-1, cin)  # a view for stride 1 (NHWC rows are contiguous), one gather otherwise
@@ -94,7 +99,8 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
                 w2 = _weight_2d(w)
                 if residual is None or (tuple(conv.stride) == (1, 1) and residual.is_contiguous(memory_format=torch.channels_last)
                                         and (alo_hip.linear_shortk_supported(rows_probe, w2)
-                                             or alo_hip.linear_packed_supported(rows_probe, w2))):
+                                             or alo_hip.linear_packed_supported(rows_probe, w2)
+                                             or alo_hip.linear_f32_routed(rows_probe, w2, identity=True))):
                     # bias + identity + ReLU ride in the epilogue of the streaming GEMM
                     return conv1x1_as_gemm(x, w, b, conv.stride, relu=relu, residual=residual)
                 out = conv1x1_as_gemm(x, w, None, conv.stride)
@@ -102,6 +108,12 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
             if residual is None and alo_hip.conv3x3_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
                 # the bottleneck's 3x3: implicit GEMM on MFMA, bias + ReLU in its epilogue (2-3.5x MIOpen at these shapes)
                 return alo_hip.conv3x3(x, w, b, relu, conv.stride)
+            if (residual is None and alo_hip.f32_layers_split() and not (conv.stride == (2, 2) and w.shape[1] == 256)
+                    and alo_hip.conv3x3_f32_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups)):
+                # ALO_F32_LAYERS=split: the fp32 bottleneck's 3x3 on the fp16 matrix cores, bias + ReLU in its epilogue: 0.27-0.79 of
+                # MIOpen + bias_act_ at six of the seven shapes of the fp32 headline (tools/gemmbench_f32.py; docs/experiments.md,
+                # "`linear_f32`").  Off the route: layer3.0.conv2, 256 channels at stride 2 on 100 x 167, 462 us against 416 (1.11)
+                return alo_hip.conv3x3_f32(x, w, b, relu, conv.stride)
             if relu or residual is not None:
                 # bias (+ identity) + ReLU are ONE in-place pass over the convolution output instead of MIOpen's separate
                 # bias kernel followed by add / relu kernels

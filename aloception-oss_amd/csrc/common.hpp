@@ -111,6 +111,11 @@ int linear_shortk_gather(const void* x, const void* weight, const void* bias, co
 int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,
                 int stride, int relu, hipStream_t stream);
 
+// gemm_f32.hip: the fp32 flavour of alo_linear_packed / alo_conv1x1_nhwc on checked arguments (w_split: alo_hotpath.h); `what` names the
+// entry point in a launch error.
+int linear_f32(const void* x, const void* w_split, const void* bias, const void* residual, void* y, long M, int N, int K, int relu,
+               const RowGather& gather, hipStream_t stream, const char* what);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

@@ -1,5 +1,5 @@
 // Y (M, N) = act(X (M, K) @ W (N, K)^T + bias [+ R]), bf16 (or, for alo_linear_packed, fp16) with fp32 accumulation, K a multiple of
-// 256, N of 128: the backbone's 1x1
+// 256, N of 128 (dtype = ALO_F32 of either entry point: gemm_f32.hip): the backbone's 1x1
 // convolutions with many input channels (512 / 1024 / 2048; alonet/detr/backbone.py:19-47 + torchvision Bottleneck.conv1 / conv3 /
 // downsample) and the 1x1 input projections (alonet/deformable_detr/deformable_detr.py:75-84) over NHWC rows.
 //
@@ -141,9 +141,16 @@ using namespace alo;
 
 extern "C" int alo_linear_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, long M,
                                  int N, int K, int relu, int dtype, void* stream) {
-    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_linear_packed: bf16 / fp16 only (dtype %d)", dtype);
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED,
+                "alo_linear_packed: bf16 / fp16, or fp32 with split weights, only (dtype %d)", dtype);
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: null pointer argument");
     ALO_REQUIRE(M > 0 && N > 0 && K > 0, ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: sizes must be positive");
+    if (dtype == ALO_F32) {   // gemm_f32.hip: w_packed is the split layout of alo_hotpath.h
+        ALO_REQUIRE(K % 64 == 0 && N % 64 == 0, ALO_ERR_UNSUPPORTED, "alo_linear_packed: fp32 needs K and N to be multiples of 64 (K=%d N=%d)", K, N);
+        ALO_REQUIRE(aligned16(x, w_packed, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: pointers must be 16-byte aligned");
+        ALO_REQUIRE((M + 63) / 64 < (1L << 28), ALO_ERR_UNSUPPORTED, "alo_linear_packed: too many rows");
+        return linear_f32(x, w_packed, bias, residual, y, M, N, K, relu, row_gather(), static_cast<hipStream_t>(stream), "alo_linear_packed");
+    }
     ALO_REQUIRE(K % 256 == 0 && N % 128 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_linear_packed: K must be a multiple of 256 and N of 128 (K=%d N=%d)", K, N);
     ALO_REQUIRE(aligned16(x, w_packed, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_linear_packed: pointers must be 16-byte aligned");
@@ -157,12 +164,20 @@ extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is
                                 void* y, int N, int H, int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream) {
     ALO_REQUIRE(x && weight && y, ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0 && stride >= 1, ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: N, H, W, stride must be positive");
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: bf16 only (dtype %d)", dtype);
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED,
+                "alo_conv1x1_nhwc: bf16 only, or fp32 with split packed weights (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(x, weight, y, residual), ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: pointers must be 16-byte aligned");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     const long M = (long)N * Ho * Wo;
     ALO_REQUIRE((long)H * W < (1L << 30), ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: map too large");
     const RowGather gather = row_gather(stride, Ho, Wo, H, W);
+    if (dtype == ALO_F32) {   // gemm_f32.hip behind the same row addressing
+        ALO_REQUIRE(weight_is_packed, ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: fp32 takes the split packed weight only (weight_is_packed = 1)");
+        ALO_REQUIRE(Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 64 == 0, ALO_ERR_UNSUPPORTED,
+                    "alo_conv1x1_nhwc: fp32 needs Cin and Cout to be multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
+        ALO_REQUIRE((M + 63) / 64 < (1L << 28), ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: too many output pixels");
+        return linear_f32(x, weight, bias, residual, y, M, Cout, Cin, relu, gather, static_cast<hipStream_t>(stream), "alo_conv1x1_nhwc");
+    }
     if (!weight_is_packed) {
         ALO_REQUIRE(Cout % 64 == 0, ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: Cout must be a multiple of 64 (got %d)", Cout);
         return linear_shortk_gather(x, weight, bias, residual, y, M, Cout, Cin, relu, gather, static_cast<hipStream_t>(stream));

@@ -51,7 +51,7 @@ typedef enum alo_status {
  * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
  * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
- * (alo_conv3x3_nhwc also serves ALO_F32: see there).
+ * (alo_conv3x3_nhwc, alo_linear_packed and alo_conv1x1_nhwc also serve ALO_F32: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -369,6 +369,13 @@ int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, co
  * alo_linear_packed: y (M, N) = act(x (M, K) @ w (N, K)^T + bias [+ residual]) for the long-K 1x1 convolutions of the backbone and the
  * 1x1 input projections over NHWC rows (alonet/detr/backbone.py:19-47, deformable_detr.py:75-84): bf16 or fp16, fp32 accumulation,
  * K % 256 == 0, N % 128 == 0.  w_packed = alo_pack_mfma_b(w).  residual (M, N) or NULL is added before the activation.
+ *
+ * dtype = ALO_F32: x, bias, residual and y are fp32 and the product runs on the fp16 matrix cores at fp32-class accuracy (the two-term
+ * split of alo_conv3x3_nhwc's fp32 flavour, below): one power of two per ROW of x, found inside the call (a row's result does not
+ * depend on the other rows; an Inf / NaN element spoils exactly its own row), and one per output channel; three cross products, fp32
+ * accumulation, the residual added in fp32 before the activation.  w_packed is then ONE buffer, the layout of that flavour for a (N, K)
+ * matrix: alo_pack_mfma_b (ALO_F16) of the high terms hi = fp16(w 2^-k_o), the same of the low terms lo = fp16(w 2^-k_o - hi), then
+ * the N exponents k_o as int32 (k_o brings row o's largest magnitude into [2^14, 2^15)).  K % 64 == 0, N % 64 == 0; no workspace.
  */
 int alo_linear_packed(const void* x, const void* w_packed, const void* bias, const void* residual, void* y, long M, int N, int K,
                       int relu, int dtype, void* stream);
@@ -378,7 +385,9 @@ int alo_linear_packed(const void* x, const void* w_packed, const void* bias, con
  * `downsample` convolutions of the bottlenecks (alonet/detr/backbone.py:84-92; torchvision Bottleneck) without a gathered copy of the
  * kept pixels — the tile loader of alo_linear_shortk (weight (Cout, Cin) row-major, weight_is_packed = 0, Cin in {64, 128, 256}) or
  * alo_linear_packed (weight = alo_pack_mfma_b(w), weight_is_packed = 1, Cin % 256 == 0, Cout % 128 == 0) addresses pixel
- * (n, stride * yo, stride * xo) itself.  Ho = (H - 1) / stride + 1.  residual (N, Ho, Wo, Cout) or NULL.  bf16 only.
+ * (n, stride * yo, stride * xo) itself.  Ho = (H - 1) / stride + 1.  residual (N, Ho, Wo, Cout) or NULL.  bf16 only —
+ * but for dtype = ALO_F32 with weight_is_packed = 1: alo_linear_packed's fp32 flavour (its split weight buffer, fp32 x, bias, residual
+ * and y, Cin % 64 == 0, Cout % 64 == 0) behind the same pixel addressing; weight_is_packed = 0 is refused in fp32.
  */
 int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual, void* y, int N,
                      int H, int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream);
