@@ -1109,6 +1109,61 @@ def ffn256(x, w1, b1, w2, b2):
     return y.view(x.shape)
 
 
+# ---- the fp32 feed-forward block in one kernel on the fp16 matrix cores (alo_ffn256 with ALO_F32) ----------------------------------
+# The widest hidden layer whose LDS frame fits (csrc/ffn_f32.hip: two split 64 x 256 tiles of 66560 bytes, (F + 256) x 8 bytes of
+# biases and exponents, 1280 bytes of row tables, against alo::launch's 160 KiB); the entry point refuses the next multiple of 256.
+FFN_F32_MAX_HIDDEN = 3328
+
+
+def ffn_f32_supported(x, w1, w2):
+    """fp32 CUDA input with last dimension 256, an fp32 (F, 256) ``w1`` with F % 256 == 0 and F <= :data:`FFN_F32_MAX_HIDDEN`, an
+    fp32 (256, F) ``w2``, no autograd on any of them."""
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 1 and x.shape[-1] == 256 and w1.dtype == torch.float32
+            and w2.dtype == torch.float32 and w1.dim() == 2 and w1.shape[1] == 256 and w1.shape[0] % 256 == 0
+            and 0 < w1.shape[0] <= FFN_F32_MAX_HIDDEN and w2.dim() == 2 and tuple(w2.shape) == (256, w1.shape[0])
+            and not needs_autograd(x, w1, w2))
+
+
+# F -> the rows M at which ffn_f32 beat the two launches that _ffn otherwise makes on the split route (linear_auto twice) by more than
+# both spreads (tools/gemmbench_f32.py on MI355X at the fp32 headline's shapes; docs/experiments.md, section "`ffn_f32`"), kernel /
+# stock medians in the comments.  An M that was not measured goes by the nearest one that was; an F that was not measured is not
+# routed.  Off the route: F = 1024 at M = 2400 (0.96, inside the spreads: one tile per workgroup on 38 of 256 CUs).
+_FFN_F32_ROUTED = {
+    1024: (1 << 14, None),        # 0.45 at 177784
+    2048: (0, None),              # 0.54 at 8400
+}
+
+
+def ffn_f32_routed(x, w1, w2):
+    """Whether the transformer's feed-forward block takes :func:`ffn_f32`: the switch is set (:func:`f32_layers_split`), the kernel
+    serves the operands and (F, M) is a shape it was measured to win at."""
+    if not (f32_layers_split() and ffn_f32_supported(x, w1, w2)):
+        return False
+    lo, hi = _FFN_F32_ROUTED.get(w1.shape[0], (0, 0))
+    M = x.numel() // 256
+    return M >= lo and (hi is None or M < hi)
+
+
+def ffn_f32(x, w1, b1, w2, b2):
+    """``relu(x @ w1.T + b1) @ w2.T + b2`` over the last dim (= 256) of an fp32 ``x`` in one kernel on the fp16 matrix cores at
+    fp32-class accuracy (csrc/ffn_f32.hip: :func:`linear_f32`'s two-term splits, a power of two per row of ``x`` and per row and
+    256-unit chunk of the hidden activation, which never leaves the chip)."""
+    _no_autograd("ffn_f32", x, w1, b1, w2, b2)
+    if not ffn_f32_supported(x, w1, w2):
+        raise RuntimeError(f"ffn_f32: needs fp32 CUDA tensors, d_model = 256, a hidden width that is a multiple of 256 and at most "
+                           f"{FFN_F32_MAX_HIDDEN}, no autograd")
+    x2 = x.reshape(-1, 256)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    y = torch.empty_like(x2)
+    M, Fh = x2.shape[0], w1.shape[0]
+    if M:
+        _launch("alo_ffn256", x.device, f"ffn_f32/F={Fh}", 8.0 * M * 256, 4.0 * M * 256 * Fh, x2, _split_weight_of(w1),
+                None if b1 is None else b1.float().contiguous(), _split_weight_of(w2), None if b2 is None else b2.float().contiguous(),
+                y, M, Fh, ALO_F32)
+    return y.view(x.shape)
+
+
 def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
     """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last bf16 CUDA activation, Cin % 64 == 0, Cout % 64 == 0."""
     return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x.dim() == 4 and weight.dim() == 4

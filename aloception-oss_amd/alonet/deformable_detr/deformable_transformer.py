@@ -76,10 +76,14 @@ def _self_attention(mha, qk_in, v_in):
 def _ffn(linear1, activation, linear2, x):
     """``linear2(act(linear1(x)))``; for ReLU the activation rides in the first GEMM's epilogue (alo_linear_shortk when
     d_model is 64 / 128 / 256 and the tensors are bf16 / fp16, else hipBLASLt's RELU_BIAS via ``torch._addmm_activation``) instead
-    of a separate pass over the (rows, d_ffn) intermediate."""
+    of a separate pass over the (rows, d_ffn) intermediate.  d_model = 256: one kernel for both layers in bf16 / fp16, and in fp32
+    under ``ALO_F32_LAYERS=split`` at the shapes ``alo_hip.ffn_f32_routed`` admits."""
     if activation is F.relu and alo_hip.ffn256_supported(x, linear1.weight, linear2.weight, f16=True):
         # d_model = 256, bf16 / fp16: both layers in one kernel, the hidden activation never leaves the chip
         return alo_hip.ffn256(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
+    if activation is F.relu and alo_hip.ffn_f32_routed(x, linear1.weight, linear2.weight):
+        # d_model = 256, fp32 under ALO_F32_LAYERS=split, at the shapes it was measured to win: the same block on the fp16 matrix cores
+        return alo_hip.ffn_f32(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
     if activation is F.relu and linear1.bias is not None:
         h = alo_hip.linear_auto(x, linear1.weight, linear1.bias, relu=True)
         return alo_hip.linear_auto(h, linear2.weight, linear2.bias)

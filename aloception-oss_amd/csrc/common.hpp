@@ -116,6 +116,11 @@ int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, v
 int linear_f32(const void* x, const void* w_split, const void* bias, const void* residual, void* y, long M, int N, int K, int relu,
                const RowGather& gather, hipStream_t stream, const char* what);
 
+// ffn_f32.hip: the fp32 flavour of alo_ffn256 on checked arguments (w1_split, w2_split: alo_hotpath.h); refuses an F whose tiles and
+// tables do not fit in LDS with ALO_ERR_UNSUPPORTED.
+int ffn_f32(const void* x, const void* w1_split, const void* b1, const void* w2_split, const void* b2, void* y, long M, int F,
+            hipStream_t stream, const char* what);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

@@ -349,11 +349,16 @@ extern "C" int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dt
 
 extern "C" int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y, long M,
                           int F, int dtype, void* stream) {
-    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16, ALO_ERR_UNSUPPORTED, "alo_ffn256: bf16 / fp16 only (dtype %d)", dtype);
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED,
+                "alo_ffn256: bf16 / fp16 / fp32 only (dtype %d)", dtype);
     ALO_REQUIRE(x && w1 && w2 && y, ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: null pointer argument");
     ALO_REQUIRE(M > 0 && F > 0 && F % 256 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_ffn256: M must be positive and the hidden width a positive multiple of 256 (M=%ld F=%d)", M, F);
     ALO_REQUIRE(aligned16(x, w1, w2, y), ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: pointers must be 16-byte aligned");
+    if (dtype == ALO_F32) {   // ffn_f32.hip; the fp32 biases are held to the alignment of the other operands
+        ALO_REQUIRE(aligned16(b1, b2), ALO_ERR_INVALID_ARGUMENT, "alo_ffn256: pointers must be 16-byte aligned");
+        return ffn_f32(x, w1, b1, w2, b2, y, M, F, static_cast<hipStream_t>(stream), "alo_ffn256");
+    }
     FfnDims dm;
     dm.M = M; dm.F = F; dm.tiles = (int)((M + kFfnRows - 1) / kFfnRows);
     const size_t lds = 2 * kFfnRows * kFfnStride + ((size_t)F + 256) * sizeof(float);

@@ -51,7 +51,7 @@ typedef enum alo_status {
  * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
  * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
- * (alo_conv3x3_nhwc, alo_linear_packed and alo_conv1x1_nhwc also serve ALO_F32: see there).
+ * (alo_conv3x3_nhwc, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -353,13 +353,22 @@ int alo_value_proj_head_major(const void* x, const void* weight, const void* bia
                               int batch, int S, int heads, int K, int dtype, void* stream);
 
 /*
- * alo_ffn256: y (M, 256) = relu(x (M, 256) @ w1 (F, 256)^T + b1) @ w2 (256, F)^T + b2, bf16 or fp16 with fp32 accumulation (the
+ * alo_ffn256: y (M, 256) = relu(x (M, 256) @ w1 (F, 256)^T + b1) @ w2 (256, F)^T + b2, bf16 or fp16 (fp32: last paragraph) with fp32 accumulation (the
  * hidden activation is rounded to the storage type before the second product, as two launches would store it),
  * F % 256 == 0: `linear2(relu(linear1(x)))` of the transformer layers (deformable_transformer.py:336-338,470-478) in one
  * kernel — the (M, F) hidden activation lives 64 rows at a time in LDS and never reaches memory.  b1 / b2 may be NULL.
  * w1 and w2 are PACKED weights: alo_pack_mfma_b(w (N, K) row-major) -> [N / 32][K / 16][64][8], the lane order of the MFMA
  * B operand, so that the weight stream is read in whole lines (pack once per weight update).  alo_pack_mfma_b moves 16-bit
  * elements: ALO_BF16 and ALO_F16 take the same kernel.
+ *
+ * dtype = ALO_F32 (alo_ffn256 only): x, b1, b2 and y are fp32 and both products run on the fp16 matrix cores at fp32-class accuracy,
+ * with alo_linear_packed's fp32 arithmetic (below).  w1 and w2 are then each ONE buffer in that flavour's layout, for the (F, 256) and
+ * the (256, F) matrix: alo_pack_mfma_b (ALO_F16) of the high terms, the same of the low terms, then the output channels' exponents as
+ * int32.  First product: one power of two per row of x, found inside the call; h = relu(.. + b1) in fp32.  Second product: the hidden
+ * activation is consumed 256 units at a time, each (row, chunk) with its own power of two (the chunk's largest finite |h| of that row),
+ * a chunk's three cross products in a fresh fp32 accumulator, the chunks added in fp32 in ascending order, then b2.  A row's result does
+ * not depend on the other rows; an Inf / NaN in x or in a hidden row spoils exactly that row.  b1 / b2, when given, are 16-byte aligned
+ * like the other pointers.  An F whose tiles and tables exceed the LDS (F > 3328) is refused with ALO_ERR_UNSUPPORTED, as for bf16.
  */
 int alo_pack_mfma_b(const void* w, void* packed, int N, int K, int dtype, void* stream);
 int alo_ffn256(const void* x, const void* w1, const void* b1, const void* w2, const void* b2, void* y, long M, int F,

@@ -1,7 +1,8 @@
 """alo_hip.linear_f32 / conv1x1_strided_f32 against what ``linear_auto`` / ``conv1x1_as_gemm`` launch for fp32 operands today
 (hipBLASLt: ``torch.addmm`` / ``torch._addmm_activation``, a gathered copy first when strided, a separate pass for the identity),
 layer by layer at the (M, K, N) of the fp32 headline: Deformable-DETR R50, batch 8 of 1333 x 800 — and alo_hip.conv3x3_f32 against
-MIOpen + alo_hip.bias_act_ at the bottlenecks' 3x3 convolutions of the same step.
+MIOpen + alo_hip.bias_act_ at the bottlenecks' 3x3 convolutions of the same step, and alo_hip.ffn_f32 against the two ``linear_auto``
+launches of the transformer's feed-forward block on the split route.
 
     python tools/gemmbench_f32.py [--rounds 5] [--reps 20] [--only SUBSTRING]
 
@@ -72,6 +73,14 @@ CONV3X3 = [
     ("layer3.x.conv2", P3, 256, 1),
     ("layer4.0.conv2", P3, 512, 2),
     ("layer4.x.conv2", P4, 512, 1),
+]
+
+
+# name, M, F: the transformer's feed-forward blocks (d_model = 256), alo_hip.ffn_f32 against the two launches it replaces
+FFN = [
+    ("encoder ffn", B * S, 1024),
+    ("decoder ffn", B * 300, 1024),
+    ("ffn 8400 x 2048", rows(P4), 2048),
 ]
 
 
@@ -156,6 +165,18 @@ def main():
                  "stock": lambda: alo_hip.bias_act_(F.conv2d(x, w, None, stride, 1), b, None, True)}
         measure({"layer": name, "map": [B, c, h, w_], "Cout": c, "stride": stride}, sides, args.rounds, args.reps)
         del x, w, b, sides
+    for name, m, f in FFN:
+        if args.only not in name:
+            continue
+        x = torch.randn(m, 256, device="cuda")
+        w1, b1 = torch.randn(f, 256, device="cuda") / 16, torch.randn(f, device="cuda")
+        w2, b2 = torch.randn(256, f, device="cuda") / f ** 0.5, torch.randn(256, device="cuda")
+        # stock: what _ffn launches without the kernel on the split route, linear_auto twice (each half on whichever of linear_f32 and
+        # hipBLASLt it is routed to at this shape)
+        sides = {"kernel": lambda: alo_hip.ffn_f32(x, w1, b1, w2, b2),
+                 "stock": with_knob("split", lambda: alo_hip.linear_auto(alo_hip.linear_auto(x, w1, b1, relu=True), w2, b2))}
+        measure({"layer": name, "M": m, "F": f}, sides, args.rounds, args.reps)
+        del x, w1, b1, w2, b2, sides
     os.environ.pop(KNOB, None)
 
 
