@@ -943,6 +943,71 @@ def conv1x1_strided(x, weight2d, bias, stride, relu=False):
     return y
 
 
+# ---- a layer1 bottleneck's last 1x1 convolution with its row-local neighbours (alo_conv1x1_nhwc with a chain buffer) -----------------
+CONV1X1_CHAIN, CONV1X1_CHAIN_DOWN = 2, 4   # ALO_CONV1X1_CHAIN* of include/alo_hotpath.h
+
+
+def bottleneck_chain_enabled():
+    """``ALO_BOTTLENECK_CHAIN=off`` (read per call) keeps the bottlenecks on their separate launches: for tests and profiling."""
+    return os.environ.get("ALO_BOTTLENECK_CHAIN", "on").lower() not in ("off", "0")
+
+
+def _chain_map(t, channels):
+    return (t.dim() == 4 and t.is_cuda and t.dtype == torch.bfloat16 and t.shape[1] == channels and t.numel() > 0
+            and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def _chain_vectors(*pairs):
+    return all(w.dtype == torch.bfloat16 and tuple(w.shape[:2]) == (cout, cin) and w.numel() == cout * cin
+               and b is not None and b.dtype == torch.bfloat16 and tuple(b.shape) == (cout,) for w, b, cout, cin in pairs)
+
+
+def conv1x1_chain_supported(mid, conv3, identity=None, down=None, nxt=None):
+    """What :func:`conv1x1_chain` takes, with grad mode off: channels-last bf16 CUDA maps, ``mid`` (N, 64, H, W),
+    ``conv3 = (w, b)`` with 256 output channels, either ``identity`` (N, 256, H, W) or ``down = (x0, wd, bd)`` with ``x0``
+    (N, 64, H, W) and 256 output channels, and, if given, ``nxt = (w1, b1)`` with 256 input and 64 or 128 output channels; weights
+    (Cout, Cin, 1, 1) or (Cout, Cin), every bias present."""
+    if (identity is None) == (down is None) or not bottleneck_chain_enabled() or torch.is_grad_enabled():
+        return False
+    other = identity if down is None else down[0]
+    if not (_chain_map(mid, 64) and _chain_map(other, 256 if down is None else 64) and other.shape[0] == mid.shape[0]
+            and other.shape[2:] == mid.shape[2:] and other.device == mid.device):
+        return False
+    pairs = [(*conv3, 256, 64)] + ([] if down is None else [(down[1], down[2], 256, 64)])
+    if nxt is not None:
+        if nxt[0].shape[0] not in (64, 128):
+            return False
+        pairs.append((*nxt, nxt[0].shape[0], 256))
+    return _chain_vectors(*pairs) and fusable(mid, other, *[t for w, b, _, _ in pairs for t in (w, b)])
+
+
+def conv1x1_chain(mid, conv3, identity=None, down=None, nxt=None):
+    """``y = relu(conv1x1(mid, *conv3) + identity)`` with ``identity`` given or ``conv1x1(x0, wd, bd)`` for ``down = (x0, wd, bd)``,
+    and with ``nxt = (w1, b1)`` also ``z = relu(conv1x1(y, w1, b1))``, in one launch; bit for bit the :func:`linear_shortk` launches
+    it stands in for (include/alo_hotpath.h, alo_conv1x1_nhwc with a chain buffer).  -> (y, z | None), channels-last."""
+    _no_autograd("conv1x1_chain", mid, *conv3, identity, *(down or ()), *(nxt or ()))
+    if not conv1x1_chain_supported(mid, conv3, identity, down, nxt):
+        raise RuntimeError("conv1x1_chain: needs channels-last bf16 CUDA maps outside autograd, a 64 -> 256 convolution, an identity or "
+                           "a 64 -> 256 downsample convolution, a next convolution 256 -> 64 or 128, and ALO_BOTTLENECK_CHAIN not off")
+    n, _, h, w_ = mid.shape
+    n2 = 0 if nxt is None else nxt[0].shape[0]
+    parts = [*conv3, *(down[1:] if down is not None else ()), *(nxt or ())]
+    # the chain buffer rides on the convolution's (cached, folded) weight and is rebuilt when any part changes
+    buf = derived(conv3[0], f"chain/{down is not None}/{n2}", parts, lambda: torch.cat([p.reshape(-1) for p in parts]))
+    rows = n * h * w_
+    out = torch.empty(rows * (256 + n2), dtype=mid.dtype, device=mid.device)   # y, then z: one buffer (alo_hotpath.h)
+    other = identity if down is None else down[0]
+    # what the result needs: mid, the identity or x0, y (+ z)
+    nbytes = 2.0 * rows * (64 + (256 if down is None else 64) + 256 + n2)
+    flops = 2.0 * rows * 256 * (64 * (1 + (down is not None)) + n2)
+    tag = f"conv1x1_chain/{'down' if down is not None else 'res'}{f'+next{n2}' if n2 else ''}"
+    _launch("alo_conv1x1_nhwc", mid.device, tag, nbytes, flops, mid, buf, CONV1X1_CHAIN | (CONV1X1_CHAIN_DOWN if down is not None else 0) | n2,
+            None, other, out, n, h, w_, 64, 256, 1, 1, ALO_BF16)
+    y = out[:rows * 256].view(n, h, w_, 256).permute(0, 3, 1, 2)
+    z = None if nxt is None else out[rows * 256:].view(n, h, w_, n2).permute(0, 3, 1, 2)
+    return y, z
+
+
 # ---- fp32 linear layers and 1x1 convolutions on the fp16 matrix cores (alo_linear_packed / alo_conv1x1_nhwc with ALO_F32) -----------
 def f32_layers_split():
     """``ALO_F32_LAYERS=split``: at inference the fp32 linear layers, 1x1 and 3x3 convolutions that the split kernels serve

@@ -132,6 +132,9 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
     return F.relu_(out) if relu else out
 
 
+_conv_bn = conv_bn   # Bottleneck._chain: the chain stands in for calls of THIS function
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -146,11 +149,50 @@ class Bottleneck(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
 
-    def forward(self, x):
-        identity = x if self.downsample is None else conv_bn(x, self.downsample[0], self.downsample[1])
-        out = conv_bn(x, self.conv1, self.bn1, relu=True)
+    def _chain(self, x, mid, nxt):
+        """The operands of ``alo_hip.conv1x1_chain`` for this block's conv3 — with its downsample convolution, and with ``nxt``'s conv1
+        when that block can take the hand-off — or None when the separate launches run: grad mode on, fp32 / fp16, other widths (only
+        layer1 has a 64 -> 256 conv3), a strided or dilated neighbour, or nothing to fold in (no downsample and no ``nxt``).
+        Also None while the module's ``conv_bn`` is swapped for another function: every convolution of the body goes through that
+        name, callers rely on it to see or re-route them all, and the chain is bit for bit three calls of the module's own only."""
+        def pointwise(conv, bn):
+            return (isinstance(bn, FrozenBatchNorm2d) and conv.bias is None and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+                    and conv.padding == (0, 0) and conv.groups == 1)
+
+        if not (conv_bn is _conv_bn and alo_hip.bottleneck_chain_enabled() and not torch.is_grad_enabled()
+                and x.is_cuda and x.dtype == torch.bfloat16 and pointwise(self.conv3, self.bn3)
+                and alo_hip.fusable(x, mid, self.conv3, self.bn3, self.downsample)):
+            return None
+        down = identity = head = None
+        if self.downsample is None:
+            identity = x
+        elif len(self.downsample) == 2 and pointwise(self.downsample[0], self.downsample[1]):
+            down = (x, *folded_conv_bn(self.downsample[0], self.downsample[1]))
+        else:
+            return None
+        if isinstance(nxt, Bottleneck) and pointwise(nxt.conv1, nxt.bn1) and alo_hip.fusable(x, nxt.conv1, nxt.bn1):
+            head = folded_conv_bn(nxt.conv1, nxt.bn1)
+            if head[0].shape[0] not in (64, 128):
+                head = None
+        if down is None and head is None:
+            return None
+        args = (mid, folded_conv_bn(self.conv3, self.bn3), identity, down, head)
+        return args if alo_hip.conv1x1_chain_supported(*args) else None
+
+    def forward(self, x, head=None, nxt=None):
+        """``head``: this block's ``relu(bn1(conv1(x)))`` when the block before has already made it.  ``nxt``: the block that follows;
+        then ``(out, head of nxt | None)`` is returned instead of ``out``: the hand-off ResNetBody passes along a stage."""
+        out = conv_bn(x, self.conv1, self.bn1, relu=True) if head is None else head
         out = conv_bn(out, self.conv2, self.bn2, relu=True)
-        return conv_bn(out, self.conv3, self.bn3, relu=True, residual=identity)
+        chain = self._chain(x, out, nxt)
+        if chain is not None:
+            # conv3 multiplies the block input by the downsample weights itself and hands its tile of the result to nxt's conv1 while
+            # it is still on chip: neither the identity map nor a second read of the block output reaches memory
+            out, head = alo_hip.conv1x1_chain(*chain)
+        else:
+            identity = x if self.downsample is None else conv_bn(x, self.downsample[0], self.downsample[1])
+            out, head = conv_bn(out, self.conv3, self.bn3, relu=True, residual=identity), None
+        return out if nxt is None else (out, head)
 
 
 _DEPTHS = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3)}
@@ -214,7 +256,14 @@ class ResNetBody(nn.Module):
             x = x.contiguous(memory_format=torch.channels_last)
             x = self.maxpool(conv_bn(x, self.conv1, self.bn1, relu=True))
         for name in ("layer1", "layer2", "layer3", "layer4"):
-            x = getattr(self, name)(x)
+            stage = getattr(self, name)
+            head = None  # a block's relu(bn1(conv1(x))) when the block before it has made it (Bottleneck.forward)
+            for i, block in enumerate(stage):
+                # the hand-off stays inside a stage: a stage's last block ends in the plain launch with the identity in its epilogue
+                if i + 1 < len(stage):
+                    x, head = block(x, head=head, nxt=stage[i + 1])
+                else:
+                    x = block(x, head=head)
             if name in self.return_layers:
                 out[self.return_layers[name]] = x
         return out

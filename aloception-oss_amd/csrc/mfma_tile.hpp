@@ -1,6 +1,6 @@
 // What the GEMM-shaped kernels do around v_mfma_f32_32x32x16_*, once.  linear_shortk_kernel, ffn256_kernel (gemm.hip),
-// linear_packed_kernel (gemm_packed.hip), encoder_block_kernel, conv3x3_kernel, conv3x3_c64_kernel (conv.hip) and stem_conv_pool_kernel
-// (stem.hip) share one frame:
+// linear_packed_kernel (gemm_packed.hip), conv1x1_chain_kernel, encoder_block_kernel, conv3x3_kernel, conv3x3_c64_kernel (conv.hip) and
+// stem_conv_pool_kernel (stem.hip) share one frame:
 //   * A wave owns a 64 x 64 (or 32 x 64) block of the output and computes it TRANSPOSED (weights = the MFMA's row operand), as
 //     [row tile][column tile] of 32 x 32: lane (nl = lane & 31, kg = lane >> 5) holds ONE row per row tile, and registers 4 q .. 4 q + 3 of
 //     column tile t are the four consecutive columns 32 t + 8 q + 4 kg .. + 3.

@@ -397,7 +397,20 @@ int alo_linear_packed(const void* x, const void* w_packed, const void* bias, con
  * (n, stride * yo, stride * xo) itself.  Ho = (H - 1) / stride + 1.  residual (N, Ho, Wo, Cout) or NULL.  bf16 only —
  * but for dtype = ALO_F32 with weight_is_packed = 1: alo_linear_packed's fp32 flavour (its split weight buffer, fp32 x, bias, residual
  * and y, Cin % 64 == 0, Cout % 64 == 0) behind the same pixel addressing; weight_is_packed = 0 is refused in fp32.
+ *
+ * weight_is_packed = ALO_CONV1X1_CHAIN [| ALO_CONV1X1_CHAIN_DOWN] [+ N2, 64 or 128]: the last 1x1 convolution of a layer1 bottleneck with
+ * its row-local neighbours in ONE launch (csrc/conv1x1_chain.hip): bf16, Cin = 64, Cout = 256, stride 1, relu != 0, bias = NULL.
+ *     y = relu(x W3^T + b3 + identity)        identity = residual (N, H, W, 256), or with _DOWN bf16(x0 Wd^T + bd) for
+ *                                             residual = x0 (N, H, W, 64): the bottleneck's `downsample` convolution
+ *     z = relu(y W1^T + b1)                   with N2: the NEXT bottleneck's first 1x1 convolution, W1 (N2, 256)
+ * weight is then ONE bf16 buffer, W3 (256, 64) row-major, b3 (256), [Wd (256, 64), bd (256)], [W1 (N2, 256), b1 (N2)], the bracketed
+ * parts present as the flags say; y receives y (N, H, W, 256) and, with N2, z (N, H, W, N2) straight after it (one buffer of
+ * N H W (256 + N2) elements, which may overlap neither x nor residual).  Every intermediate is rounded to bf16 where the separate
+ * launches round it, so y and z are bit for bit what alo_linear_shortk gives for (x0, Wd, bd), then (x, W3, b3, relu, residual =
+ * that), then (y, W1, b1, relu).  The (N, H, W, 256) identity of _DOWN is never written, and y is not read back to make z.
  */
+#define ALO_CONV1X1_CHAIN 2
+#define ALO_CONV1X1_CHAIN_DOWN 4
 int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is_packed, const void* bias, const void* residual, void* y, int N,
                      int H, int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream);
 
