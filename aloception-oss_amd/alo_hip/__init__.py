@@ -1229,13 +1229,18 @@ def ffn_f32(x, w1, b1, w2, b2):
     return y.view(x.shape)
 
 
-def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
-    """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last bf16 CUDA activation, Cin % 64 == 0, Cout % 64 == 0."""
-    return (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and x.dim() == 4 and weight.dim() == 4
+def _conv3x3_gate(dtype, x, weight, stride, padding, dilation, groups):
+    """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last CUDA activation of ``dtype``, Cin % 64 == 0, Cout % 64 == 0."""
+    return (x.is_cuda and x.dtype == dtype and weight.dtype == dtype and x.dim() == 4 and weight.dim() == 4
             and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) in ((1, 1), (2, 2)) and tuple(padding) == (1, 1)
             and tuple(dilation) == (1, 1) and groups == 1 and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0
             and weight.shape[0] % 64 == 0 and x.is_contiguous(memory_format=torch.channels_last)
             and not torch.is_grad_enabled())
+
+
+def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
+    """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last bf16 CUDA activation, Cin % 64 == 0, Cout % 64 == 0."""
+    return _conv3x3_gate(torch.bfloat16, x, weight, stride, padding, dilation, groups)
 
 
 def conv3x3(x, weight, bias=None, relu=False, stride=1):
@@ -1263,11 +1268,7 @@ def conv3x3(x, weight, bias=None, relu=False, stride=1):
 
 def conv3x3_f32_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
     """The shape rules of :func:`conv3x3_supported` for a channels-last fp32 CUDA activation and an fp32 weight."""
-    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and weight.dim() == 4
-            and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) in ((1, 1), (2, 2)) and tuple(padding) == (1, 1)
-            and tuple(dilation) == (1, 1) and groups == 1 and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0
-            and weight.shape[0] % 64 == 0 and x.is_contiguous(memory_format=torch.channels_last)
-            and not torch.is_grad_enabled())
+    return _conv3x3_gate(torch.float32, x, weight, stride, padding, dilation, groups)
 
 
 def split_exponent(absmax):

@@ -205,23 +205,7 @@ conv3x3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, cons
 
         if (KSPLIT) {  // wave 1 hands its partial sums to wave 0
             float* red = reinterpret_cast<float*>(smem + kRedOffset);
-            if (wave == 1) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) red[((a * 2 + b) * 16 + r) * 64 + lane] = acc[a][b][r];
-            }
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[a][b][r] += red[((a * 2 + b) * 16 + r) * 64 + lane];
-            }
+            ALO_KSPLIT_HANDOFF(acc, red, wave, lane);
         }
 
         if (!KSPLIT && dm.zsplit > 1) {

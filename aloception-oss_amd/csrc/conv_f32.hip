@@ -1,16 +1,12 @@
-// 3x3 convolution, padding 1, stride 1 or 2, NHWC fp32 in and out, on the fp16 matrix cores at fp32-class accuracy: the arithmetic of
-// the correlation build (corr.hip's header) in the frame of conv3x3_kernel (conv.hip's header) — RAFT's update block is fp32 end to end.
+// 3x3 convolution, padding 1, stride 1 or 2, NHWC fp32 in and out, on the fp16 matrix cores at fp32-class accuracy: the two-term split
+// arithmetic of split_f16.hpp (scale, split, non-finite rule, term order, undo) in the frame of conv3x3_kernel (conv.hip's header) —
+// RAFT's update block is fp32 end to end.
 //
-//   * activations: one power of two per IMAGE (conv_f32_absmax_kernel: the image's largest finite magnitude, split_exponent brings it
-//     into [2^14, 2^15)), so an image's result does not depend on its batch neighbours.  The split  x 2^-k = hi + lo  (two fp16 terms,
-//     round to nearest) happens where a tile's halo is parked in LDS: the raw fp32 pixels travel through registers one chunk ahead, as
-//     in conv3x3_kernel, and there is no split copy of the activation in memory.  An Inf / NaN element takes no part in the scale and
-//     is parked as hi = 0, lo = the element: it then meets only the high weight term (lo * lo is not formed), so an infinity keeps its
-//     sign and a non-finite element spoils exactly the outputs whose window holds it.
-//   * weights: split once by the caller, one power of two per output channel, both terms in alo_pack_mfma_b order, the channels'
-//     exponents behind them (alo_hotpath.h).
-//   * per 16 input channels of a tap three MFMAs per 32 x 32 tile, small terms first: w_lo x_hi, w_hi x_lo, w_hi x_hi, fp32 accumulators.
-//   * epilogue: ldexp by k_image + k_channel (exact), + bias, ReLU, fp32 stores in whole 256-byte runs through LDS.
+//   * scale: one power of two per IMAGE (conv_f32_absmax_kernel: the image's largest finite magnitude), so an image's result does not
+//     depend on its batch neighbours.  The raw fp32 pixels travel through registers one chunk ahead, as in conv3x3_kernel, and are split
+//     where a tile's halo is parked in LDS; a non-finite element spoils exactly the outputs whose window holds it.
+//   * weights: split once by the caller as a (Cout, 9 Cin) matrix, one power of two per output channel (alo_hotpath.h).
+//   * epilogue: the undo by k_image + k_channel, + bias, ReLU, fp32 stores in whole 256-byte runs through LDS.
 //
 // Tile: 64 consecutive output pixels x 128 output channels on two waves (64 each, 2 x 2 MFMA tiles), as conv3x3_kernel; the halo is
 // staged 16 input channels (one k-step per tap) at a time, a pixel's hi terms and lo terms side by side (the 80-byte pixel stride of
@@ -23,9 +19,6 @@ namespace {
 
 constexpr int kPix = 64;                          // output pixels per tile
 constexpr int kThreads = 128;                     // two waves
-constexpr int kOutStride = 64 * 4 + 16;           // LDS bytes per pixel of a wave's 32 x 64 fp32 output block
-constexpr int kOutBytes = 32 * kOutStride;        // one row tile of one wave
-constexpr int kRedOffset = kOutBytes;             // K-split: wave 1's partial sums [64 regs][64 lanes] sit behind wave 0's output block
 
 template <int STRIDE>
 struct Geo {
@@ -48,8 +41,6 @@ struct ConvF32Dims {
     int tiles_per_image;
     int relu;
 };
-
-struct WFrag { u32x4 v[2][2]; };    // [term: hi, lo][column tile]
 
 // flattened input pixel (clamped into the image) behind staging slot `slot` of the tile whose first output pixel is p0: the halo plan of
 // conv3x3_kernel (conv.hip, slot_pixel)
@@ -90,17 +81,6 @@ conv_f32_absmax_kernel(const float* __restrict__ X, unsigned* __restrict__ mag, 
     if ((threadIdx.x & 63) == 0 && w) atomicMax(mag + blockIdx.y, w);
 }
 
-// x 2^-k -> (hi, lo); a non-finite element -> (0, itself)
-__device__ __forceinline__ void split2(float x, float down, _Float16& hi, _Float16& lo) {
-    const float xs = x * down;
-    hi = (_Float16)xs;
-    lo = (_Float16)(xs - (float)hi);
-    if (!(fabsf(xs) < INFINITY)) {
-        hi = (_Float16)0.f;
-        lo = (_Float16)xs;
-    }
-}
-
 template <int STRIDE, bool KSPLIT>
 __global__ void __launch_bounds__(kThreads, STRIDE == 1 ? 2 : 1)   // stride 2 stages twice the halo: it takes the registers of a second wave
 conv3x3_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, const float* __restrict__ bias, float* __restrict__ Y,
@@ -117,12 +97,8 @@ conv3x3_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, co
     // the workgroup's 128 (K-split: 64) bias values and channel exponents
     float* const bias_s = reinterpret_cast<float*>(smem + G::kLds);
     int* const kc_s = reinterpret_cast<int*>(smem + G::kLds + kThreads * 4);
-    {
-        const int c = (KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128) + tid;
-        const bool live = c < dm.Cout && (!KSPLIT || tid < 64);
-        bias_s[tid] = (bias != nullptr && live) ? bias[c] : 0.f;
-        kc_s[tid] = live ? reinterpret_cast<const int*>(Wp + 2 * term_stride)[c] : 0;
-    }
+    fill_channel_tables<KSPLIT>(bias_s, kc_s, bias, reinterpret_cast<const int*>(Wp + 2 * term_stride), KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128,
+                                dm.Cout, tid);
 
     // persistent workgroups, one contiguous eighth of the tiles per XCD (see conv3x3_kernel)
     const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
@@ -181,33 +157,22 @@ conv3x3_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, co
         for (int c0 = 0; c0 < dm.Cin; c0 += G::kChunk) {
             // weights of pair kb of this chunk: tap kb / kSteps, k-step kb % kSteps of the chunk, both terms
             auto load_w = [&](WFrag& f, int kb) {
-                const f16_t* p = wfrag + (size_t)((kb / G::kSteps) * ksteps_per_tap + c0 / 16 + kb % G::kSteps) * 512;
-#pragma unroll
-                for (int term = 0; term < 2; ++term)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        f.v[term][b] = *reinterpret_cast<const u32x4*>(p + term * term_stride + b * ctile_stride);
+                load_wfrag(f, wfrag + (size_t)((kb / G::kSteps) * ksteps_per_tap + c0 / 16 + kb % G::kSteps) * 512, term_stride, ctile_stride);
             };
             auto compute = [&](const WFrag& f, int kb) {
                 const int t = kb / G::kSteps, dy = t / 3, dx = t - 3 * dy;
                 const int slot = STRIDE == 1 ? dy * G::kRun + dx : dy * G::kRun + (dx == 0 ? 0 : (dx == 1 ? kPix + 1 : 1));
                 const bool ok0 = (tapmask[0] >> t) & 1u, ok1 = (tapmask[1] >> t) & 1u;
                 const unsigned char* a_base = halo + (slot + nl) * G::kPixStride + kg * 16 + (kb % G::kSteps) * 32;
-                u32x4 x[2][2];   // [row tile][term]
+                XFrag x;
 #pragma unroll
                 for (int term = 0; term < 2; ++term) {
-                    x[0][term] = *reinterpret_cast<const u32x4*>(a_base + term * G::kLoOffset);
-                    x[1][term] = *reinterpret_cast<const u32x4*>(a_base + 32 * G::kPixStride + term * G::kLoOffset);
-                    if (!ok0) x[0][term] = u32x4{0u, 0u, 0u, 0u};
-                    if (!ok1) x[1][term] = u32x4{0u, 0u, 0u, 0u};
+                    x.v[term][0] = *reinterpret_cast<const u32x4*>(a_base + term * G::kLoOffset);
+                    x.v[term][1] = *reinterpret_cast<const u32x4*>(a_base + 32 * G::kPixStride + term * G::kLoOffset);
+                    if (!ok0) x.v[term][0] = u32x4{0u, 0u, 0u, 0u};
+                    if (!ok1) x.v[term][1] = u32x4{0u, 0u, 0u, 0u};
                 }
-                // small cross terms first; the four tiles rotate, so no MFMA waits on the one before it
-#define ALO_CONV_STEP(WT, XT)                                                                          \
-                _Pragma("unroll") for (int b = 0; b < 2; ++b)                                          \
-                _Pragma("unroll") for (int a = 0; a < 2; ++a)                                          \
-                    acc[a][b] = mfma_32x32x16<f16_t>(f.v[WT][b], x[a][XT], acc[a][b]);
-                ALO_CONV_STEP(1, 0) ALO_CONV_STEP(0, 1) ALO_CONV_STEP(0, 0)
-#undef ALO_CONV_STEP
+                mma_split(acc, f, x);
             };
             WFrag w0, w1;
             if (has_cols) load_w(w0, batch(0));
@@ -217,25 +182,13 @@ conv3x3_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, co
             for (int it = 0; it < G::kIters; ++it) {
                 const int i = tid + it * kThreads;
                 const int piece = i % (G::kChunk / 4), slot = i / (G::kChunk / 4);
-                if (i < G::kPieces) {
-                    _Float16 hi[4], lo[4];
-                    split2(__uint_as_float(stage[it].x), down, hi[0], lo[0]);
-                    split2(__uint_as_float(stage[it].y), down, hi[1], lo[1]);
-                    split2(__uint_as_float(stage[it].z), down, hi[2], lo[2]);
-                    split2(__uint_as_float(stage[it].w), down, hi[3], lo[3]);
-                    auto two = [](_Float16 e0, _Float16 e1) {
-                        return (unsigned)__builtin_bit_cast(uint16_t, e0) | ((unsigned)__builtin_bit_cast(uint16_t, e1) << 16);
-                    };
-                    unsigned char* dst = halo + slot * G::kPixStride + piece * 8;
-                    *reinterpret_cast<u32x2*>(dst) = u32x2{two(hi[0], hi[1]), two(hi[2], hi[3])};
-                    *reinterpret_cast<u32x2*>(dst + G::kLoOffset) = u32x2{two(lo[0], lo[1]), two(lo[2], lo[3])};
-                }
+                if (i < G::kPieces) park4(halo + slot * G::kPixStride + piece * 8, G::kLoOffset, stage[it], down);
             }
             __syncthreads();
             if (c0 + G::kChunk < dm.Cin) load_halo(tile, c0 + G::kChunk);
             else if (tile + lanes_per_xcd < tile_end) load_halo(tile + lanes_per_xcd, 0);
 
-            if (has_cols) {
+            if (has_cols) {   // (linear_f32_kernel's loop; as a shared function it costs that kernel 14 VGPRs and changes three of these four)
 #pragma unroll 1
                 for (int i = 0; i < my_batches; i += 2) {
                     if (i + 1 < my_batches) load_w(w1, batch(i + 1));
@@ -249,46 +202,17 @@ conv3x3_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, co
 
         if (KSPLIT) {  // wave 1 hands its partial sums to wave 0
             float* red = reinterpret_cast<float*>(smem + kRedOffset);
-            if (wave == 1) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) red[((a * 2 + b) * 16 + r) * 64 + lane] = acc[a][b][r];
-            }
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[a][b][r] += red[((a * 2 + b) * 16 + r) * 64 + lane];
-            }
+            ALO_KSPLIT_HANDOFF(acc, red, wave, lane);
         }
 
         if (has_cols && !(KSPLIT && wave == 1)) {
             unsigned char* const obuf = smem + (KSPLIT ? 0 : wave) * kOutBytes;
             const int cs0 = (KSPLIT ? 0 : wave) * 64;    // this wave's first channel in bias_s / kc_s
-            // lane = output pixel 32 a + nl, registers 4 q .. 4 q + 3 = channels col0 + 32 b + 8 q + 4 kg .. + 3 (see conv3x3_kernel): one row
-            // tile at a time -> 2^(k_image + k_channel), bias, ReLU, one 16-byte LDS write per quad; then 16 lanes x 16 B per pixel
+            // one row tile (32 output pixels) at a time: 2^(k_image + k_channel), bias, ReLU -> LDS; then 16 lanes x 16 B per pixel.  (The
+            // row store as a shared function too: layer2.x.conv2 273.5 -> 275.2 us against spreads of 0.9 and 1.5.)
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int c = 32 * b + 8 * q + 4 * kg;
-                        const f32x4 bb = *reinterpret_cast<const f32x4*>(bias_s + cs0 + c);
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            v[e] = ldexpf(acc[a][b][4 * q + e], kimg + kc_s[cs0 + c + e]) + bb[e];
-                            if (dm.relu) v[e] = relu_keep_nan(v[e]);
-                        }
-                        *reinterpret_cast<f32x4*>(obuf + nl * kOutStride + c * 4) = v;
-                    }
+                stage_scaled_quads(obuf, acc[a], kimg, bias_s + cs0, kc_s + cs0, dm.relu, nl, kg);
                 wave_lds_fence();
 #pragma unroll
                 for (int pass = 0; pass < 8; ++pass) {

@@ -1,21 +1,16 @@
 // y (M, 256) = relu(x (M, 256) W1 (F, 256)^T + b1) W2 (256, F)^T + b2, fp32 in and out, in ONE kernel on the fp16 matrix cores at fp32-class
-// accuracy: the fp32 flavour of alo_ffn256.  linear_f32_kernel's arithmetic (gemm_f32.hip's header) in ffn256_kernel's frame
-// (gemm.hip): a workgroup keeps 64 rows in LDS and the (M, F) hidden activation never reaches memory.
+// accuracy: the fp32 flavour of alo_ffn256.  The two-term split arithmetic of split_f16.hpp (scale, split, non-finite rule, term order,
+// undo) in ffn256_kernel's frame (gemm.hip): a workgroup keeps 64 rows in LDS and the (M, F) hidden activation never reaches memory.
 //
-// The arithmetic (tests/ffn_f32_ref.py restates it):
+// What is this kernel's own (tests/ffn_f32_ref.py restates it):
 //   * weights: w1 and w2 each arrive as ONE buffer in the layout of alo_linear_packed's fp32 flavour (alo_hotpath.h) for the (F, 256)
-//     and the (256, F) matrix: alo_pack_mfma_b order of the high terms hi = fp16(w 2^-k_o), the same of the low terms
-//     lo = fp16(w 2^-k_o - hi), then one int32 exponent k_o per output channel (hidden unit for w1, output column for w2).
-//   * first product: one power of two per ROW of x, from the row's largest finite magnitude (split_exponent brings it into
-//     [2^14, 2^15)); the whole row is in the tile, so one sweep over the registers the row arrives in finds it and x is read once.
-//     x 2^-k = hi + lo is formed where the tile is parked in LDS; an Inf / NaN element takes no part in the scale and is parked as
-//     (0, itself): it meets only the high weight term, so an infinity keeps its sign.  Per 16 input channels three MFMAs per 32 x 32
-//     tile, small terms first (w_lo x_hi, w_hi x_lo, w_hi x_hi), fp32 accumulators;  h = relu_keep_nan(ldexp(acc, k_row + k_unit) + b1).
+//     and the (256, F) matrix, one power of two per output channel (hidden unit for w1, output column for w2).
+//   * first product: one power of two per ROW of x; the whole row is in the tile, so one sweep over the registers the row arrives in
+//     finds it and x is read once.  h = relu_keep_nan(ldexp(acc, k_row + k_unit) + b1).
 //   * second product: the hidden activation is consumed 256 units at a time.  Each (row, chunk) gets its OWN power of two, from the
 //     largest finite |h| of that row in that chunk (the four waves hold 64 of the 256 units each: one cross-wave maximum through LDS);
-//     the chunk is split into hi + lo on its way into LDS, a non-finite h as (0, itself); the chunk's three products per 16 units go
-//     into a FRESH accumulator, and then  y_acc += ldexp(acc_chunk, k_row,chunk + k_column)  in fp32, chunks in ascending order;
-//     finally  y = y_acc + b2.
+//     the chunk is split on its way into LDS; the chunk's three products per 16 units go into a FRESH accumulator, and then
+//     y_acc += ldexp(acc_chunk, k_row,chunk + k_column)  in fp32, chunks in ascending order; finally  y = y_acc + b2.
 //   * a row's result depends on no other row of the call, and there is no atomic and no order that depends on the launch: two launches
 //     give the same bits.  An Inf / NaN in x, or one that arises in a hidden row, spoils exactly that row's outputs.
 //
@@ -54,31 +49,7 @@ struct FfnF32Dims {
 // the waves' row maxima of a hidden chunk (4 x 64)
 constexpr size_t tail_bytes(int F) { return ((size_t)F + 256) * 8 + kRows * 4 + 4 * kRows * 4; }
 
-struct WBatch { u32x4 v[2][2][kKB]; };   // [term: hi, lo][column tile][k-step of the batch]
-
-// x 2^-k -> (hi, lo); a non-finite element -> (0, itself)
-__device__ __forceinline__ void split2(float x, float down, _Float16& hi, _Float16& lo) {
-    const float xs = x * down;
-    hi = (_Float16)xs;
-    lo = (_Float16)(xs - (float)hi);
-    if (!(fabsf(xs) < INFINITY)) {
-        hi = (_Float16)0.f;
-        lo = (_Float16)xs;
-    }
-}
-__device__ __forceinline__ unsigned two_f16(_Float16 e0, _Float16 e1) {
-    return (unsigned)__builtin_bit_cast(uint16_t, e0) | ((unsigned)__builtin_bit_cast(uint16_t, e1) << 16);
-}
-// four consecutive values of one row -> their four hi terms at dst, their four lo terms kLoOffset behind
-__device__ __forceinline__ void park4(unsigned char* dst, float v0, float v1, float v2, float v3, float down) {
-    _Float16 hi[4], lo[4];
-    split2(v0, down, hi[0], lo[0]);
-    split2(v1, down, hi[1], lo[1]);
-    split2(v2, down, hi[2], lo[2]);
-    split2(v3, down, hi[3], lo[3]);
-    *reinterpret_cast<u32x2*>(dst) = u32x2{two_f16(hi[0], hi[1]), two_f16(hi[2], hi[3])};
-    *reinterpret_cast<u32x2*>(dst + kLoOffset) = u32x2{two_f16(lo[0], lo[1]), two_f16(lo[2], lo[3])};
-}
+struct WBatch { WFrag f[kKB]; };   // the k-steps of a batch, both terms of both column tiles each
 
 // load_batch / mma_batch / mma_tile256 of mfma_tile.hpp with both terms of the weights and of the LDS tile.
 // frag0 = this lane's 16 bytes of the high terms' first fragment of column tile 0; the low terms sit term_stride elements behind.
@@ -89,36 +60,27 @@ __device__ __forceinline__ void load_wbatch(WBatch& buf, const f16_t* frag0, siz
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < kKB; ++j)
-                buf.v[term][t][j] = *reinterpret_cast<const u32x4*>(frag0 + term * term_stride + t * tile_stride + (size_t)(kKB * batch + j) * 512);
+                buf.f[j].v[term][t] = *reinterpret_cast<const u32x4*>(frag0 + term * term_stride + t * tile_stride + (size_t)(kKB * batch + j) * 512);
     __builtin_amdgcn_sched_barrier(0);
 }
 // the LDS tile's fragments of a batch, both terms of both row tiles.  One wave per SIMD: nobody else covers an LDS round trip, so a
 // batch's fragments are read a batch AHEAD of their use as well, during the previous batch's MFMAs.
-struct ABatch { u32x4 v[2][2][kKB]; };   // [row tile][term][k-step of the batch]
+struct ABatch { XFrag f[kKB]; };   // the k-steps of a batch, both terms of both row tiles each
 __device__ __forceinline__ void read_abatch(ABatch& af, const unsigned char* a_lds, int batch, int nl, int kg) {
 #pragma unroll
     for (int j = 0; j < kKB; ++j) {
         const unsigned char* p = a_lds + nl * kRowStride + (16 * (kKB * batch + j) + 8 * kg) * 2;
 #pragma unroll
         for (int term = 0; term < 2; ++term) {
-            af.v[0][term][j] = *reinterpret_cast<const u32x4*>(p + term * kLoOffset);
-            af.v[1][term][j] = *reinterpret_cast<const u32x4*>(p + 32 * kRowStride + term * kLoOffset);
+            af.f[j].v[term][0] = *reinterpret_cast<const u32x4*>(p + term * kLoOffset);
+            af.f[j].v[term][1] = *reinterpret_cast<const u32x4*>(p + 32 * kRowStride + term * kLoOffset);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 __device__ __forceinline__ void mma_wbatch(f32x16 (&acc)[2][2], const WBatch& buf, const ABatch& a) {
-    const auto& af = a.v;
 #pragma unroll
-    for (int j = 0; j < kKB; ++j) {
-        // small cross terms first; the four tiles rotate, so no MFMA waits on the one before it
-#define ALO_FFN_STEP(WT, XT)                                                                           \
-        _Pragma("unroll") for (int b = 0; b < 2; ++b)                                                  \
-        _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                  \
-            acc[a][b] = mfma_32x32x16<f16_t>(buf.v[WT][b][j], af[a][XT][j], acc[a][b]);
-        ALO_FFN_STEP(1, 0) ALO_FFN_STEP(0, 1) ALO_FFN_STEP(0, 0)
-#undef ALO_FFN_STEP
-    }
+    for (int j = 0; j < kKB; ++j) mma_split(acc, buf.f[j], a.f[j]);
     __builtin_amdgcn_sched_barrier(0);
 }
 // One 256-deep contraction of the split LDS tile against the split weights w.  bufa already holds batch 0; on return it holds batch 0 of
@@ -193,10 +155,8 @@ ffn_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ W1, const 
         for (int it = 0; it < kPasses; ++it) {
             unsigned m = 0u;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 v = stage[it][j];
-                m = max(max(m, max(finite_mag(v.x), finite_mag(v.y))), max(finite_mag(v.z), finite_mag(v.w)));
-            }
+            for (int j = 0; j < 4; ++j) m = finite_mag4(m, stage[it][j]);
+            // (row_exponent's body: through the helper one more instruction, decoder ffn 53.2 -> 53.8 us against spreads of 0.2 and 0.3)
 #pragma unroll
             for (int o = kRowLanes / 2; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
             const int k = split_exponent(m);
@@ -204,11 +164,7 @@ ffn_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ W1, const 
             const int row = grp + kPassRows * it;
             if (l16 == 0) krow_s[row] = k;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const u32x4 v = stage[it][j];
-                park4(xs + row * kRowStride + (64 * j + 4 * l16) * 2, __uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
-                      __uint_as_float(v.w), down);
-            }
+            for (int j = 0; j < 4; ++j) park4(xs + row * kRowStride + (64 * j + 4 * l16) * 2, kLoOffset, stage[it][j], down);
         }
         if (tile + (int)gridDim.x < dm.tiles) fetch(tile + gridDim.x);   // in flight through this tile's products
         load_wbatch(bufa, w1_frag(0), (size_t)16 * 512, term1, 0);
@@ -259,7 +215,7 @@ ffn_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ W1, const 
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int c = 64 * wave + 32 * b + 8 * q + 4 * kg;
-                        park4(hs + row * kRowStride + c * 2, acc1[a][b][4 * q], acc1[a][b][4 * q + 1], acc1[a][b][4 * q + 2],
+                        park4(hs + row * kRowStride + c * 2, kLoOffset, acc1[a][b][4 * q], acc1[a][b][4 * q + 1], acc1[a][b][4 * q + 2],
                               acc1[a][b][4 * q + 3], down);
                     }
             }

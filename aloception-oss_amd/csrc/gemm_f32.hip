@@ -1,18 +1,15 @@
-// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias [+ R]), fp32 in and out, on the fp16 matrix cores at fp32-class accuracy: the arithmetic of
-// conv3x3_f32_kernel (conv_f32.hip's header) in that kernel's frame with ONE tap — the fp32 flavour of alo_linear_packed and of
-// alo_conv1x1_nhwc (the detector's 1x1 convolutions, input projections and transformer matrices in fp32 mode).
+// Y (M, N) = act(X (M, K) @ W (N, K)^T + bias [+ R]), fp32 in and out, on the fp16 matrix cores at fp32-class accuracy: the two-term split
+// arithmetic of split_f16.hpp (scale, split, non-finite rule, term order, undo) in conv3x3_f32_kernel's frame with ONE tap — the fp32
+// flavour of alo_linear_packed and of alo_conv1x1_nhwc (the detector's 1x1 convolutions, input projections and transformer matrices in
+// fp32 mode).
 //
-//   * activations: one power of two per ROW (the row's largest finite magnitude, split_exponent brings it into [2^14, 2^15)), found by a
-//     first sweep over the tile's rows inside the kernel — 16 lanes per row, the very lanes that later park that row, so the scale
-//     stays in their registers — and a row's result does not depend on any other row of the call.  The split  x 2^-k = hi + lo
-//     happens where the tile is parked in LDS (split2 of conv_f32.hip): the raw fp32 rows travel through registers one chunk ahead and
-//     there is no split copy in memory.  An Inf / NaN element takes no part in the scale and is parked as hi = 0, lo = the element: it
-//     meets only the high weight term, so an infinity keeps its sign and a non-finite element spoils exactly its own row.
-//   * weights: split once by the caller, one power of two per output channel, both terms in alo_pack_mfma_b order, the channels'
-//     exponents behind them (alo_hotpath.h) — the layout of conv3x3_f32_kernel for a (N, K) matrix.
-//   * per 16 input channels three MFMAs per 32 x 32 tile, small terms first: w_lo x_hi, w_hi x_lo, w_hi x_hi, fp32 accumulators.
-//   * epilogue: ldexp by k_row + k_channel (exact), + bias, + residual (fp32, before the activation), ReLU, fp32 stores in whole 256-byte
-//     runs through LDS.
+//   * scale: one power of two per ROW, found by a first sweep over the tile's rows inside the kernel — 16 lanes per row, the very lanes
+//     that later park that row, so the scale stays in their registers — and a row's result does not depend on any other row of the
+//     call.  The raw fp32 rows travel through registers one chunk ahead and are split where the tile is parked in LDS; a non-finite
+//     element spoils exactly its own row.
+//   * weights: split once by the caller, one power of two per output channel: the layout of conv3x3_f32_kernel for a (N, K) matrix.
+//   * epilogue: the undo by k_row + k_channel, + bias, + residual (fp32, before the activation), ReLU, fp32 stores in whole 256-byte runs
+//     through LDS.
 //
 // Tile: 64 rows x 128 columns on two waves (64 each, 2 x 2 MFMA tiles); 64 input channels (four k-steps) are staged per barrier pair, a
 // row's hi terms and lo terms side by side; N == 64: the two waves take every other k-step and wave 0 adds wave 1's sums (a fixed
@@ -34,9 +31,6 @@ constexpr int kRowLanes = kChunk / 4;             // lanes per staged row: one 1
 constexpr int kPassRows = kThreads / kRowLanes;   // rows staged per pass of the workgroup
 constexpr int kLoads = kRows / kPassRows;         // passes = pieces per thread and chunk
 constexpr int kTile = kRows * kRowStride;
-constexpr int kOutStride = 64 * 4 + 16;           // LDS bytes per row of a wave's 32 x 64 fp32 output block
-constexpr int kOutBytes = 32 * kOutStride;        // one row tile of one wave
-constexpr int kRedOffset = kOutBytes;             // K-split: wave 1's partial sums [64 regs][64 lanes] sit behind wave 0's output block
 constexpr int kStaging = kRedOffset + 64 * 64 * 4;        // the epilogue's staging aliases the tile
 constexpr int kLds = kTile > kStaging ? kTile : kStaging;
 constexpr int kTail = kThreads * 8 + kRows * 20;  // behind both: bias and channel exponents of the column block; the rows' exponents; their offsets, twice
@@ -47,19 +41,6 @@ struct F32Dims {
     int N, K, tiles, relu;
     RowGather g;
 };
-
-struct WFrag { u32x4 v[2][2]; };    // [term: hi, lo][column tile]
-
-// x 2^-k -> (hi, lo); a non-finite element -> (0, itself)
-__device__ __forceinline__ void split2(float x, float down, _Float16& hi, _Float16& lo) {
-    const float xs = x * down;
-    hi = (_Float16)xs;
-    lo = (_Float16)(xs - (float)hi);
-    if (!(fabsf(xs) < INFINITY)) {
-        hi = (_Float16)0.f;
-        lo = (_Float16)xs;
-    }
-}
 
 template <bool KSPLIT>
 __global__ void __launch_bounds__(kThreads, 2)
@@ -78,12 +59,8 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
     int* const krow_s = reinterpret_cast<int*>(smem + kLds + kThreads * 8);
     long* rows = reinterpret_cast<long*>(smem + kLds + kThreads * 8 + kRows * 4);   // this tile's row offsets, and behind them
     long* rows_next = rows + kRows;                                                   // the next tile's (written while this tile's are read)
-    {
-        const int c = (KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128) + tid;
-        const bool live = c < dm.N && (!KSPLIT || tid < 64);
-        bias_s[tid] = (bias != nullptr && live) ? bias[c] : 0.f;
-        kc_s[tid] = live ? reinterpret_cast<const int*>(Wp + 2 * term_stride)[c] : 0;
-    }
+    fill_channel_tables<KSPLIT>(bias_s, kc_s, bias, reinterpret_cast<const int*>(Wp + 2 * term_stride), KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128,
+                                dm.N, tid);
 
     // persistent workgroups, one contiguous eighth of the row tiles per XCD (see conv3x3_kernel)
     const TileRange range = xcd_tile_range(dm.tiles);
@@ -129,16 +106,11 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
 #pragma unroll 1
             for (int c0 = 0; c0 < dm.K; c0 += kChunk) {
 #pragma unroll
-                for (int it = 0; it < kLoads; ++it) {
-                    const u32x4 v = *piece(it, c0);
-                    m[it] = max(max(m[it], max(finite_mag(v.x), finite_mag(v.y))), max(finite_mag(v.z), finite_mag(v.w)));
-                }
+                for (int it = 0; it < kLoads; ++it) m[it] = finite_mag4(m[it], *piece(it, c0));
             }
 #pragma unroll
             for (int it = 0; it < kLoads; ++it) {
-#pragma unroll
-                for (int o = kRowLanes / 2; o > 0; o >>= 1) m[it] = max(m[it], (unsigned)__shfl_xor((int)m[it], o, 64));
-                const int k = split_exponent(m[it]);
+                const int k = row_exponent<kRowLanes>(m[it]);
                 down[it] = ldexpf(1.0f, -k);
                 if (l16 == 0) krow_s[grp + kPassRows * it] = k;     // read by the epilogue, behind the chunk loop's barriers
             }
@@ -149,48 +121,23 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
 
         for (int c0 = 0; c0 < dm.K; c0 += kChunk) {
             // weights of k-step ks of this chunk, both terms
-            auto load_w = [&](WFrag& f, int ks) {
-                const f16_t* p = wfrag + (size_t)(c0 / 16 + ks) * 512;
-#pragma unroll
-                for (int term = 0; term < 2; ++term)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        f.v[term][b] = *reinterpret_cast<const u32x4*>(p + term * term_stride + b * ctile_stride);
-            };
+            auto load_w = [&](WFrag& f, int ks) { load_wfrag(f, wfrag + (size_t)(c0 / 16 + ks) * 512, term_stride, ctile_stride); };
             auto compute = [&](const WFrag& f, int ks) {
                 const unsigned char* a_base = xs + nl * kRowStride + kg * 16 + ks * 32;
-                u32x4 x[2][2];   // [row tile][term]
+                XFrag x;
 #pragma unroll
                 for (int term = 0; term < 2; ++term) {
-                    x[0][term] = *reinterpret_cast<const u32x4*>(a_base + term * kLoOffset);
-                    x[1][term] = *reinterpret_cast<const u32x4*>(a_base + 32 * kRowStride + term * kLoOffset);
+                    x.v[term][0] = *reinterpret_cast<const u32x4*>(a_base + term * kLoOffset);
+                    x.v[term][1] = *reinterpret_cast<const u32x4*>(a_base + 32 * kRowStride + term * kLoOffset);
                 }
-                // small cross terms first; the four tiles rotate, so no MFMA waits on the one before it
-#define ALO_GEMM_STEP(WT, XT)                                                                          \
-                _Pragma("unroll") for (int b = 0; b < 2; ++b)                                          \
-                _Pragma("unroll") for (int a = 0; a < 2; ++a)                                          \
-                    acc[a][b] = mfma_32x32x16<f16_t>(f.v[WT][b], x[a][XT], acc[a][b]);
-                ALO_GEMM_STEP(1, 0) ALO_GEMM_STEP(0, 1) ALO_GEMM_STEP(0, 0)
-#undef ALO_GEMM_STEP
+                mma_split(acc, f, x);
             };
             WFrag w0, w1;
             if (has_cols) load_w(w0, batch(0));
 
             // park the chunk: four channels of one row -> four hi terms and four lo terms
 #pragma unroll
-            for (int it = 0; it < kLoads; ++it) {
-                _Float16 hi[4], lo[4];
-                split2(__uint_as_float(stage[it].x), down[it], hi[0], lo[0]);
-                split2(__uint_as_float(stage[it].y), down[it], hi[1], lo[1]);
-                split2(__uint_as_float(stage[it].z), down[it], hi[2], lo[2]);
-                split2(__uint_as_float(stage[it].w), down[it], hi[3], lo[3]);
-                auto two = [](_Float16 e0, _Float16 e1) {
-                    return (unsigned)__builtin_bit_cast(uint16_t, e0) | ((unsigned)__builtin_bit_cast(uint16_t, e1) << 16);
-                };
-                unsigned char* dst = xs + (grp + kPassRows * it) * kRowStride + l16 * 8;
-                *reinterpret_cast<u32x2*>(dst) = u32x2{two(hi[0], hi[1]), two(hi[2], hi[3])};
-                *reinterpret_cast<u32x2*>(dst + kLoOffset) = u32x2{two(lo[0], lo[1]), two(lo[2], lo[3])};
-            }
+            for (int it = 0; it < kLoads; ++it) park4(xs + (grp + kPassRows * it) * kRowStride + l16 * 8, kLoOffset, stage[it], down[it]);
             const bool last = c0 + kChunk >= dm.K, more = tile + lanes_per_xcd < tile_end;
             if (last && more) tile_rows(tile + lanes_per_xcd, rows_next);
             __syncthreads();
@@ -200,7 +147,7 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
                 load_chunk(0);
             }
 
-            if (has_cols) {
+            if (has_cols) {   // (this loop as a shared function over the three lambdas: <true> 220 -> 234 VGPRs)
 #pragma unroll 1
                 for (int i = 0; i < my_batches; i += 2) {
                     if (i + 1 < my_batches) load_w(w1, batch(i + 1));
@@ -214,23 +161,7 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
 
         if (KSPLIT) {  // wave 1 hands its partial sums to wave 0
             float* red = reinterpret_cast<float*>(smem + kRedOffset);
-            if (wave == 1) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) red[((a * 2 + b) * 16 + r) * 64 + lane] = acc[a][b][r];
-            }
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[a][b][r] += red[((a * 2 + b) * 16 + r) * 64 + lane];
-            }
+            ALO_KSPLIT_HANDOFF(acc, red, wave, lane);
         }
 
         if (has_cols && !(KSPLIT && wave == 1)) {
@@ -239,7 +170,8 @@ linear_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, con
             const long row0 = (long)tile * kRows;
             const bool relu_first = dm.relu && R == nullptr;
             // lane = row 32 a + nl, registers 4 q .. 4 q + 3 = channels col0 + 32 b + 8 q + 4 kg .. + 3 (mfma_tile.hpp): one row tile at a
-            // time -> 2^(k_row + k_channel), bias (ReLU), one 16-byte LDS write per quad; then 16 lanes x 16 B per row (+ identity, ReLU)
+            // time -> 2^(k_row + k_channel), bias (ReLU), one 16-byte LDS write per quad; then 16 lanes x 16 B per row (+ identity, ReLU).
+            // (stage_scaled_quads' body: through the helper, encoder linear1 went 690.9 -> 699.6 us against spreads of 8.0 and 2.6)
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const int krow = krow_s[32 * a + nl];

@@ -37,6 +37,25 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[C]) {
         for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
 }
 
+// K-split (two waves take every other k-step of one 64-column block): wave 1 hands its partial sums to wave 0 through LDS, `red` =
+// [64 registers][64 lanes] of fp32, a fixed order.  A macro: as a function over f32x16 (&)[2][2], with or without the barrier inside,
+// the K-split kernels lose their register allocation (linear_f32_kernel<true> 220 -> 256 VGPRs and 36 to 104 bytes of scratch,
+// conv3x3_f32_kernel<2, true> 336 + 80 -> 400 + 144 registers).
+#define ALO_KSPLIT_HANDOFF(acc, red, wave, lane)                                                                                    \
+    do {                                                                                                                            \
+        if ((wave) == 1) {                                                                                                          \
+            _Pragma("unroll") for (int a_ = 0; a_ < 2; ++a_)                                                                        \
+            _Pragma("unroll") for (int b_ = 0; b_ < 2; ++b_)                                                                        \
+            _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (red)[((a_ * 2 + b_) * 16 + r_) * 64 + (lane)] = (acc)[a_][b_][r_];  \
+        }                                                                                                                           \
+        __syncthreads();                                                                                                            \
+        if ((wave) == 0) {                                                                                                          \
+            _Pragma("unroll") for (int a_ = 0; a_ < 2; ++a_)                                                                        \
+            _Pragma("unroll") for (int b_ = 0; b_ < 2; ++b_)                                                                        \
+            _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (acc)[a_][b_][r_] += (red)[((a_ * 2 + b_) * 16 + r_) * 64 + (lane)];  \
+        }                                                                                                                           \
+    } while (0)
+
 // ---- the quad epilogue ------------------------------------------------------------------------------------------------------------------
 // Column tile t of a wave's accumulators, f32x16[2] (one row tile) or f32x16[2][2] ([row tile][column tile]): + bias[column] when
 // ADD_BIAS, ReLU when `relu` (a constant in most callers, conv3x3_c64_kernel's run-time flag otherwise), -> T (one rounding to nearest

@@ -26,32 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from kernel_bounds import c_acc
-
-
-def split_exponent(absmax):
-    """split_exponent of csrc/split_f16.hpp: 2^-k absmax lands in [2^14, 2^15); 0 for zero, fp32-subnormal and non-finite values."""
-    if not np.isfinite(absmax) or absmax == 0:
-        return 0
-    e = int(np.floor(np.log2(float(absmax))))
-    if e < -126:
-        return 0
-    return int(np.clip(e - 14, -110, 110))
-
-
-def finite_amax(a):
-    mag = np.abs(a)
-    mag = np.where(np.isfinite(mag), mag, 0)
-    return float(mag.max()) if mag.size else 0.0
-
-
-def split_terms(a32, k):
-    """a 2^-k -> (hi, lo) as fp32 arrays holding fp16 values; a non-finite element -> (0, itself), as the kernel parks it."""
-    with np.errstate(over="ignore", invalid="ignore"):
-        s = np.ldexp(a32, -k).astype(np.float32)                # exact
-        hi = s.astype(np.float16).astype(np.float32)
-        lo = (s - hi).astype(np.float16).astype(np.float32)     # the difference is exact in fp32, then rounded
-        bad = ~np.isfinite(s)
-        return np.where(bad, np.float32(0), hi), np.where(bad, s, lo)
+from split_f16_ref import finite_amax, split_exponent, split_terms  # noqa: F401  (re-exported)
 
 
 def windows(x, stride):

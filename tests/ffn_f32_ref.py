@@ -29,9 +29,9 @@ import numpy as np
 import torch
 
 import linear_f32_ref
-from conv_f32_ref import split_terms
 from kernel_bounds import c_acc
-from linear_f32_ref import linear_split, row_exponents, split_weight     # conv_f32_ref's split_exponent / finite_amax per row and channel
+from linear_f32_ref import linear_split
+from split_f16_ref import row_exponents, split_terms, split_weight
 
 CHUNK = 256
 

@@ -17,21 +17,8 @@ holds one are compared for kind (kernel_bounds.compare), not for value.
 import numpy as np
 import torch
 
-from conv_f32_ref import finite_amax, split_exponent, split_terms
 from kernel_bounds import c_acc
-
-
-def row_exponents(a):
-    """split_exponent of every row's largest finite magnitude -> int32 (rows,)."""
-    amax = np.where(np.isfinite(a), np.abs(a), 0).max(axis=1) if a.shape[1] else np.zeros(a.shape[0])
-    return np.array([split_exponent(np.float32(v)) for v in amax], dtype=np.int32)
-
-
-def split_weight(w):
-    """(N, K) fp32 -> (hi, lo, k): what alo_hip._split_weight packs (fp32 arrays holding fp16 values; int32 exponents)."""
-    k = np.array([split_exponent(np.float32(finite_amax(r))) for r in w], dtype=np.int32)
-    hi, lo = split_terms(w, k[:, None])
-    return hi, lo, k
+from split_f16_ref import row_exponents, split_terms, split_weight
 
 
 def linear_split(x, w, b=None, res=None, relu=False):
