@@ -827,6 +827,38 @@ def gru_update_(q, bias_q, zr, hx, C, net=None):
             B, C, H * W, hx.stride(0))
 
 
+def _require_f32_rows(name, t, cols=None):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and (cols is None or t.shape[1] == cols)):
+        raise RuntimeError(f"{name} must be a contiguous float32 CUDA matrix (rows, {'channels' if cols is None else cols})")
+
+
+def gru_gate_rows_(zr, bias_zr, hx, rhx, C):
+    """:func:`gru_gate_` channels-last: ``zr`` (rows, 2C), ``hx`` / ``rhx`` (rows, C + Cx), a row per pixel; C % 4 == 0.  The planar
+    call's results bit for bit."""
+    _no_autograd("gru_gate_rows_", zr, bias_zr, hx, rhx)
+    _require_f32_rows("zr", zr, 2 * C); _require_f32_rows("hx", hx); _require_f32_rows("rhx", rhx)
+    rows = zr.shape[0]
+    if C % 4 or hx.shape != rhx.shape or hx.shape[0] != rows or hx.shape[1] < C or hx.shape[1] % 4 or bias_zr.numel() != 2 * C:
+        raise RuntimeError("gru_gate_rows_: zr must be (rows, 2C), hx / rhx (rows, C + Cx), bias_zr (2C,), C and C + Cx multiples of 4")
+    _launch("alo_gru_gate", zr.device, f"gru_gate_rows/C={C}", 4.0 * rows * C * 5, 0.0, zr, bias_zr.float().contiguous(), hx, rhx, rows, C, 1,
+            hx.stride(0), rhx.stride(0))
+
+
+def gru_update_rows_(q, bias_q, zr, hx, C, net=None):
+    """:func:`gru_update_` channels-last: ``q`` and ``net`` (rows, C), ``zr`` (rows, 2C), ``hx`` (rows, C + Cx)."""
+    _no_autograd("gru_update_rows_", q, bias_q, zr, hx, net)
+    _require_f32_rows("q", q, C); _require_f32_rows("zr", zr, 2 * C); _require_f32_rows("hx", hx)
+    rows = q.shape[0]
+    if C % 4 or zr.shape[0] != rows or hx.shape[0] != rows or hx.shape[1] < C or hx.shape[1] % 4 or bias_q.numel() != C:
+        raise RuntimeError("gru_update_rows_: q must be (rows, C), zr (rows, 2C), hx (rows, C + Cx), bias_q (C,), C and C + Cx multiples of 4")
+    if net is not None:
+        _require_f32_rows("net", net, C)
+        if net.shape[0] != rows:
+            raise RuntimeError("gru_update_rows_: net must be (rows, C)")
+    _launch("alo_gru_update", q.device, f"gru_update_rows/C={C}", 4.0 * rows * C * (4 + (net is not None)), 0.0, q, bias_q.float().contiguous(),
+            zr, hx, net, rows, C, 1, hx.stride(0))
+
+
 def pos_sine_flat(mask_flatten, spatial_shapes, level_start_index, dim_t, level_embed, normalize, center, scale, dtype,
                   eps=1e-6):
     """Sine positional encoding of the flattened pyramid + level embedding -> (B, S, 2F) in ``dtype`` (two launches).
@@ -1279,7 +1311,7 @@ def split_exponent(absmax):
 
 
 def _split_weight(weight):
-    """``w_packed`` of an ALO_F32 call of ``alo_conv3x3_nhwc`` (a (Cout, Cin, 3, 3) weight), ``alo_linear_packed`` or
+    """``w_packed`` of an ALO_F32 call of ``alo_conv3x3_nhwc`` (a (Cout, Cin, 3, 3), (1, 5) or (5, 1) weight), ``alo_linear_packed`` or
     ``alo_conv1x1_nhwc`` (a (N, K) weight) as one uint8 tensor (include/alo_hotpath.h): the packed high terms, the packed low terms,
     the output channels' exponents."""
     if weight.dim() == 4:
@@ -1315,6 +1347,41 @@ def conv3x3_f32(x, weight, bias=None, relu=False, stride=1):
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
     _launch("alo_conv3x3_nhwc", x.device, f"conv3x3_f32/C={cin}/s={stride}", 4.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
             x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_F32)
+    return y
+
+
+ALO_CONV_TAPS_1X5, ALO_CONV_TAPS_5X1 = 0x100, 0x200   # include/alo_hotpath.h: OR-ed into alo_conv3x3_nhwc's stride
+_CONV_TAPS = {(1, 5): ((0, 2), ALO_CONV_TAPS_1X5, "1x5"), (5, 1): ((2, 0), ALO_CONV_TAPS_5X1, "5x1")}   # kernel -> padding, flag, name
+
+
+def conv_taps_f32_supported(x, weight, padding):
+    """1x5 / padding (0, 2) or 5x1 / padding (2, 0) convolution (stride 1, no dilation, no groups) of a channels-last fp32 CUDA
+    activation with an fp32 weight, Cin % 64 == 0, Cout % 64 == 0, no autograd."""
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and weight.dim() == 4
+            and tuple(weight.shape[2:]) in _CONV_TAPS and tuple(padding) == _CONV_TAPS[tuple(weight.shape[2:])][0]
+            and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0 and weight.shape[0] % 64 == 0
+            and x.is_contiguous(memory_format=torch.channels_last) and not torch.is_grad_enabled())
+
+
+def conv_taps_f32(x, weight, bias=None, relu=False):
+    """``act(F.conv2d(x, weight, bias, 1, padding))`` for a (Cout, Cin, 1, 5) weight with padding (0, 2) or a (Cout, Cin, 5, 1) weight with
+    padding (2, 0) — RAFT's SepConvGRU — on a channels-last fp32 ``x``: the arithmetic of :func:`conv3x3_f32` over five taps
+    (csrc/conv_f32.hip, conv_taps_f32_kernel).  Returns a channels-last fp32 (N, Cout, H, W) tensor."""
+    _no_autograd("conv_taps_f32", x, weight, bias)
+    taps = _CONV_TAPS.get(tuple(weight.shape[2:])) if weight.dim() == 4 else None
+    if taps is None or not conv_taps_f32_supported(x, weight, taps[0]):
+        raise RuntimeError("conv_taps_f32: needs a channels-last fp32 CUDA activation, an fp32 (Cout, Cin, 1, 5) or (Cout, Cin, 5, 1) weight, "
+                           "Cin % 64 == 0, Cout % 64 == 0, no autograd")
+    _, flag, name = taps
+    n, cin, h, w_ = x.shape
+    cout = weight.shape[0]
+    packed = derived(weight, "conv_taps_f32_b", (weight,), lambda: _split_weight(weight))   # tap-major (Cout, 5 Cin) either way
+    y = torch.empty((n, cout, h, w_), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    bias_c = None if bias is None else bias.float().contiguous()
+    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, 1 | flag) + (4 * n + 255) // 256 * 256   # the per-image magnitudes
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
+    _launch("alo_conv3x3_nhwc", x.device, f"conv{name}_f32/C={cin}", 4.0 * (x.numel() + y.numel()), 2.0 * 5 * cin * y.numel(),
+            x, packed, bias_c, y, ws, n, h, w_, cin, cout, 1 | flag, 1 if relu else 0, ALO_F32)
     return y
 
 

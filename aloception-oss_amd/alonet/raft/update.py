@@ -40,6 +40,12 @@ def _split_route():
 _CL = torch.channels_last
 
 
+def _gru_split_route():
+    """``ALO_RAFT_GRU=split``: SepConvGRU runs channels-last, its 1x5 / 5x1 convolutions on ``alo_hip.conv_taps_f32`` (fp32 on the fp16
+    matrix cores) and its gate passes on the channels-last flavour of alo_gru_gate / alo_gru_update.  Opt-in; read per call."""
+    return os.environ.get("ALO_RAFT_GRU") == "split"
+
+
 def _conv3x3_split(conv, x, relu, pad_to=None):
     """``act(conv(x))`` of a 3x3 / padding-1 ``conv`` on a channels-last fp32 ``x`` -> channels-last, bias and ReLU in the kernel's
     epilogue.  ``pad_to``: the output channels are zero-padded to that many (a multiple of 64; the padded weight and bias are
@@ -106,9 +112,45 @@ class SepConvGRU(nn.Module):
 
     def forward(self, h, x):
         if _fusable(h, x, self):
+            if _gru_split_route() and self.split_serves(h.shape[1], x.shape[1]):
+                hx, rhx = self.split_buffers(h, x.shape[1])
+                hx[:, h.shape[1]:].copy_(x)
+                return self.forward_split(hx, rhx, h.shape[1]).contiguous()   # callers of this module get NCHW, as on every route
             return self._forward_fused(h, x)
         h = _gru_step(h, x, self.convz1, self.convr1, self.convq1)
         return _gru_step(h, x, self.convz2, self.convr2, self.convq2)
+
+    def split_serves(self, C, Cx):
+        """The shapes ``alo_hip.conv_taps_f32`` takes: [h | x] a multiple of 64 channels, as are C and 2C."""
+        return C % 64 == 0 and (C + Cx) % 64 == 0 and self.convz1.weight.shape[:2] == (C, C + Cx)
+
+    @staticmethod
+    def split_buffers(h, Cx):
+        """The channels-last [h | x] and [r*h | x] buffers of :meth:`forward_split` with ``h`` in place; the caller fills
+        ``hx[:, C:]`` with x (``forward_split`` copies it to ``rhx``)."""
+        B, C, H, W = h.shape
+        hx = torch.empty((B, C + Cx, H, W), dtype=h.dtype, device=h.device, memory_format=_CL)
+        hx[:, :C].copy_(h)
+        return hx, torch.empty_like(hx)
+
+    def forward_split(self, hx, rhx, C):
+        """``_forward_fused`` channels-last (``ALO_RAFT_GRU=split``): a buffer is a (rows, C + Cx) matrix, a row per pixel; the four
+        convolutions run on ``alo_hip.conv_taps_f32`` without bias and the gate passes add it.  All four launches beat what
+        ``_forward_fused`` launches in their place (docs/experiments.md, "SepConvGRU on the split family").  -> net, channels-last."""
+        B, Ct, H, W = hx.shape
+        rows = lambda t: t.permute(0, 2, 3, 1).view(B * H * W, t.shape[1])   # noqa: E731  (a channels-last map as a matrix)
+        rhx[:, C:].copy_(hx[:, C:])
+        net = torch.empty((B, C, H, W), dtype=hx.dtype, device=hx.device, memory_format=_CL)
+        halves = ((self.convz1, self.convr1, self.convq1), (self.convz2, self.convr2, self.convq2))
+        for i, (cz, cr, cq) in enumerate(halves):
+            wzr, bzr = alo_hip.derived(self, f"zr{i}", (cz.weight, cr.weight, cz.bias, cr.bias),
+                                       lambda: (torch.cat([cz.weight, cr.weight], 0).contiguous(),
+                                                torch.cat([cz.bias, cr.bias], 0).contiguous()))
+            zr = rows(alo_hip.conv_taps_f32(hx, wzr))
+            alo_hip.gru_gate_rows_(zr, bzr, rows(hx), rows(rhx), C)
+            q = rows(alo_hip.conv_taps_f32(rhx, cq.weight))
+            alo_hip.gru_update_rows_(q, cq.bias, zr, rows(hx), C, rows(net) if i == 1 else None)
+        return net
 
     def _forward_fused(self, h, x):
         """Same arithmetic, different plumbing: the z and r convolutions of a pass are ONE convolution with 2C outputs,
@@ -159,10 +201,11 @@ class BasicMotionEncoder(nn.Module):
         self.convf2 = nn.Conv2d(128, 64, 3, padding=1)
         self.conv = nn.Conv2d(64 + 192, 128 - out_planes, 3, padding=1)
 
-    def _forward_split(self, flow, corr):
+    def _forward_split(self, flow, corr, into=None):
         """The fused route with convc2 and conv on conv3x3_f32: channels-last from convc1's GEMM (which reads the NCHW lookup
         transposed) to conv's output.  convf2 stays on MIOpen (a tie at this shape, docs/experiments.md, and its input is NCHW):
-        its output turns channels-last inside the concatenation, and conv's turns NCHW inside the one with the flow."""
+        its output turns channels-last inside the concatenation, and conv's turns NCHW inside the one with the flow — or, with
+        ``into`` (a channels-last slice of SepConvGRU's [h | x] buffer), stays channels-last there."""
         B, _, H, W = flow.shape
         cor = _conv3x3_split(self.convc2, _conv1x1_to_nhwc(self.convc1, corr), True)
         flo = _conv_act(self.convf2, _conv_act(self.convf1, flow))
@@ -171,7 +214,7 @@ class BasicMotionEncoder(nn.Module):
         x[:, cor.shape[1]:].copy_(flo)
         out = _conv3x3_split(self.conv, x, True, pad_to=128)  # 126 -> 128 output channels
         k = self.conv.weight.shape[0]
-        enc = torch.empty((B, k + flow.shape[1], H, W), dtype=flow.dtype, device=flow.device)
+        enc = torch.empty((B, k + flow.shape[1], H, W), dtype=flow.dtype, device=flow.device) if into is None else into
         enc[:, :k].copy_(out[:, :k])
         enc[:, k:].copy_(flow)
         return enc
@@ -211,15 +254,33 @@ class BasicUpdateBlock(nn.Module):
         self.flow_head = FlowHead(hidden_dim, hidden_dim=256, out_planes=out_planes)
         self.mask = nn.Sequential(nn.Conv2d(128, 256, 3, padding=1), nn.ReLU(inplace=True), nn.Conv2d(256, 64 * 9, 1))
 
+    def _gru_channels_last(self, net, inp, corr, flow):
+        """Both knobs (``ALO_RAFT_CONV3X3=split`` and ``ALO_RAFT_GRU=split``): the encoder writes its channels-last output straight
+        into the GRU's [h | x] buffer, and ``net`` stays channels-last from one iteration to the next and into the heads.  -> net
+        (channels-last), or None when a shape or a layout is not the route's."""
+        enc, C, Ci = self.encoder, net.shape[1], inp.shape[1]
+        Cx = Ci + enc.conv.weight.shape[0] + flow.shape[1]
+        if not (_split_route() and _gru_split_route() and _fusable(net, inp, corr, flow, self) and self.gru.split_serves(C, Cx)
+                and corr.is_contiguous() and flow.is_contiguous()):
+            return None
+        hx, rhx = self.gru.split_buffers(net, Cx)
+        hx[:, C:C + Ci].copy_(inp)
+        enc._forward_split(flow, corr, into=hx[:, C + Ci:])
+        return self.gru.forward_split(hx, rhx, C)
+
     def forward(self, net, inp, corr, flow, upsample=True):
-        inp = torch.cat([inp, self.encoder(flow, corr)], dim=1)
-        net = self.gru(net, inp)
+        net_cl = self._gru_channels_last(net, inp, corr, flow)
+        if net_cl is None:
+            inp = torch.cat([inp, self.encoder(flow, corr)], dim=1)
+            net = self.gru(net, inp)
+        else:
+            net = net_cl
         if _fusable(net, self.flow_head, self.mask):
             fh, m0, m2 = self.flow_head, self.mask[0], self.mask[2]
             # the 0.25 of the original RAFT (gradient balancing) is folded into the last convolution's weight and bias
             quarter = lambda: alo_hip.derived(self, "mask_quarter", (m2.weight, m2.bias), lambda: (0.25 * m2.weight, 0.25 * m2.bias))  # noqa: E731
-            if _split_route() and net.is_contiguous():
-                # net goes channels-last once for both heads; flow_head.conv2 (256 -> 2: the kernel would run 64 output channels for
+            if _split_route() and (net.is_contiguous() or net_cl is not None):
+                # net goes channels-last once for both heads (with ALO_RAFT_GRU=split it already is); flow_head.conv2 (256 -> 2: the kernel would run 64 output channels for
                 # 2 and is slower than MIOpen there, docs/experiments.md) stays on F.conv2d behind one copy back to NCHW; mask.2 (1x1)
                 # reads the channels-last map as the GEMM's transposed operand and writes NCHW
                 B, _, H, W = net.shape

@@ -471,6 +471,7 @@ int launch_conv_c64(const void* x, const void* w, const void* bias, void* y, con
 using namespace alo;
 
 extern "C" size_t alo_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride) {
+    // a stride that carries a five-tap flag (ALO_F32 only, conv_f32.hip) answers 0 here as well: those kernels never split K
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return 0;
     const long hwo = (long)((H - 1) / stride + 1) * ((W - 1) / stride + 1);
     const int z = conv_zsplit((int)((hwo + kPix - 1) / kPix) * N, Cin, Cout);
@@ -481,11 +482,18 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
                                 int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream) {
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0, ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: N, H, W must be positive");
+    // ALO_CONV_TAPS_1X5 / ALO_CONV_TAPS_5X1 ride above the stride's low byte (a negative stride is no flagged one)
+    const int taps = stride > 0 ? stride & ~0xff : 0;
+    if (taps) stride &= 0xff;
     ALO_REQUIRE(stride == 1 || stride == 2, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: stride must be 1 or 2 (got %d)", stride);
+    ALO_REQUIRE(!taps || taps == ALO_CONV_TAPS_1X5 || taps == ALO_CONV_TAPS_5X1, ALO_ERR_UNSUPPORTED,
+                "alo_conv3x3_nhwc: stride carries 0x%x above its low byte: one of ALO_CONV_TAPS_1X5, ALO_CONV_TAPS_5X1 (five taps) or nothing", taps);
+    ALO_REQUIRE(!taps || stride == 1, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: the five-tap flavours (ALO_CONV_TAPS_*) are stride 1 only");
     ALO_REQUIRE(Cin >= 64 && Cin % 64 == 0 && Cout >= 64 && Cout % 64 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_nhwc: Cin and Cout must be multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
     // ALO_F32 (conv_f32.hip) is held to the checks of a bf16 call; every other dtype meets the refusal it always met
     ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: bf16 only (dtype %d)", dtype);
+    ALO_REQUIRE(!taps || dtype == ALO_F32, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: the five-tap flavours (ALO_CONV_TAPS_*) take ALO_F32 only");
     ALO_REQUIRE(aligned16(x, w_packed, y, workspace), ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: pointers must be 16-byte aligned");
     ALO_REQUIRE((long)H * W < (1L << 24) && (long)N * H * W * (long)(Cin > Cout ? Cin : Cout) < (1L << 40), ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_nhwc: image too large");
@@ -494,8 +502,10 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
                     "alo_conv3x3_nhwc: a workspace is required (alo_conv3x3_workspace_bytes + 4 N rounded up to 256 bytes)");
         ALO_REQUIRE(N <= 65535, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: image too large");
         // the per-image magnitudes sit behind the bytes alo_conv3x3_workspace_bytes reports (split-K partial sums: unused here)
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (taps) return conv_taps_f32(x, w_packed, bias, y, workspace, N, H, W, Cin, Cout, taps == ALO_CONV_TAPS_5X1, relu, s);
         void* const image_mag = static_cast<char*>(workspace) + alo_conv3x3_workspace_bytes(N, H, W, Cin, Cout, stride);
-        return conv3x3_f32(x, w_packed, bias, y, image_mag, N, H, W, Cin, Cout, stride, relu, static_cast<hipStream_t>(stream));
+        return conv3x3_f32(x, w_packed, bias, y, image_mag, N, H, W, Cin, Cout, stride, relu, s);
     }
     ConvDims dm;
     dm.N = N; dm.H = H; dm.W = W; dm.Cin = Cin; dm.Cout = Cout; dm.relu = relu;

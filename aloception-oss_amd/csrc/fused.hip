@@ -247,6 +247,51 @@ gru_update_kernel(const float* q, const float* __restrict__ bias_q, const float*
     }
 }
 
+// The same two passes channels-last: `rows` pixels of C channels each (the entry points' B = rows, HW = 1), zr (rows, 2C), q / net
+// (rows, C), h / rh the first C channels of (rows, C + Cx) buffers with row strides hb / rb.  Lanes run along the channels (C % 4 == 0);
+// the per-element formulas are the planar kernels', so the results are theirs bit for bit.
+__global__ void __launch_bounds__(kThreads)
+gru_gate_rows_kernel(float* zr, const float* __restrict__ bias_zr, const float* h, float* rh, long n4, int C4, long hb, long rb) {
+    const long stride = (long)gridDim.x * kThreads;
+    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
+        const long row = i / C4;
+        const int c = (int)(i - row * C4) * 4, C = C4 * 4;
+        const long zoff = row * 2 * C + c, roff = zoff + C;
+        float z[4], r[4], hv[4], bz[4], br[4];
+        load4(zr + zoff, z);
+        load4(zr + roff, r);
+        load4(h + row * hb + c, hv);
+        load4(bias_zr + c, bz);
+        load4(bias_zr + C + c, br);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            z[k] = sigmoidf_(z[k] + bz[k]);
+            r[k] = sigmoidf_(r[k] + br[k]) * hv[k];
+        }
+        store4(zr + zoff, z);
+        store4(rh + row * rb + c, r);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads)
+gru_update_rows_kernel(const float* q, const float* __restrict__ bias_q, const float* zr, float* h, float* net, long n4, int C4, long hb) {
+    const long stride = (long)gridDim.x * kThreads;
+    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
+        const long row = i / C4;
+        const int c = (int)(i - row * C4) * 4, C = C4 * 4;
+        const long hoff = row * hb + c;
+        float qv[4], z[4], hv[4], bq[4];
+        load4(q + i * 4, qv);
+        load4(zr + row * 2 * C + c, z);
+        load4(h + hoff, hv);
+        load4(bias_q + c, bq);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hv[k] = (1.0f - z[k]) * hv[k] + z[k] * tanhf(qv[k] + bq[k]);
+        store4(h + hoff, hv);
+        if (net != nullptr) store4(net + i * 4, hv);
+    }
+}
+
 // ---- sine positional encoding of the flattened pyramid (alonet/transformers/position_encoding.py:29-72) ---------------------
 // Pass 1: per (level, image) the cumulative count of un-padded pixels along y and along x, centred / normalised the way the
 // module does it, as (ey, ex) per pixel.  Work items are WAVES: one per 64 columns (a lane walks its column: coalesced byte loads,
@@ -434,6 +479,15 @@ extern "C" int alo_bias_act_nchw(const float* x, const float* bias, float* y, in
 extern "C" int alo_gru_gate(float* zr, const float* bias_zr, const float* h, float* rh, int B, int C, int HW,
                             long h_batch_stride, long rh_batch_stride, void* stream) {
     ALO_REQUIRE(zr && bias_zr && h && rh, ALO_ERR_INVALID_ARGUMENT, "alo_gru_gate: null pointer argument");
+    if (HW == 1 && B > 0 && C > 0) {   // channels-last: B rows of C channels
+        ALO_REQUIRE(C % 4 == 0 && h_batch_stride % 4 == 0 && rh_batch_stride % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
+                    "alo_gru_gate: channels-last rows (H*W = 1) need C and the row strides to be multiples of 4 (B=%d C=%d)", B, C);
+        ALO_REQUIRE(aligned16(zr, bias_zr, h, rh), ALO_ERR_INVALID_ARGUMENT, "alo_gru_gate: pointers must be 16-byte aligned");
+        long n4 = (long)B * C / 4;
+        int c4 = C / 4;
+        void* args[] = {&zr, &bias_zr, &h, &rh, &n4, &c4, &h_batch_stride, &rh_batch_stride};
+        return launch<gru_gate_rows_kernel>(stream_blocks(n4), kThreads, 0, static_cast<hipStream_t>(stream), "alo_gru_gate", args);
+    }
     ALO_REQUIRE(B > 0 && C > 0 && HW > 0 && HW % 4 == 0 && h_batch_stride % 4 == 0 && rh_batch_stride % 4 == 0,
                 ALO_ERR_INVALID_ARGUMENT, "alo_gru_gate: H*W and the batch strides must be multiples of 4 (B=%d C=%d HW=%d)",
                 B, C, HW);
@@ -447,6 +501,15 @@ extern "C" int alo_gru_gate(float* zr, const float* bias_zr, const float* h, flo
 extern "C" int alo_gru_update(const float* q, const float* bias_q, const float* zr, float* h, float* net, int B, int C,
                               int HW, long h_batch_stride, void* stream) {
     ALO_REQUIRE(q && bias_q && zr && h, ALO_ERR_INVALID_ARGUMENT, "alo_gru_update: null pointer argument");
+    if (HW == 1 && B > 0 && C > 0) {   // channels-last: B rows of C channels
+        ALO_REQUIRE(C % 4 == 0 && h_batch_stride % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
+                    "alo_gru_update: channels-last rows (H*W = 1) need C and the row stride to be multiples of 4 (B=%d C=%d)", B, C);
+        ALO_REQUIRE(aligned16(q, bias_q, zr, h, net), ALO_ERR_INVALID_ARGUMENT, "alo_gru_update: pointers must be 16-byte aligned");
+        long n4 = (long)B * C / 4;
+        int c4 = C / 4;
+        void* args[] = {&q, &bias_q, &zr, &h, &net, &n4, &c4, &h_batch_stride};
+        return launch<gru_update_rows_kernel>(stream_blocks(n4), kThreads, 0, static_cast<hipStream_t>(stream), "alo_gru_update", args);
+    }
     ALO_REQUIRE(B > 0 && C > 0 && HW > 0 && HW % 4 == 0 && h_batch_stride % 4 == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_gru_update: H*W and the batch stride must be multiples of 4 (B=%d C=%d HW=%d)", B, C, HW);
     ALO_REQUIRE(aligned16(q, zr, h, net), ALO_ERR_INVALID_ARGUMENT, "alo_gru_update: pointers must be 16-byte aligned");

@@ -439,7 +439,17 @@ int alo_conv3x3_small_nhwc(const void* x, const void* w_frag, const void* bias32
  * hi = fp16(w 2^-k_o), the same of the low terms lo = fp16(w 2^-k_o - hi), then the Cout exponents k_o as int32 (k_o brings row o's
  * largest magnitude into [2^14, 2^15)).  A workspace is REQUIRED: alo_conv3x3_workspace_bytes(...) + 4 * N rounded up to a multiple of
  * 256 bytes; the extra bytes, behind the others, hold the per-image magnitudes the exponents come from.  Same shape rules, same checks.
+ *
+ * dtype = ALO_F32 with a tap flag OR-ed into `stride` (stride = 1 | ALO_CONV_TAPS_1X5 or 1 | ALO_CONV_TAPS_5X1): the five-tap
+ * convolutions of RAFT's SepConvGRU (alonet/raft/update.py:94-133) on the same arithmetic — 1x5 with zero padding (0, 2), or 5x1 with
+ * zero padding (2, 0); stride 1, y (N, H, W, Cout).  w_packed is the fp32 flavour's buffer of the (Cout, 5 * Cin) tap-major matrix
+ * w[o][t * Cin + c] (= the channels-last memory order of a (Cout, Cin, 1, 5) or (Cout, Cin, 5, 1) weight).  The flags sit above the low
+ * byte, which still holds the stride.  A flag with ALO_BF16, with stride 2, both flags at once or any other bit above the low byte is
+ * refused (ALO_ERR_UNSUPPORTED, the message names the taps); every other check is the 3x3 call's.  alo_conv3x3_workspace_bytes takes the
+ * same flagged stride (it answers 0: no split-K; the 4 * N bytes of magnitudes come on top as above).
  */
+#define ALO_CONV_TAPS_1X5 0x100
+#define ALO_CONV_TAPS_5X1 0x200
 size_t alo_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride);
 int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void* bias, void* y, void* workspace, int N, int H, int W, int Cin,
                      int Cout, int stride, int relu, int dtype, void* stream);
@@ -530,6 +540,10 @@ int alo_pos_sine_flat(const void* padding_mask, const int32_t* spatial_shapes, c
  *                    rh <- sigmoid(r + bias_zr[C:]) * h             written into the first C channels of the [r*h | x] buffer
  * alo_gru_update:    h  <- (1 - z) * h + z * tanh(q + bias_q)       in place in the [h | x] buffer (+ contiguous copy `net`)
  *   h / rh are channel slices of (B, C + Cx, H, W) buffers: *_batch_stride = (C + Cx) * H * W elements.
+ *
+ * alo_gru_gate / alo_gru_update, channels-last: HW = 1 and B = the number of pixel rows (N * H * W).  zr is then (rows, 2C), q and net
+ * (rows, C), h / rh the first C channels of (rows, C + Cx) buffers and *_batch_stride their ROW stride (C + Cx) in elements.  C % 4 == 0;
+ * the bias pointers are 16-byte aligned as well.  Same formulas per element: the results are the planar calls' bit for bit.
  */
 int alo_bias_act_nchw(const float* x, const float* bias, float* y, int B, int C, int HW, int relu, void* stream);
 int alo_gru_gate(float* zr, const float* bias_zr, const float* h, float* rh, int B, int C, int HW,

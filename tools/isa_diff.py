@@ -10,7 +10,8 @@ as msda.hip's -fno-slp-vectorize are kept), `-c` replaced by `--offload-device-o
   * the resource figures of the code object's metadata (.vgpr_count, .agpr_count, .sgpr_count, .private_segment_fixed_size,
     .group_segment_fixed_size),
   * the instruction count and the count per opcode,
-  * the instruction sequence in order, register numbers ignored: class (a) identical, class (b) not.
+  * the instruction sequence in order, register numbers and a branch target's function ordinal (the N of `.LBBN_k`, which counts
+    the functions of the file) ignored: class (a) identical, class (b) not.
 
 Exit status 0: the same kernels on both sides, equal figures and equal counts everywhere (class (b) is reported, not an error).
 Exit status 1: anything else.  The assembly is kept under --out (default: a temporary directory) as A/<file>.s and B/<file>.s.
@@ -29,6 +30,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join("aloception-oss_amd", "csrc")
 FIGURES = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
+LABEL = re.compile(r"\.LBB\d+_(\d+)")   # .LBB<function's ordinal in its file>_<block>: the ordinal moves when a kernel is added before it
 
 
 def compile_command(tree, src, out):
@@ -87,7 +89,7 @@ def parse(path):
         kernels[k["name"]] = {
             "figures": {f: k.get(f, "?") for f in FIGURES},
             "ops": [t.split()[0] for t in body],
-            "seq": [REG.sub(r"\1#", t) for t in body],
+            "seq": [LABEL.sub(r".LBB#_\1", REG.sub(r"\1#", t)) for t in body],
         }
     return kernels
 
