@@ -1450,6 +1450,37 @@ def groupnorm_nhwc(x, norm, relu=False):
     return out
 
 
+def instancenorm_nhwc_f32_supported(x):
+    """``instancenorm_nhwc_f32`` covers: fp32 CUDA (N, C, H, W) channels-last maps with C % 64 == 0, C <= 256, no autograd."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 64 == 0 and 0 < x.shape[1] <= 256
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and not needs_autograd(x))
+
+
+def instancenorm_nhwc_f32(x, eps=1e-5, relu=False, out=None):
+    """``relu?(F.instance_norm(x, eps=eps))`` (no affine, no running statistics: ``nn.InstanceNorm2d``'s default) for a channels-last
+    fp32 map (N, C, H, W); channels-last result (csrc/instancenorm_f32.hip: chunk statistics, a merge, the normalise pass).  ``out``:
+    where the result goes — ``x`` itself (in place), or a channels-last (N, C, H, W) fp32 map whose images may lie further apart than
+    H * W * C elements; what lies between them is not touched."""
+    _no_autograd("instancenorm_nhwc_f32", x, out)
+    if not instancenorm_nhwc_f32_supported(x):
+        raise RuntimeError("instancenorm_nhwc_f32: needs a channels-last fp32 CUDA map with C % 64 == 0, C <= 256, no autograd")
+    n, c_, h, w_ = x.shape
+    if out is None:
+        out = torch.empty_like(x)           # preserves channels-last
+    elif (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or out.data_ptr() % 16
+          or any(out.stride(d) != s for d, s in ((1, 1), (2, w_ * c_), (3, c_)) if out.shape[d] > 1)
+          or (n > 1 and (out.stride(0) < h * w_ * c_ or out.stride(0) % 4))):
+        raise RuntimeError("instancenorm_nhwc_f32: out must be an fp32 (N, C, H, W) map of the input's shape and device with channels-last "
+                           "images, 16-byte aligned")
+    image_stride = out.stride(0) if n > 1 else h * w_ * c_
+    if n and h * w_:
+        nbytes = lib().alo_groupnorm_rows_workspace_bytes(n, h * w_, c_)
+        ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+        _launch("alo_groupnorm_rows_act", x.device, f"instancenorm_f32/C={c_}", 12.0 * x.numel(), 0.0, x, None, None, out, ws,
+                n, h * w_, c_, c_, float(eps), image_stride, 1 if relu else 0, ALO_F32)
+    return out
+
+
 def conv3x3_small_supported(x, conv):
     """``conv3x3_small`` covers: an ``nn.Conv2d`` 3x3 / stride 1 / padding 1 with Cin in (16, 32, 64) and Cout = 1 or 4k <= 32 on a
     channels-last bf16 CUDA map, no autograd."""

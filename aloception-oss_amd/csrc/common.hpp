@@ -128,6 +128,11 @@ int linear_f32(const void* x, const void* w_split, const void* bias, const void*
 int ffn_f32(const void* x, const void* w1_split, const void* b1, const void* w2_split, const void* b2, void* y, long M, int F,
             hipStream_t stream, const char* what);
 
+// instancenorm_f32.hip: the fp32 flavour of alo_groupnorm_rows_act on checked arguments (groups == C, no affine; alo_hotpath.h); the
+// workspace is the bf16 call's: a triple per 256-row chunk and channel.
+int instancenorm_f32(const void* x, void* y, void* workspace, int B, int HW, int C, float eps, long y_batch_stride, int relu,
+                     hipStream_t stream, const char* what);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

@@ -267,18 +267,31 @@ extern "C" size_t alo_groupnorm_rows_workspace_bytes(int B, int HW, int groups) 
 
 namespace {
 int groupnorm_rows_impl(const void* x, const void* weight, const void* bias, void* y, void* workspace, int B, int HW, int C, int groups,
-                        float eps, long y_batch_stride, int relu, int dtype, void* stream) {
-    ALO_REQUIRE(x && weight && bias && y && workspace, ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: null pointer argument");
+                        float eps, long y_batch_stride, int relu, bool act, int dtype, void* stream) {
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED,
+                "alo_groupnorm_rows: bf16, or fp32 InstanceNorm through alo_groupnorm_rows_act (dtype %d)", dtype);
+    const bool f32 = dtype == ALO_F32;   // InstanceNorm without affine (instancenorm_f32.hip): weight and bias are NULL there
+    ALO_REQUIRE(x && (f32 || (weight && bias)) && y && workspace, ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: null pointer argument");
     ALO_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0, ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: sizes must be positive");
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_groupnorm_rows: bf16 only (dtype %d)", dtype);
     const int cpg = C % groups == 0 ? C / groups : 0;
     const bool wide = cpg > 0 && cpg % 8 == 0, narrow = cpg == 2 || cpg == 4;
-    ALO_REQUIRE(C % 8 == 0 && kGnThreads % (C / 8) == 0 && (wide || narrow) && kGnThreads % groups == 0, ALO_ERR_UNSUPPORTED,
-                "alo_groupnorm_rows: needs C / 8 and groups to divide 256 and 2, 4 or a multiple of 8 channels per group (C=%d groups=%d)",
-                C, groups);
-    ALO_REQUIRE(y_batch_stride >= (long)HW * C && y_batch_stride % 8 == 0, ALO_ERR_INVALID_ARGUMENT,
+    if (f32) {
+        ALO_REQUIRE(act, ALO_ERR_UNSUPPORTED, "alo_groupnorm_rows: ALO_F32 is served by alo_groupnorm_rows_act alone");
+        ALO_REQUIRE(!weight && !bias, ALO_ERR_UNSUPPORTED,
+                    "alo_groupnorm_rows: ALO_F32 is InstanceNorm without affine: weight and bias must be NULL");
+        ALO_REQUIRE(groups == C && C % 64 == 0 && C <= 256 && B <= 65535, ALO_ERR_UNSUPPORTED,
+                    "alo_groupnorm_rows: ALO_F32 needs groups == C, C a multiple of 64 up to 256 and B <= 65535 (C=%d groups=%d B=%d)",
+                    C, groups, B);
+    } else {
+        ALO_REQUIRE(C % 8 == 0 && kGnThreads % (C / 8) == 0 && (wide || narrow) && kGnThreads % groups == 0, ALO_ERR_UNSUPPORTED,
+                    "alo_groupnorm_rows: needs C / 8 and groups to divide 256 and 2, 4 or a multiple of 8 channels per group (C=%d groups=%d)",
+                    C, groups);
+    }
+    ALO_REQUIRE(y_batch_stride >= (long)HW * C && y_batch_stride % (f32 ? 4 : 8) == 0, ALO_ERR_INVALID_ARGUMENT,
                 "alo_groupnorm_rows: y_batch_stride must cover HW * C and keep rows 16-byte aligned");
     ALO_REQUIRE(aligned16(x, weight, bias, y, workspace), ALO_ERR_INVALID_ARGUMENT, "alo_groupnorm_rows: pointers must be 16-byte aligned");
+    if (f32)   // the workspace is the one alo_groupnorm_rows_workspace_bytes(B, HW, C) answers: a triple per kGnRows-row chunk and channel
+        return instancenorm_f32(x, y, workspace, B, HW, C, eps, y_batch_stride, relu, static_cast<hipStream_t>(stream), "alo_groupnorm_rows");
     GnDims dm;
     dm.HW = HW; dm.C = C; dm.groups = groups; dm.nchunks = (HW + kGnRows - 1) / kGnRows;
     dm.y_batch_stride = y_batch_stride; dm.eps = eps; dm.relu = relu ? 1 : 0;
@@ -299,12 +312,12 @@ int groupnorm_rows_impl(const void* x, const void* weight, const void* bias, voi
 
 extern "C" int alo_groupnorm_rows(const void* x, const void* weight, const void* bias, void* y, void* workspace, int B, int HW,
                                   int C, int groups, float eps, long y_batch_stride, int dtype, void* stream) {
-    return groupnorm_rows_impl(x, weight, bias, y, workspace, B, HW, C, groups, eps, y_batch_stride, 0, dtype, stream);
+    return groupnorm_rows_impl(x, weight, bias, y, workspace, B, HW, C, groups, eps, y_batch_stride, 0, false, dtype, stream);
 }
 
 extern "C" int alo_groupnorm_rows_act(const void* x, const void* weight, const void* bias, void* y, void* workspace, int B, int HW,
                                       int C, int groups, float eps, long y_batch_stride, int relu, int dtype, void* stream) {
-    return groupnorm_rows_impl(x, weight, bias, y, workspace, B, HW, C, groups, eps, y_batch_stride, relu, dtype, stream);
+    return groupnorm_rows_impl(x, weight, bias, y, workspace, B, HW, C, groups, eps, y_batch_stride, relu, true, dtype, stream);
 }
 
 extern "C" int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* out, int BQ, int Q, int C, int h, int w, int H, int W,

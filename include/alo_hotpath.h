@@ -51,7 +51,8 @@ typedef enum alo_status {
  * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
  * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
- * (alo_conv3x3_nhwc, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32: see there).
+ * (alo_conv3x3_nhwc, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32, and alo_groupnorm_rows_act serves it as an
+ * InstanceNorm: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -479,6 +480,14 @@ int alo_groupnorm_rows(const void* x, const void* weight, const void* bias, void
  * optional ReLU in the normalise pass: the GroupNorm(8, 32) / GroupNorm(8, 16) + ReLU of PanopticHead's mask decoder over B*Q maps of
  * up to 200 x 334 pixels (alonet/detr_panoptic/nn/FPNstyle.py:24-36,60-84), channels-last in and out — ATen's GroupNorm takes NCHW,
  * i.e. a layout copy either side of every one of them.
+ *
+ * dtype = ALO_F32: InstanceNorm (+ ReLU) of fp32 rows, nn.InstanceNorm2d of RAFT's feature encoder (alonet/raft/extractor.py) between
+ * channels-last convolutions.  groups == C, C % 64 == 0, C <= 256; weight == bias == NULL (no affine); x, y fp32 (B, HW, C), y may be x;
+ * biased variance, as torch.nn.functional.instance_norm with use_input_stats.  Every other fp32 call (groups != C, an affine, and
+ * alo_groupnorm_rows itself) is ALO_ERR_UNSUPPORTED.  Statistics per 256-row chunk from two passes over registers (the squared
+ * distances to the rows' own mean, never sum-of-squares minus square-of-sum), chunks merged by Chan's formula in a launch of its own,
+ * then y = (x - mean) * rstd: deterministic, no atomics; a non-finite element makes its own (image, channel) non-finite and no other.
+ * The workspace is the same alo_groupnorm_rows_workspace_bytes(B, HW, groups) bytes.
  */
 int alo_groupnorm_rows_act(const void* x, const void* weight, const void* bias, void* y, void* workspace, int B, int HW, int C,
                            int groups, float eps, long y_batch_stride, int relu, int dtype, void* stream);
