@@ -24,8 +24,8 @@ ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
 # fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
 # value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
-# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32, linear_f32 and
-# conv1x1_strided_f32 are the fp32 flavours of three of them, each behind a gate of its own).  fp16 is opt-in per call site: `fusable`
+# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32, stem_conv_pool_f32, linear_f32
+# and conv1x1_strided_f32 are the fp32 flavours of four of them, each behind a gate of its own).  fp16 is opt-in per call site: `fusable`
 # and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
 # fp16 kernels do (the transformer's layers), so an fp16 tensor never reaches a kernel that lacks it
 _DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
@@ -1042,9 +1042,10 @@ def conv1x1_chain(mid, conv3, identity=None, down=None, nxt=None):
 
 # ---- fp32 linear layers and 1x1 convolutions on the fp16 matrix cores (alo_linear_packed / alo_conv1x1_nhwc with ALO_F32) -----------
 def f32_layers_split():
-    """``ALO_F32_LAYERS=split``: at inference the fp32 linear layers, 1x1 and 3x3 convolutions that the split kernels serve
-    (:func:`linear_f32`, :func:`conv1x1_strided_f32`, :func:`conv3x3_f32`: fp32 on the fp16 matrix cores, two-term splits of both
-    operands) take them instead of hipBLASLt / MIOpen.  Read per call; unset, every route is what it was."""
+    """``ALO_F32_LAYERS=split``: at inference the fp32 linear layers, 1x1 and 3x3 convolutions, feed-forward blocks and the ResNet
+    stem that the split kernels serve (:func:`linear_f32`, :func:`conv1x1_strided_f32`, :func:`conv3x3_f32`, :func:`ffn_f32`,
+    :func:`stem_conv_pool_f32`: fp32 on the fp16 matrix cores, two-term splits of both operands) take them instead of hipBLASLt /
+    MIOpen.  Read per call; unset, every route is what it was."""
     return os.environ.get("ALO_F32_LAYERS") == "split"
 
 
@@ -1413,6 +1414,55 @@ def stem_conv_pool(x, weight, bias=None):
     sn, sc, sh, sw = x.stride()
     _launch("alo_stem_conv_pool", x.device, "stem_conv_pool", 2.0 * (x.numel() + y.numel()), 2.0 * 147 * 64 * n * hc * wc,
             x, packed, bias_c, y, n, h, w_, sn, sc, sh, sw, ALO_BF16)
+    return y
+
+
+# ---- the fp32 stem in one kernel on the fp16 matrix cores (alo_stem_conv_pool with ALO_F32) ------------------------------------------
+def stem_conv_pool_f32_supported(x, weight):
+    """fp32 CUDA (N, 3, H, W) image (any strides), (64, 3, 7, 7) fp32 weight, no autograd on either."""
+    return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3
+            and tuple(weight.shape) == (64, 3, 7, 7) and not needs_autograd(x, weight))
+
+
+# Whether ``ALO_F32_LAYERS=split`` sends the fp32 ResNet stem to :func:`stem_conv_pool_f32`: the kernel against what the default fp32
+# route launches (channels-last copy + MIOpen's 7x7 + bias_act_ + max_pool2d), tools/stembench_f32.py on MI355X, medians (min - max) of
+# 5 rounds x 20 calls; docs/experiments.md, section "`stem_conv_pool_f32`".  8 x 3 x 800 x 1333: 384.4 us (382.7 - 408.5) against 1000.9
+# (998.3 - 1026.6), 0.38; 1 x 3 x 800 x 1333: 60.7 (60.2 - 63.0) against 141.4 (140.3 - 145.8), 0.43: below the stock median by more than
+# both spreads at both, so the route is on
+STEM_F32_ROUTED = True
+
+
+def stem_f32_routed(x, weight):
+    """Whether the backbone's fp32 stem takes :func:`stem_conv_pool_f32`: the switch is set (:func:`f32_layers_split`), the kernel
+    serves the operands and it was measured to win (:data:`STEM_F32_ROUTED`)."""
+    return STEM_F32_ROUTED and f32_layers_split() and stem_conv_pool_f32_supported(x, weight)
+
+
+def stem_matrix(weight):
+    """The (64, 176) matrix of ``alo_stem_conv_pool`` from a (64, 3, 7, 7) weight: per tap row the 7 taps x 3 channels interleaved as
+    the staged image rows are, then 3 zero columns; the eighth tap row is cut after its first 8 (zero) columns."""
+    wm = torch.zeros((64, 8, 24), dtype=weight.dtype, device=weight.device)
+    wm[:, :7, :21] = weight.permute(0, 2, 3, 1).reshape(64, 7, 21)
+    return wm.reshape(64, 192)[:, :176].contiguous()
+
+
+def stem_conv_pool_f32(x, weight, bias=None):
+    """``max_pool2d(relu(conv2d(x, weight, bias, stride=2, padding=3)), 3, 2, 1)`` — the ResNet stem — for an fp32 image of any strides
+    in one kernel on the fp16 matrix cores at fp32-class accuracy (csrc/stem_f32.hip: :func:`conv3x3_f32`'s two-term splits, a power
+    of two per output channel and per staged window of the image).  Returns a channels-last (N, 64, Hp, Wp) fp32 tensor."""
+    _no_autograd("stem_conv_pool_f32", x, weight, bias)
+    if not stem_conv_pool_f32_supported(x, weight):
+        raise RuntimeError("stem_conv_pool_f32: needs an fp32 CUDA (N, 3, H, W) image, a (64, 3, 7, 7) fp32 weight, no autograd")
+    n, _, h, w_ = x.shape
+    packed = derived(weight, "stem_f32_b", (weight,), lambda: _split_weight(stem_matrix(weight)))
+    hc, wc = (h - 1) // 2 + 1, (w_ - 1) // 2 + 1
+    hp, wp = (hc - 1) // 2 + 1, (wc - 1) // 2 + 1
+    y = torch.empty((n, 64, hp, wp), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if y.numel():
+        bias_c = None if bias is None else bias.float().contiguous()
+        sn, sc, sh, sw = x.stride()
+        _launch("alo_stem_conv_pool", x.device, "stem_conv_pool_f32", 4.0 * (x.numel() + y.numel()), 2.0 * 147 * 64 * n * hc * wc,
+                x, packed, bias_c, y, n, h, w_, sn, sc, sh, sw, ALO_F32)
     return y
 
 

@@ -236,12 +236,23 @@ class ResNetBody(nn.Module):
         layers += [Bottleneck(self.inplanes, planes, 1, self.dilation, None, norm_layer) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
-    def _stem_fusable(self, x):
+    def _stem_geometry(self):
+        """conv1 / bn1 / maxpool are what the one-kernel stems compute: a 7x7 / stride 2 / padding 3 convolution without bias, a frozen
+        batch-norm, a 3x3 / stride 2 / padding 1 max-pool."""
         c, p = self.conv1, self.maxpool
-        return (alo_hip.stem_conv_pool_supported(x, c.weight) and isinstance(self.bn1, FrozenBatchNorm2d) and c.bias is None
+        return (isinstance(self.bn1, FrozenBatchNorm2d) and c.bias is None
                 and c.stride == (2, 2) and c.padding == (3, 3) and c.dilation == (1, 1) and c.groups == 1
                 and isinstance(p, nn.MaxPool2d) and p.kernel_size == 3 and p.stride == 2 and p.padding == 1
                 and p.dilation == 1 and not p.ceil_mode)
+
+    def _stem_fusable(self, x):
+        return alo_hip.stem_conv_pool_supported(x, self.conv1.weight) and self._stem_geometry()
+
+    def _stem_f32_routed(self, x):
+        """ALO_F32_LAYERS=split: the fp32 stem on the split kernel — where it was measured to win (alo_hip.stem_f32_routed), for the
+        same modules as the bf16 one, with nothing on the way that autograd would have to see."""
+        return (alo_hip.stem_f32_routed(x, self.conv1.weight) and self._stem_geometry()
+                and alo_hip.fusable(x, self.conv1, self.bn1))
 
     def forward(self, x):
         out = {}
@@ -252,6 +263,10 @@ class ResNetBody(nn.Module):
             # (the largest activation of the network) never reaches memory
             w, b = folded_conv_bn(self.conv1, self.bn1)
             x = alo_hip.stem_conv_pool(x, w, b)
+        elif self._stem_f32_routed(x):
+            # the same in fp32 on the fp16 matrix cores; the image goes in as it is, no channels-last copy first
+            w, b = folded_conv_bn(self.conv1, self.bn1)
+            x = alo_hip.stem_conv_pool_f32(x, w, b)
         else:
             x = x.contiguous(memory_format=torch.channels_last)
             x = self.maxpool(conv_bn(x, self.conv1, self.bn1, relu=True))

@@ -128,6 +128,10 @@ int linear_f32(const void* x, const void* w_split, const void* bias, const void*
 int ffn_f32(const void* x, const void* w1_split, const void* b1, const void* w2_split, const void* b2, void* y, long M, int F,
             hipStream_t stream, const char* what);
 
+// stem_f32.hip: the fp32 flavour of alo_stem_conv_pool on checked arguments (w_split: alo_hotpath.h); refuses a batch with 2^30 tiles or more.
+int stem_conv_pool_f32(const void* x, const void* w_split, const void* bias, void* y, int N, int H, int W, long stride_n, long stride_c,
+                       long stride_h, long stride_w, hipStream_t stream);
+
 // instancenorm_f32.hip: the fp32 flavour of alo_groupnorm_rows_act on checked arguments (groups == C, no affine; alo_hotpath.h); the
 // workspace is the bf16 call's: a triple per 256-row chunk and channel.
 int instancenorm_f32(const void* x, void* y, void* workspace, int B, int HW, int C, float eps, long y_batch_stride, int relu,

@@ -199,8 +199,10 @@ extern "C" int alo_stem_conv_pool(const void* x, const void* w_packed, const voi
                                   long stride_n, long stride_c, long stride_h, long stride_w, int dtype, void* stream) {
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0, ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: N, H, W must be positive");
-    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "alo_stem_conv_pool: bf16 only (dtype %d)", dtype);
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED, "alo_stem_conv_pool: bf16 only (dtype %d)", dtype);
     ALO_REQUIRE(aligned16(w_packed, y), ALO_ERR_INVALID_ARGUMENT, "alo_stem_conv_pool: w_packed and y must be 16-byte aligned");
+    if (dtype == ALO_F32)   // fp32 on the fp16 matrix cores (stem_f32.hip): w_packed holds both split terms and the channel exponents
+        return stem_conv_pool_f32(x, w_packed, bias, y, N, H, W, stride_n, stride_c, stride_h, stride_w, static_cast<hipStream_t>(stream));
     StemDims dm;
     dm.N = N; dm.H = H; dm.W = W;
     dm.Hc = (H - 1) / 2 + 1; dm.Wc = (W - 1) / 2 + 1;        // (H + 6 - 7) / 2 + 1

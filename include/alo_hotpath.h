@@ -51,8 +51,8 @@ typedef enum alo_status {
  * alo_two_stage.h).  There storage is fp16 and arithmetic fp32; each result is rounded once, to nearest even, and a result outside the
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
  * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
- * (alo_conv3x3_nhwc, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32, and alo_groupnorm_rows_act serves it as an
- * InstanceNorm: see there).
+ * (alo_conv3x3_nhwc, alo_stem_conv_pool, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32, and
+ * alo_groupnorm_rows_act serves it as an InstanceNorm: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -461,6 +461,16 @@ int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void* bias, void
  * folded into weight and bias).  x is a (N, 3, H, W) bf16 image addressed through its ELEMENT strides (NCHW or channels-last);
  * Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1.  w_packed = alo_pack_mfma_b of the (64, 176) matrix
  * m[o][ky * 24 + kx * 3 + c] = w[o][c][ky][kx] (zero elsewhere).  The half-resolution convolution output never reaches memory.
+ *
+ * dtype = ALO_F32: x, bias and y are fp32 (x again through its element strides: NCHW, channels-last or a window of a larger tensor) and
+ * the product runs on the fp16 matrix cores at fp32-class accuracy, the two-term split of alo_conv3x3_nhwc's fp32 flavour: one power of
+ * two per output channel, and one per WINDOW of the image — the 39 x 35 x 3 pixels (zero outside the image) behind a tile of 8 x 7
+ * pooled pixels, found inside the launch from the window's largest finite magnitude, so a pooled pixel depends on its tile's window
+ * only and no workspace is needed.  Three cross products, fp32 accumulation; the undo, the bias, ReLU (NaN kept) and the pool (a NaN
+ * stays) are exact in fp32.  A non-finite pixel spoils exactly the outputs whose convolution windows hold it.  w_packed is then ONE
+ * buffer in alo_conv3x3_nhwc's convention over the same (64, 176) matrix: alo_pack_mfma_b (ALO_F16) of the high terms
+ * hi = fp16(m 2^-k_o), the same of the low terms lo = fp16(m 2^-k_o - hi), then the 64 exponents k_o as int32.  Same checks, same
+ * messages; ALO_F16 and ALO_F64 are refused for their dtype.
  */
 int alo_stem_conv_pool(const void* x, const void* w_packed, const void* bias, void* y, int N, int H, int W, long stride_n,
                        long stride_c, long stride_h, long stride_w, int dtype, void* stream);
