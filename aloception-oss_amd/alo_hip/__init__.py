@@ -1762,6 +1762,109 @@ def encoder_block(src, w1, b1, w2, b2, norm2, tail=None, nxt=None):
     return out, value, both
 
 
+# ---- the decoder layer's two row-local chains on the same entry point (ALO_BLOCK_* of include/alo_encoder_block.h) ------------------
+ALO_BLOCK_NO_FFN, ALO_BLOCK_DECODER_NEXT, ALO_BLOCK_TILE_32, ALO_BLOCK_TILE_64 = 0x100, 0x200, 0x400, 0x800   # OR-ed into the dtype
+
+
+def decoder_block_enabled():
+    """``ALO_DEC_BLOCK=off`` (read per call) keeps the decoder on its separate launches: for tests and profiling."""
+    return os.environ.get("ALO_DEC_BLOCK", "on").lower() not in ("off", "0")
+
+
+def decoder_block_supported(tgt, *operands):
+    """What :func:`decoder_block_a` / :func:`decoder_block_b` take: a bf16 CUDA (N, Lq, 256) ``tgt`` outside autograd and every
+    tensor in ``operands`` (weights, biases, LayerNorm vectors, ``query_pos``) present, bf16 and on its device."""
+    return (all(t is not None for t in operands) and fusable(tgt, *operands) and tgt.dtype == torch.bfloat16 and tgt.dim() == 3
+            and tgt.shape[-1] == 256 and tgt.numel() > 0
+            and all(t.dtype == tgt.dtype and t.device == tgt.device for t in operands))
+
+
+# The fewest rows (batch x queries) the decoder takes the fused chains at: the smallest count tools/decbench.py timed them against
+# the separate launches (docs/experiments.md); below it the layers keep their separate launches.
+DECODER_BLOCK_MIN_ROWS = 300
+
+
+def decoder_block_routed(tgt):
+    """Whether a decoder over ``tgt`` (N, Lq, 256) is sent through the fused chains: ``ALO_DEC_BLOCK`` and the measured row range."""
+    return decoder_block_enabled() and tgt.dim() == 3 and tgt.shape[0] * tgt.shape[1] >= DECODER_BLOCK_MIN_ROWS
+
+
+_CU_COUNT = {}
+
+
+def decoder_block_tile_rows(rows, device):
+    """The tile height the decoder chains run at (the rule of include/alo_encoder_block.h): 32 rows while 64-row tiles would leave
+    compute units without work, else 64."""
+    index = torch.device(device).index
+    index = torch.cuda.current_device() if index is None else index
+    if index not in _CU_COUNT:
+        _CU_COUNT[index] = torch.cuda.get_device_properties(index).multi_processor_count
+    return 32 if (rows + 63) // 64 < _CU_COUNT[index] else 64
+
+
+def _decoder_block(name, flag, attn_out, tgt, pos, tail, ffn, nxt, tile_rows):
+    """One flagged launch: ``tail = (wo, bo, g1, e1, eps1)``, ``ffn = (w1, b1, w2, b2, g2, e2, eps2) | None``,
+    ``nxt = (wv, bv) | None`` and the query projection ``(wq, bq)`` -> (out, value | None, projected query)."""
+    wo, bo, g1, e1, eps1 = tail
+    N, L, C = tgt.shape
+    dt, dev, rows = tgt.dtype, tgt.device, N * L
+    for label, t in (("attn_out", attn_out), ("pos", pos)):
+        if t.shape != tgt.shape or t.dtype != dt or t.device != dev:
+            raise RuntimeError(f"{name}: {label} must have the shape, dtype and device of tgt")
+    (wq, bq), qc = nxt[2:], (512 if ffn is not None else 384)
+    named = [("wo", wo, (256, 256)), ("wq", wq, (qc, 256))]
+    f_args, v_args, value, eps2, Fh = [None] * 6, [None, None], None, 0.0, 0
+    if ffn is not None:
+        w1, b1, w2, b2, g2, e2, eps2 = ffn
+        Fh = w1.shape[0]
+        if not ffn256_supported(tgt, w1, w2):
+            raise RuntimeError(f"{name}: needs bf16 FFN weights with a hidden width that is a multiple of 256")
+        named += [("w1", w1, (Fh, 256)), ("w2", w2, (256, Fh)), ("wv", nxt[0], (256, 256))]
+        f_args = [pack_mfma_b(w1), _vec(b1, dt), pack_mfma_b(w2), _vec(b2, dt), _vec(g2, dt), _vec(e2, dt)]
+        v_args = [pack_mfma_b(nxt[0]), _vec(nxt[1], dt)]
+        value = torch.empty((N, L, 256), dtype=dt, device=dev)
+    for label, w, shape in named:
+        if tuple(w.shape) != shape or w.dtype != dt or w.device != dev:
+            raise RuntimeError(f"{name}: {label} must be a {shape} tensor of tgt's dtype on its device")
+    if tile_rows not in (None, 32, 64):
+        raise RuntimeError(f"{name}: tile_rows must be 32, 64 or None")
+    tile_rows = tile_rows or decoder_block_tile_rows(rows, dev)
+    out = torch.empty_like(tgt, memory_format=torch.contiguous_format)
+    query = torch.empty((N, L, qc), dtype=dt, device=dev)
+    nbytes = 2.0 * rows * (256 * (4 + (ffn is not None)) + qc)   # attn_out, tgt, pos, out (+ value), the projected query
+    flops = 2.0 * rows * 256 * (256 + qc + (2 * Fh + 256) * (ffn is not None))
+    _launch("alo_encoder_block", dev, f"{name}/rows={rows}/tile={tile_rows}", nbytes, flops,
+            attn_out.contiguous(), pack_mfma_b(wo), _vec(bo, dt), _vec(g1, dt), _vec(e1, dt), tgt.contiguous(), *f_args, out,
+            pos.contiguous(), None, *v_args, pack_mfma_b(wq), _vec(bq, dt), value, query, N, L, Fh, float(eps1), float(eps2),
+            ALO_BF16 | flag | (ALO_BLOCK_TILE_32 if tile_rows == 32 else ALO_BLOCK_TILE_64))
+    return out, value, query
+
+
+def decoder_block_a(attn_out, tgt, pos, wo, bo, norm, wq, bq, tile_rows=None):
+    """Chain A of a decoder layer, between self-attention and the MSDA launch, in one kernel and bit for bit the launches it stands
+    in for: ``tgt1 = LayerNorm(linear(attn_out, wo, bo) + tgt)`` with ``norm = (weight, bias, eps)`` and
+    ``linear(tgt1 + pos, wq, bq)`` for the merged (384, 256) offsets + logits weight.  All of (N, Lq, 256) bf16.
+    ``tile_rows``: 32 or 64 instead of :func:`decoder_block_tile_rows`.  -> (tgt1, offsets_logits (N, Lq, 384))"""
+    _no_autograd("decoder_block_a", attn_out, tgt, pos, wo, bo, *norm[:2], wq, bq)
+    if not decoder_block_supported(tgt, attn_out, pos, wo, bo, norm[0], norm[1], wq, bq):
+        raise RuntimeError("decoder_block_a: needs bf16 CUDA (N, Lq, 256) tensors outside autograd and every weight, bias and pos")
+    out, _, both = _decoder_block("decoder_block_a", ALO_BLOCK_NO_FFN, attn_out, tgt, pos, (wo, bo, *norm), None,
+                                  (None, None, wq, bq), tile_rows)
+    return out, both
+
+
+def decoder_block_b(attn_out, tgt1, pos, wo, bo, norm1, w1, b1, w2, b2, norm3, wv, bv, wqk, bqk, tile_rows=None):
+    """Chain B of a decoder layer, between the MSDA launch and the NEXT layer's self-attention:
+    ``tgt2 = LayerNorm1(linear(attn_out, wo, bo) + tgt1)``, ``out = LayerNorm3(ffn256(tgt2) + tgt2)``, and the next layer's
+    ``v = linear(out, wv, bv)`` (row-major, as ``linear_auto`` writes it) and ``qk = linear(out + pos, wqk, bqk)`` with the
+    (512, 256) [q; k] rows of its ``in_proj_weight``.  -> (out, v (N, Lq, 256), qk (N, Lq, 512))"""
+    _no_autograd("decoder_block_b", attn_out, tgt1, pos, wo, bo, *norm1[:2], w1, b1, w2, b2, *norm3[:2], wv, bv, wqk, bqk)
+    if not decoder_block_supported(tgt1, attn_out, pos, wo, bo, norm1[0], norm1[1], w1, b1, w2, b2, norm3[0], norm3[1], wv, bv, wqk, bqk):
+        raise RuntimeError("decoder_block_b: needs bf16 CUDA (N, Lq, 256) tensors outside autograd and every weight, bias and pos")
+    return _decoder_block("decoder_block_b", ALO_BLOCK_DECODER_NEXT, attn_out, tgt1, pos, (wo, bo, *norm1), (w1, b1, w2, b2, *norm3),
+                          (wv, bv, wqk, bqk), tile_rows)
+
+
 def panoptic_onehot(mask_logits, frame_size, threshold=0.5):
     """(B, Q, h, w) mask logits -> (B, Q, H, W) int64 one-hot instance masks: bilinear up-sampling, sigmoid, threshold and the
     per-pixel arg-max over the queries in one pass (PanopticHead.inference).  A NaN probability selects its query (the first one

@@ -59,18 +59,29 @@ def _self_attention(mha, qk_in, v_in):
     """Inference form of ``nn.MultiheadAttention(q = k = qk_in, v = v_in)`` on batch-first (B, L, E) tensors: the packed
     input projection as two GEMMs (q and k share their input), ``scaled_dot_product_attention`` over the heads, the output
     projection — no sequence-first transposes, projections on the short-K MFMA kernel when the shape allows."""
-    B, L, E = qk_in.shape
-    H = mha.num_heads
+    (w_qk, b_qk), (w_v, b_v) = _in_proj_rows(mha)
+    qk = alo_hip.linear_auto(qk_in, w_qk, b_qk)
+    v = alo_hip.linear_auto(v_in, w_v, b_v)
+    return alo_hip.linear_auto(_attend(mha, qk, v), mha.out_proj.weight, mha.out_proj.bias)
+
+
+def _in_proj_rows(mha):
+    """((w_qk (2E, E), b_qk), (w_v (E, E), b_v)) of ``mha``'s packed input projection."""
+    E = mha.embed_dim
     w, b = mha.in_proj_weight, mha.in_proj_bias
     # the SAME row slices every call (inference only: _fused_ok): what linear_auto derives from a weight rides on the tensor object
     w_qk, w_v = alo_hip.derived(mha, "in_proj_rows", (w,), lambda: (w[: 2 * E], w[2 * E:]))
-    qk = alo_hip.linear_auto(qk_in, w_qk, None if b is None else b[: 2 * E])
-    v = alo_hip.linear_auto(v_in, w_v, None if b is None else b[2 * E:])
-    q, k = qk[..., :E], qk[..., E:]
+    return (w_qk, None if b is None else b[: 2 * E]), (w_v, None if b is None else b[2 * E:])
+
+
+def _attend(mha, qk, v):
+    """``scaled_dot_product_attention`` over ``mha``'s heads on the projected (B, L, 2E) [q; k] and (B, L, E) v -> (B, L, E),
+    before the output projection."""
+    B, L, E = v.shape
+    H = mha.num_heads
     heads = lambda t: t.reshape(B, L, H, E // H).transpose(1, 2)  # (B, H, L, E/H)
-    out = F.scaled_dot_product_attention(heads(q), heads(k), heads(v))
-    out = out.transpose(1, 2).reshape(B, L, E)
-    return alo_hip.linear_auto(out, mha.out_proj.weight, mha.out_proj.bias)
+    out = F.scaled_dot_product_attention(heads(qk[..., :E]), heads(qk[..., E:]), heads(v))
+    return out.transpose(1, 2).reshape(B, L, E)
 
 
 def _ffn(linear1, activation, linear2, x):
@@ -332,6 +343,44 @@ class DeformableTransformerDecoderLayer(nn.Module):
         tgt = self.norm1(tgt + self.dropout1(tgt2))
         return self.forward_ffn(tgt)
 
+    def block_supported(self, tgt, query_pos, src):
+        """Whether this layer's two row-local chains fit the fused kernels (alo_hip.decoder_block_a / _b): stock forward methods,
+        bf16 with d_model = 256, 8 heads, L = P = 4, ReLU, every bias, and what the separate launches of ``decoder_layer_forward``
+        and of the head-major attention path ask for."""
+        mha, attn, cls = self.self_attn, self.cross_attn, DeformableTransformerDecoderLayer
+        stock = all(getattr(type(self), name) is getattr(cls, name) for name in ("forward", "pre_process_tgt", "decoder_layer_forward"))
+        return (stock and self.activation is F.relu and mha._qkv_same_embed_dim and mha.embed_dim == 256 and mha.num_heads == 8
+                and attn.n_heads == 8 and attn.head_major_supported(tgt, src)
+                and alo_hip.ffn256_supported(tgt, self.linear1.weight, self.linear2.weight)
+                and alo_hip.decoder_block_supported(
+                    tgt, query_pos, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
+                    attn.output_proj.weight, attn.output_proj.bias, self.linear1.weight, self.linear1.bias, self.linear2.weight,
+                    self.linear2.bias, self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, self.norm3.weight,
+                    self.norm3.bias))
+
+    def forward_block(self, tgt, qk, v, query_pos, reference_points, src, src_spatial_shapes, level_start_index,
+                      src_padding_mask=None, next_layer=None):
+        """``decoder_layer_forward`` at inference with ONE launch between two attention kernels: self-attention on the ready-made
+        projections ``qk`` (B, L, 512) and ``v`` (B, L, 256), chain A (alo_hip.decoder_block_a: output projection, norm2, the
+        merged offsets + logits projection of ``tgt + query_pos``), the MSDA kernel, chain B (alo_hip.decoder_block_b: output
+        projection, norm1, the FFN, norm3 and ``next_layer``'s two input projections).  The last layer has no next projections
+        and keeps its separate launches after the MSDA kernel.  -> (out, next qk | None, next v | None)"""
+        mha, attn = self.self_attn, self.cross_attn
+        w_cat, b_cat = attn._merged_query_projection()
+        tgt, both = alo_hip.decoder_block_a(_attend(mha, qk, v), tgt, query_pos, mha.out_proj.weight, mha.out_proj.bias,
+                                            (self.norm2.weight, self.norm2.bias, self.norm2.eps), w_cat, b_cat)
+        value = alo_hip.value_proj_head_major(src, attn.value_proj.weight, attn.value_proj.bias, src_padding_mask, attn.n_heads)
+        out = attn.forward_head_major(value, both, reference_points, src_spatial_shapes, level_start_index, project=False)
+        if next_layer is None:
+            tgt = _add_norm(self.norm1, alo_hip.linear_auto(out, attn.output_proj.weight, attn.output_proj.bias), tgt)
+            return _add_norm(self.norm3, _ffn(self.linear1, self.activation, self.linear2, tgt), tgt), None, None
+        (w_qk, b_qk), (w_v, b_v) = _in_proj_rows(next_layer.self_attn)
+        out, v, qk = alo_hip.decoder_block_b(
+            out, tgt, query_pos, attn.output_proj.weight, attn.output_proj.bias, (self.norm1.weight, self.norm1.bias, self.norm1.eps),
+            self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias,
+            (self.norm3.weight, self.norm3.bias, self.norm3.eps), w_v, b_v, w_qk, b_qk)
+        return out, qk, v
+
     def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index,
                 tgt_key_padding_mask=None, src_padding_mask=None, **kwargs):
         tgt, query_pos, tgt_key_padding_mask = self.pre_process_tgt(tgt, query_pos, tgt_key_padding_mask, **kwargs)
@@ -347,6 +396,7 @@ class DeformableTransformerDecoder(nn.Module):
         self.return_intermediate = return_intermediate
         self.bbox_embed = None  # set by DeformableDETR for iterative box refinement
         self.class_embed = None
+        self.two_stage = False  # set by DeformableTransformer: two-stage queries keep the layers' separate launches
 
     def pre_process_tgt(self, tgt, query_pos, tgt_key_padding_mask, reference_points, **kwargs):
         return tgt, query_pos, tgt_key_padding_mask, reference_points
@@ -356,6 +406,17 @@ class DeformableTransformerDecoder(nn.Module):
         output = tgt
         intermediate, intermediate_refs = [], []
         ref_input = None
+        # one launch between two attention kernels (forward_block): inference in bf16 on stock layers, one-stage, queries with a dense
+        # query_pos and no padding; layer 0's two input projections with the separate kernels, every later layer gets them from
+        # the block before it.  Intermediate outputs and box refinement read ``output`` as on the separate launches.
+        block = (alo_hip.decoder_block_routed(tgt) and not self.two_stage and query_pos is not None and tgt_key_padding_mask is None
+                 and query_pos.shape == tgt.shape and query_pos.is_contiguous()
+                 and all(hasattr(layer, "forward_block") and _fused_ok(layer, kwargs, tgt, query_pos, src, reference_points, layer)
+                         and layer.block_supported(tgt, query_pos, src) for layer in self.layers))
+        qk = v = None
+        if block:
+            (w_qk, b_qk), (w_v, b_v) = _in_proj_rows(self.layers[0].self_attn)
+            qk, v = alo_hip.linear_auto(tgt + query_pos, w_qk, b_qk), alo_hip.linear_auto(tgt, w_v, b_v)
         for lid, layer in enumerate(self.layers):
             if ref_input is None or self.bbox_embed is not None:  # without box refinement the reference points never change
                 if reference_points.shape[-1] == 4:
@@ -364,9 +425,14 @@ class DeformableTransformerDecoder(nn.Module):
                 else:
                     assert reference_points.shape[-1] == 2
                     ref_input = reference_points[:, :, None] * src_valid_ratios[:, None]
-            output = layer(tgt=output, query_pos=query_pos, reference_points=ref_input, src=src,
-                           src_spatial_shapes=src_spatial_shapes, level_start_index=src_level_start_index,
-                           src_padding_mask=src_padding_mask, tgt_key_padding_mask=tgt_key_padding_mask, **kwargs)
+            if block:
+                nxt = self.layers[lid + 1] if lid + 1 < len(self.layers) else None
+                output, qk, v = layer.forward_block(output, qk, v, query_pos, ref_input, src, src_spatial_shapes,
+                                                    src_level_start_index, src_padding_mask, next_layer=nxt)
+            else:
+                output = layer(tgt=output, query_pos=query_pos, reference_points=ref_input, src=src,
+                               src_spatial_shapes=src_spatial_shapes, level_start_index=src_level_start_index,
+                               src_padding_mask=src_padding_mask, tgt_key_padding_mask=tgt_key_padding_mask, **kwargs)
             if self.bbox_embed is not None:  # iterative bounding-box refinement
                 tmp = self.bbox_embed[lid](output)
                 if reference_points.shape[-1] == 4:
@@ -419,6 +485,7 @@ class DeformableTransformer(nn.Module):
                 d_model, dim_feedforward, dropout, activation, num_feature_levels, nhead, dec_n_points)
             decoder = DeformableTransformerDecoder(decoder_layer, num_decoder_layers, return_intermediate_dec)
         self.decoder = decoder
+        self.decoder.two_stage = two_stage
         self.level_embed = nn.Parameter(torch.Tensor(num_feature_levels, d_model))
         if two_stage:   # the queries come from the encoder's proposals: no learned reference points (reference :108-114)
             self.enc_output = nn.Linear(d_model, d_model)

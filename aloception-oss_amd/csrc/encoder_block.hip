@@ -299,6 +299,382 @@ int launch_block(const EncBlockArgs& a, size_t lds, hipStream_t stream) {
     return launch<encoder_block_kernel<TAIL, PROJ>>(gx, 256, lds, stream, "alo_encoder_block", args);
 }
 
+// ---- the decoder's two row-local chains (ALO_BLOCK_NO_FFN, ALO_BLOCK_DECODER_NEXT of alo_encoder_block.h) ----------------------------
+//
+//   chain A (NEXT = false), between self-attention and the MSDA launch:
+//       tgt1 = LayerNorm1(attn_out Wo^T + bo + tgt) -> out,   offsets_logits = (tgt1 + pos) Wq^T + bq over 384 columns
+//   chain B (NEXT = true), between the MSDA launch and the next layer's self-attention:
+//       tgt2 = LayerNorm1(attn_out Wo^T + bo + tgt1),  out = LayerNorm2(ffn(tgt2) + tgt2),
+//       value = out Wv^T + bv ROW-major (rows, 256),   qk = (out + pos) Wq^T + bq over 512 columns
+//
+// The decoder forms have their OWN copy of encoder_block_kernel's loop instead of more template parameters on it: the encoder's four
+// instantiations keep their device code instruction for instruction (tools/isa_diff.py), and the decoder's shape asks for another
+// schedule.  A decoder has a few thousand rows (8 x 300): at 64 rows per workgroup 38 of 256 CUs have work, and a workgroup's time is
+// its serial walk through the weights (1 MB and more in chain B), one L2 round trip per two k-steps.  So
+//   * ROWS = 32 when the 64-row tiles would not fill the chip (the host decides): a wave then owns ONE 32-row MFMA tile of its 64
+//     columns, twice as many CUs are busy and each carries half the matrix work.  The MFMA is the same v_mfma_f32_32x32x16_bf16 with
+//     the accumulators started from the bias and k ascending, and a lane of it owns one row: a row's bits cannot depend on ROWS;
+//   * the weights are prefetched KB = 8 k-steps deep at ROWS = 32 (two register buffers of half a 256-deep contraction each, 128
+//     VGPRs) and 4 deep at ROWS = 64 (where the FFN holds 128 accumulators): one round trip per half contraction.  A whole
+//     contraction per buffer (KB = 16, 256 + 234 registers) was slower: 34.5 against 31.9 us for chain B (docs/experiments.md);
+//   * the barriers wait for LDS alone (lds_barrier): __syncthreads also waits for the global loads in flight, which here are the
+//     prefetched weights of the NEXT product; for the same reason the weights come through global, not flat, loads (dec_load_batch);
+//   * the residual and pos rows are parked in LDS with the tile itself (one exposed round trip per tile for all three) instead of
+//     being warmed and loaded after a product: at one workgroup per CU the LDS is there (4 tiles of ROWS x 528 bytes).
+// Rounding points, operand roles and summation orders are the encoder kernel's, i.e. those of alo_linear_shortk, alo_add_layernorm
+// (with pos) and alo_ffn256.
+struct DecBlockArgs {
+    const bf16_t *attn, *wo, *bo, *g1, *be1;
+    const bf16_t *res, *pos;
+    const bf16_t *w1, *b1, *w2, *b2, *g2, *be2;
+    const bf16_t *wv, *bv, *wq, *bq;
+    bf16_t *out, *value, *both;
+    long M;
+    int F, tiles;
+    float eps1, eps2;
+};
+
+// waits for this wave's LDS traffic only, then the workgroup barrier; the compiler keeps memory operations on their side of it
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <int ROWS>
+__device__ __forceinline__ void fetch_rows256(u32x4 (&v)[ROWS / 8], const bf16_t* X, long row0, long M, int tid) {
+#pragma unroll
+    for (int j = 0; j < ROWS / 8; ++j) {
+        const int p = tid + 256 * j;
+        long row = row0 + (p >> 5);
+        row = row < M ? row : M - 1;  // rows past the end are read from the last row and never stored
+        v[j] = *reinterpret_cast<const u32x4*>(X + row * 256 + (p & 31) * 8);
+    }
+}
+template <int ROWS>
+__device__ __forceinline__ void park_rows256(unsigned char* lds, const u32x4 (&v)[ROWS / 8], int tid) {
+#pragma unroll
+    for (int j = 0; j < ROWS / 8; ++j) {
+        const int p = tid + 256 * j;
+        *reinterpret_cast<u32x4*>(lds + (p >> 5) * kTileStride + (p & 31) * 16) = v[j];
+    }
+}
+
+template <int RT>
+__device__ __forceinline__ void dec_init_bias(f32x16 (&acc)[RT][2], const float* bias64, int kg) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(bias64 + 32 * t + 8 * q + 4 * kg);
+#pragma unroll
+            for (int a = 0; a < RT; ++a)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[a][t][4 * q + i] = bb[i];
+        }
+}
+
+// load_batch (mfma_tile.hpp) through a pointer in the GLOBAL address space.  Behind per_tile's opaque copy the compiler no longer knows
+// where a weight pointer points and emits flat loads; those count as LDS traffic as well, so every wait for an LDS read and every
+// lds_barrier would also wait for the prefetched weights.
+template <int KB>
+__device__ __forceinline__ void dec_load_batch(u32x4 (&buf)[2][KB], const bf16_t* frag0, size_t tile_stride, int batch) {
+    typedef const u32x4 __attribute__((address_space(1))) * global_u32x4;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < KB; ++j)
+            buf[t][j] = *(global_u32x4)(uintptr_t)(frag0 + t * tile_stride + (size_t)(KB * batch + j) * 512);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// acc[row tile][column tile] += A (the LDS tile, k-steps KB * batch ..) x the batch's weight fragments
+template <int RT, int KB>
+__device__ __forceinline__ void dec_mma_batch(f32x16 (&acc)[RT][2], const unsigned char* a_lds, const u32x4 (&buf)[2][KB], int batch,
+                                              int nl, int kg) {
+#pragma unroll
+    for (int j = 0; j < KB; ++j) {
+        const int s = KB * batch + j;
+        u32x4 af[RT];
+#pragma unroll
+        for (int a = 0; a < RT; ++a) af[a] = *reinterpret_cast<const u32x4*>(a_lds + (32 * a + nl) * kTileStride + (16 * s + 8 * kg) * 2);
+#pragma unroll
+        for (int a = 0; a < RT; ++a) {
+            acc[a][0] = mfma_32x32x16<bf16_t>(buf[0][j], af[a], acc[a][0]);
+            acc[a][1] = mfma_32x32x16<bf16_t>(buf[1][j], af[a], acc[a][1]);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// One whole 256-deep contraction (mma_tile256 with KB k-steps per batch).  bufa already holds batch 0; on return it holds batch 0 of
+// `next` when next != nullptr.
+template <int RT, int KB>
+__device__ __forceinline__ void dec_product(f32x16 (&acc)[RT][2], const unsigned char* a_lds, u32x4 (&bufa)[2][KB], u32x4 (&bufb)[2][KB],
+                                            const bf16_t* w, size_t tile_stride, const bf16_t* next, size_t next_stride, int nl, int kg) {
+    constexpr int kBatches = 16 / KB;
+    static_assert(kBatches % 2 == 0, "the two buffers take turns inside a product");
+#pragma unroll
+    for (int bt = 0; bt < kBatches; bt += 2) {
+        dec_load_batch(bufb, w, tile_stride, bt + 1);
+        dec_mma_batch<RT, KB>(acc, a_lds, bufa, bt, nl, kg);
+        if (bt + 2 < kBatches) dec_load_batch(bufa, w, tile_stride, bt + 2);
+        else if (next != nullptr) dec_load_batch(bufa, next, next_stride, 0);
+        dec_mma_batch<RT, KB>(acc, a_lds, bufb, bt + 1, nl, kg);
+    }
+}
+
+// this wave's 64 staged columns of ROWS rows -> Y[(row0 + row) * ld + col ..] as whole 128-byte lines: 8 lanes x 16 B per row
+template <int ROWS>
+__device__ __forceinline__ void store_wave_cols(bf16_t* Y, int ld, int col, const unsigned char* B, int wave, long row0, long M, int lane) {
+#pragma unroll
+    for (int k = 0; k < ROWS / 8; ++k) {
+        const int row = k * 8 + (lane >> 3);
+        const long grow = row0 + row;
+        const u32x4 v = *reinterpret_cast<const u32x4*>(B + row * kTileStride + (64 * wave) * 2 + (lane & 7) * 16);
+        if (grow < M) *reinterpret_cast<u32x4*>(Y + grow * ld + col + (lane & 7) * 8) = v;
+    }
+}
+
+template <int ROWS, bool NEXT>
+__global__ void __launch_bounds__(256)
+decoder_block_kernel(const DecBlockArgs p) {
+    constexpr int RT = ROWS / 32;            // 32-row MFMA tiles per wave
+    constexpr int KB = ROWS == 32 ? 8 : 4;   // k-steps per weight batch (16: a buffer would hold a whole product's weights)
+    constexpr int kRpw = ROWS / 4;           // rows a wave normalises
+    constexpr int kQc = NEXT ? 512 : kQueryCols;
+    constexpr int kTile = ROWS * kTileStride;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const A = smem;              // the tile every product reads
+    unsigned char* const B = smem + kTile;      // hidden chunk / every product's bf16 result
+    unsigned char* const R = smem + 2 * kTile;  // LayerNorm1's residual rows
+    unsigned char* const P = smem + 3 * kTile;  // pos rows
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nl = lane & 31, kg = lane >> 5;
+    const int F = NEXT ? p.F : 0;
+
+    float* const bos = reinterpret_cast<float*>(smem + 4 * kTile);
+    float* const g1s = bos + 256;
+    float* const e1s = g1s + 256;
+    float* const bqs = e1s + 256;
+    float* const bvs = bqs + kQc;   // NEXT only from here on
+    float* const b2s = bvs + 256;
+    float* const g2s = b2s + 256;
+    float* const e2s = g2s + 256;
+    float* const b1s = e2s + 256;
+    bos[tid] = bf16_to_f32(p.bo[tid].bits);
+    g1s[tid] = bf16_to_f32(p.g1[tid].bits);
+    e1s[tid] = bf16_to_f32(p.be1[tid].bits);
+    for (int i = tid; i < kQc; i += 256) bqs[i] = bf16_to_f32(p.bq[i].bits);
+    if constexpr (NEXT) {
+        bvs[tid] = bf16_to_f32(p.bv[tid].bits);
+        b2s[tid] = bf16_to_f32(p.b2[tid].bits);
+        g2s[tid] = bf16_to_f32(p.g2[tid].bits);
+        e2s[tid] = bf16_to_f32(p.be2[tid].bits);
+        for (int i = tid; i < F; i += 256) b1s[i] = bf16_to_f32(p.b1[i].bits);
+    }
+
+    const int fs = F / 16;
+    auto k256_frag = [&](const bf16_t* W, int col0) { return W + ((size_t)((col0 + 64 * wave) / 32) * 16 * 64 + lane) * 8; };
+    auto w2_frag = [&](int r0) { return p.w2 + (((size_t)(2 * wave) * fs + r0 / 16) * 64 + lane) * 8; };
+    constexpr size_t kStride256 = (size_t)16 * 512;
+    const int wrow = kRpw * wave;
+
+    for (int tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
+        const long row0 = (long)tile * ROWS;
+        // opaque per-tile copies (per_tile above): otherwise every weight load's address pair is computed ahead of the tile loop
+        const bf16_t* const wo_f = per_tile(k256_frag(p.wo, 0));
+        const bf16_t* const wq_f = per_tile(k256_frag(p.wq, 0));
+        u32x4 bufa[2][KB], bufb[2][KB];
+        {
+            u32x4 xa[ROWS / 8], xr[ROWS / 8], xp[ROWS / 8];
+            fetch_rows256<ROWS>(xa, p.attn, row0, p.M, tid);
+            fetch_rows256<ROWS>(xr, p.res, row0, p.M, tid);
+            fetch_rows256<ROWS>(xp, p.pos, row0, p.M, tid);
+            dec_load_batch(bufa, wo_f, kStride256, 0);
+            park_rows256<ROWS>(A, xa, tid);
+            park_rows256<ROWS>(R, xr, tid);
+            park_rows256<ROWS>(P, xp, tid);
+        }
+        lds_barrier();  // the three tiles (and, first time round, the tables) are in LDS
+
+        f32x16 acc[RT][2];
+        // ---- B = attn_out Wo^T + bo ------------------------------------------------------------------------------------------------------
+        dec_init_bias<RT>(acc, bos + 64 * wave, kg);
+        dec_product<RT, KB>(acc, A, bufa, bufb, wo_f, kStride256, NEXT ? k256_frag(p.w1, 0) : wq_f, kStride256, nl, kg);
+        stage_quads<bf16_t, false>(B, kTileStride, acc, nullptr, false, nl, 64 * wave, kg);
+        lds_barrier();  // the projected rows are in B and nobody reads A any more
+
+        // ---- A = LayerNorm1(B + R); chain A: that is `out`, and A = bf16(out + pos), the sum taken on the rounded value --------------
+        {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(g1s + 4 * lane), b = *reinterpret_cast<const f32x4*>(e1s + 4 * lane);
+#pragma unroll
+            for (int r = 0; r < kRpw; ++r) {
+                float v[4], t[4], y[4];
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(R + (wrow + r) * kTileStride + lane * 8), t);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] += t[i];
+                layernorm_row(v, g, b, p.eps1, y);
+                u32x2 o = pack4<bf16_t>(y);
+                if constexpr (!NEXT) {
+                    const long row = row0 + wrow + r;
+                    if (row < p.M) *reinterpret_cast<u32x2*>(p.out + row * 256 + 4 * lane) = o;
+                    unpack4<bf16_t>(o, y);
+                    unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(P + (wrow + r) * kTileStride + lane * 8), t);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[i] += t[i];
+                    o = pack4<bf16_t>(y);
+                }
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = o;
+            }
+        }
+        lds_barrier();  // chain A: the query is in A; chain B: the FFN's x tile
+
+        if constexpr (NEXT) {
+            // ---- feed-forward block: ffn256_kernel's arithmetic, the hidden activation 256 units at a time through B -------------------
+            const bf16_t* const wv_f = per_tile(k256_frag(p.wv, 0));
+            {
+                f32x16 acc2[RT][2];
+                zero_acc(acc2);
+                for (int r0 = 0; r0 < F; r0 += 256) {
+                    zero_acc(acc);
+                    const bf16_t* w2p = w2_frag(r0);
+                    dec_product<RT, KB>(acc, A, bufa, bufb, k256_frag(p.w1, r0), kStride256, w2p, (size_t)fs * 512, nl, kg);
+                    stage_quads<bf16_t, true>(B, kTileStride, acc, b1s + r0, true, nl, 64 * wave, kg);
+                    lds_barrier();  // the whole hidden chunk is in B
+                    const bf16_t* next = r0 + 256 < F ? k256_frag(p.w1, r0 + 256) : wv_f;
+                    dec_product<RT, KB>(acc2, B, bufa, bufb, w2p, (size_t)fs * 512, next, kStride256, nl, kg);
+                    lds_barrier();  // everyone is done reading the chunk before it is overwritten
+                }
+                stage_quads<bf16_t, true>(B, kTileStride, acc2, b2s, false, nl, 64 * wave, kg);
+            }
+            lds_barrier();
+
+            // ---- out = LayerNorm2(B + A) -> A and, in whole rows, to memory ------------------------------------------------------------
+            {
+                const f32x4 g = *reinterpret_cast<const f32x4*>(g2s + 4 * lane), b = *reinterpret_cast<const f32x4*>(e2s + 4 * lane);
+#pragma unroll
+                for (int r = 0; r < kRpw; ++r) {
+                    float v[4], t[4], y[4];
+                    unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(B + (wrow + r) * kTileStride + lane * 8), v);
+                    unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), t);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] += t[i];
+                    layernorm_row(v, g, b, p.eps2, y);
+                    const u32x2 o = pack4<bf16_t>(y);
+                    *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = o;
+                    const long row = row0 + wrow + r;
+                    if (row < p.M) *reinterpret_cast<u32x2*>(p.out + row * 256 + 4 * lane) = o;
+                }
+            }
+            lds_barrier();  // out is in A; B is free
+
+            // ---- the next layer's value, row-major: A Wv^T + bv; a wave stores the 64 columns it staged itself ------------------------
+            dec_init_bias<RT>(acc, bvs + 64 * wave, kg);
+            dec_product<RT, KB>(acc, A, bufa, bufb, wv_f, kStride256, wq_f, kStride256, nl, kg);
+            stage_quads<bf16_t, false>(B, kTileStride, acc, nullptr, false, nl, 64 * wave, kg);
+            ALO_WAVE_LDS_ORDER();
+            store_wave_cols<ROWS>(p.value, 256, 64 * wave, B, wave, row0, p.M, lane);
+            lds_barrier();  // nobody reads A any more
+            // ---- the next layer's query, in place: A = bf16(A + pos), the sum taken on the rounded out ---------------------------------
+#pragma unroll
+            for (int r = 0; r < kRpw; ++r) {
+                float y[4], t[4];
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(A + (wrow + r) * kTileStride + lane * 8), y);
+                unpack4<bf16_t>(*reinterpret_cast<const u32x2*>(P + (wrow + r) * kTileStride + lane * 8), t);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) y[i] += t[i];
+                *reinterpret_cast<u32x2*>(A + (wrow + r) * kTileStride + lane * 8) = pack4<bf16_t>(y);
+            }
+            lds_barrier();  // the query is in A
+        }
+
+        // ---- A Wq^T + bq, 64 columns per wave and pass: columns 0-255, then 256 .. kQc - 1 (chain A: 128 of them, two waves) -------------
+        const bool again = NEXT || wave < 2;  // wave-uniform; no workgroup barrier below
+        auto q_pass = [&](int pass) {
+            const int col0 = 256 * pass;
+            dec_init_bias<RT>(acc, bqs + col0 + 64 * wave, kg);
+            const bf16_t* const wq_p = wq_f + (size_t)pass * 8 * kStride256;
+            const bf16_t* next = (pass == 0 && again) ? wq_f + 8 * kStride256 : nullptr;
+            dec_product<RT, KB>(acc, A, bufa, bufb, wq_p, kStride256, next, kStride256, nl, kg);
+            ALO_WAVE_LDS_ORDER();  // the read-back of the value / of pass 0 comes first
+            stage_quads<bf16_t, false>(B, kTileStride, acc, nullptr, false, nl, 64 * wave, kg);
+            ALO_WAVE_LDS_ORDER();
+            store_wave_cols<ROWS>(p.both, kQc, col0 + 64 * wave, B, wave, row0, p.M, lane);
+        };
+        q_pass(0);
+        if (again) q_pass(1);
+        lds_barrier();  // every tile of LDS is rewritten by the next tile
+    }
+}
+
+template <int ROWS, bool NEXT>
+int launch_decoder_block(DecBlockArgs& a, int cus, hipStream_t stream) {
+    a.tiles = (int)((a.M + ROWS - 1) / ROWS);
+    const size_t lds = 4 * (size_t)ROWS * kTileStride + (NEXT ? (size_t)a.F + 256 * 7 + 512 : 256 * 3 + kQueryCols) * sizeof(float);
+    ALO_REQUIRE(lds <= (size_t)kLdsLimit, ALO_ERR_UNSUPPORTED, "alo_encoder_block: hidden width %d needs %zu bytes of LDS", a.F, lds);
+    const int gx = a.tiles < cus ? a.tiles : cus;  // persistent: one workgroup per CU (its four tiles take most of the LDS at 64 rows)
+    void* args[] = {&a};
+    return launch<decoder_block_kernel<ROWS, NEXT>>(gx, 256, lds, stream, "alo_encoder_block", args);
+}
+
+// the flagged forms of alo_encoder_block: every argument is checked here, by name, before anything is enqueued
+int decoder_block(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b, const void* src,
+                  const void* w1_packed, const void* b1, const void* w2_packed, const void* b2, const void* norm2_w, const void* norm2_b,
+                  void* src_out, const void* pos, const void* padding_mask, const void* wv_packed, const void* bv, const void* wq_packed,
+                  const void* bq, void* value_hm, void* offsets_logits, int batch, int S, int F, float eps1, float eps2, int dtype,
+                  int flags, hipStream_t stream) {
+    const char* what = "alo_encoder_block";
+    constexpr int kChains = ALO_BLOCK_NO_FFN | ALO_BLOCK_DECODER_NEXT, kTiles = ALO_BLOCK_TILE_32 | ALO_BLOCK_TILE_64;
+    ALO_REQUIRE(!(flags & ~(kChains | kTiles)), ALO_ERR_UNSUPPORTED,
+                "%s: dtype carries 0x%x above its low byte: ALO_BLOCK_NO_FFN, ALO_BLOCK_DECODER_NEXT, ALO_BLOCK_TILE_32 / _64 or nothing", what,
+                flags & ~(kChains | kTiles));
+    ALO_REQUIRE((flags & kChains) != kChains, ALO_ERR_INVALID_ARGUMENT,
+                "%s: dtype carries both ALO_BLOCK_NO_FFN and ALO_BLOCK_DECODER_NEXT: one chain per call", what);
+    ALO_REQUIRE(flags & kChains, ALO_ERR_INVALID_ARGUMENT,
+                "%s: dtype carries ALO_BLOCK_TILE_32 / _64 without ALO_BLOCK_NO_FFN or ALO_BLOCK_DECODER_NEXT", what);
+    ALO_REQUIRE((flags & kTiles) != kTiles, ALO_ERR_INVALID_ARGUMENT,
+                "%s: dtype carries both ALO_BLOCK_TILE_32 and ALO_BLOCK_TILE_64", what);
+    const bool next = (flags & ALO_BLOCK_DECODER_NEXT) != 0;
+    const char* flag = next ? "ALO_BLOCK_DECODER_NEXT" : "ALO_BLOCK_NO_FFN";
+    ALO_REQUIRE(dtype == ALO_BF16, ALO_ERR_UNSUPPORTED, "%s: %s is bf16 only (dtype %d)", what, flag, dtype);
+    const struct { const void* p; const char* name; bool wanted; } ptrs[] = {
+        {attn_out, "attn_out", true}, {wo_packed, "wo_packed", true}, {bo, "bo", true}, {norm1_w, "norm1_w", true},
+        {norm1_b, "norm1_b", true}, {src, "src", true}, {w1_packed, "w1_packed", next}, {b1, "b1", next}, {w2_packed, "w2_packed", next},
+        {b2, "b2", next}, {norm2_w, "norm2_w", next}, {norm2_b, "norm2_b", next}, {src_out, "src_out", true}, {pos, "pos", true},
+        {padding_mask, "padding_mask", false}, {wv_packed, "wv_packed", next}, {bv, "bv", next}, {wq_packed, "wq_packed", true},
+        {bq, "bq", true}, {value_hm, "value_hm", next}, {offsets_logits, "offsets_logits", true}};
+    for (const auto& a : ptrs) {
+        ALO_REQUIRE(!a.wanted || a.p, ALO_ERR_INVALID_ARGUMENT, "%s: %s is NULL, %s needs it", what, a.name, flag);
+        ALO_REQUIRE(a.wanted || !a.p, ALO_ERR_INVALID_ARGUMENT, "%s: %s must be NULL with %s", what, a.name, flag);
+    }
+    ALO_REQUIRE(batch > 0 && S > 0 && (!next || (F > 0 && F % 256 == 0)), ALO_ERR_INVALID_ARGUMENT,
+                "%s: batch, S must be positive and the hidden width a positive multiple of 256 (batch=%d S=%d F=%d)", what, batch, S, F);
+    ALO_REQUIRE(aligned16(attn_out, wo_packed, src, w1_packed, w2_packed, src_out, pos, wv_packed, wq_packed, value_hm, offsets_logits),
+                ALO_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+    const size_t rows = (size_t)batch * S, qbytes = next ? 1024 : 2 * kQueryCols;
+    const struct { const void* p; size_t bytes; bool out; } spans[] = {
+        {attn_out, rows * 512, false}, {src, rows * 512, false}, {pos, rows * 512, false},
+        {src_out, rows * 512, true}, {value_hm, rows * 512, true}, {offsets_logits, rows * qbytes, true}};
+    for (const auto& o : spans)
+        for (const auto& i : spans)
+            ALO_REQUIRE(!o.out || &o == &i || !o.p || !i.p || (const char*)o.p + o.bytes <= (const char*)i.p ||
+                            (const char*)i.p + i.bytes <= (const char*)o.p,
+                        ALO_ERR_INVALID_ARGUMENT, "%s: an output overlaps an input or another output", what);
+    DecBlockArgs a;
+    a.attn = (const bf16_t*)attn_out; a.wo = (const bf16_t*)wo_packed; a.bo = (const bf16_t*)bo;
+    a.g1 = (const bf16_t*)norm1_w; a.be1 = (const bf16_t*)norm1_b; a.res = (const bf16_t*)src; a.pos = (const bf16_t*)pos;
+    a.w1 = (const bf16_t*)w1_packed; a.b1 = (const bf16_t*)b1; a.w2 = (const bf16_t*)w2_packed; a.b2 = (const bf16_t*)b2;
+    a.g2 = (const bf16_t*)norm2_w; a.be2 = (const bf16_t*)norm2_b; a.wv = (const bf16_t*)wv_packed; a.bv = (const bf16_t*)bv;
+    a.wq = (const bf16_t*)wq_packed; a.bq = (const bf16_t*)bq;
+    a.out = (bf16_t*)src_out; a.value = (bf16_t*)value_hm; a.both = (bf16_t*)offsets_logits;
+    a.M = (long)rows; a.F = next ? F : 0; a.tiles = 0; a.eps1 = eps1; a.eps2 = eps2;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        return fail(ALO_ERR_LAUNCH, "%s: cannot read the device's compute unit count", what);
+    // few rows: 32-row tiles while the 64-row ones would leave compute units without work
+    const bool rows32 = (flags & kTiles) ? (flags & ALO_BLOCK_TILE_32) != 0 : (long)((rows + 63) / 64) < (long)cus;
+    if (next) return rows32 ? launch_decoder_block<32, true>(a, cus, stream) : launch_decoder_block<64, true>(a, cus, stream);
+    return rows32 ? launch_decoder_block<32, false>(a, cus, stream) : launch_decoder_block<64, false>(a, cus, stream);
+}
+
 }  // namespace
 }  // namespace alo
 
@@ -310,6 +686,11 @@ extern "C" int alo_encoder_block(const void* attn_out, const void* wo_packed, co
                                  const void* wv_packed, const void* bv, const void* wq_packed, const void* bq, void* value_hm,
                                  void* offsets_logits, int batch, int S, int F, float eps1, float eps2, int dtype, void* stream) {
     const char* what = "alo_encoder_block";
+    // ALO_BLOCK_* ride above the dtype's low byte (a negative dtype is no flagged one): the decoder's chains
+    if (dtype > 0 && (dtype & ~0xff))
+        return decoder_block(attn_out, wo_packed, bo, norm1_w, norm1_b, src, w1_packed, b1, w2_packed, b2, norm2_w, norm2_b, src_out, pos,
+                             padding_mask, wv_packed, bv, wq_packed, bq, value_hm, offsets_logits, batch, S, F, eps1, eps2, dtype & 0xff,
+                             dtype & ~0xff, static_cast<hipStream_t>(stream));
     ALO_REQUIRE(src && w1_packed && b1 && w2_packed && b2 && norm2_w && norm2_b && src_out, ALO_ERR_INVALID_ARGUMENT,
                 "%s: null pointer argument", what);
     const bool tail = attn_out || wo_packed || bo || norm1_w || norm1_b;

@@ -41,7 +41,31 @@ extern "C" {
  *     pos (rows, 256);  padding_mask (rows,) uint8, non-zero on padding, or NULL
  *     wv_packed (256, 256), bv (256,)  -> value_hm (batch, 8, S, 32), rows under the mask zeroed
  *     wq_packed (384, 256), bq (384,)  -> offsets_logits (rows, 384): [sampling_offsets; attention_weights] of (src' + pos)
+ *
+ * The decoder's two row-local chains: a flag OR-ed into `dtype` above its low byte (dtype = ALO_BF16 | ALO_BLOCK_...; bf16 only).
+ * A decoder layer is self-attention, chain A, the MSDA launch, chain B; with tgt the layer's input and pos its query_pos:
+ *   ALO_BLOCK_NO_FFN (chain A):  src_out = LayerNorm1(attn_out @ Wo^T + bo + src),  offsets_logits = (src_out + pos) @ Wq^T + bq
+ *     attn_out the un-projected self-attention output, src = tgt, norm1_* the decoder layer's norm2, wq_packed (384, 256), bq (384,),
+ *     offsets_logits (rows, 384).  Required: attn_out, wo_packed, bo, norm1_w, norm1_b, src, src_out, pos, wq_packed, bq,
+ *     offsets_logits.  Must be NULL: w1_packed, b1, w2_packed, b2, norm2_w, norm2_b, padding_mask, wv_packed, bv, value_hm.
+ *   ALO_BLOCK_DECODER_NEXT (chain B):  x = LayerNorm1(attn_out @ Wo^T + bo + src),  src_out = LayerNorm2(ffn(x) + x),
+ *     value_hm = src_out @ Wv^T + bv written ROW-major (rows, 256),  offsets_logits = (src_out + pos) @ Wq^T + bq over 512 columns
+ *     attn_out the un-projected MSDA output, src = chain A's src_out, norm1_* / norm2_* the decoder layer's norm1 / norm3, wv_packed
+ *     and wq_packed (512, 256) the NEXT layer's self-attention value and [q; k] input projections, offsets_logits (rows, 512).
+ *     Every pointer is required except padding_mask, which must be NULL.
+ * Both equal the alo_linear_shortk / alo_add_layernorm (with pos) / alo_ffn256 launches they stand in for bit for bit.  Rows are
+ * worked on in tiles of 64, or of 32 while ceil(rows / 64) is below the device's compute unit count (few rows: more compute units get
+ * work); a row's bits do not depend on the tile height.  ALO_BLOCK_TILE_32 / ALO_BLOCK_TILE_64 (with one of the two flags above only)
+ * fix the height instead.  Refused before anything is enqueued, the message naming the flag or the argument: a bit above the low byte
+ * that is none of these (ALO_ERR_UNSUPPORTED), both chains or both heights at once, a height without a chain, a pointer that is
+ * NULL or non-NULL against the lists above (ALO_ERR_INVALID_ARGUMENT), a flag with another dtype than ALO_BF16 (ALO_ERR_UNSUPPORTED).
+ * Without a flag the call is the encoder's, as above.
  */
+#define ALO_BLOCK_NO_FFN 0x100
+#define ALO_BLOCK_DECODER_NEXT 0x200
+#define ALO_BLOCK_TILE_32 0x400
+#define ALO_BLOCK_TILE_64 0x800
+
 int alo_encoder_block(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b,
                       const void* src, const void* w1_packed, const void* b1, const void* w2_packed, const void* b2,
                       const void* norm2_w, const void* norm2_b, void* src_out, const void* pos, const void* padding_mask,
