@@ -1693,13 +1693,34 @@ def encoder_block_enabled():
     return os.environ.get("ALO_ENC_BLOCK", "on").lower() not in ("off", "0")
 
 
+# The LDS frames of csrc/encoder_block.hip against alo::launch's limit (kLdsLimit of csrc/common.hpp; kTileStride of
+# csrc/mfma_tile.hpp: a 256-wide bf16 row plus 16 bytes).  Behind its tiles a kernel keeps b1 (one fp32 per hidden unit) and its
+# other biases and LayerNorm vectors as fp32 tables, so the widest hidden layer a form takes follows from its tiles and tables.
+BLOCK_LDS_LIMIT = 160 * 1024
+BLOCK_TILE_STRIDE = 256 * 2 + 16
+ENCODER_BLOCK_TABLES = 256 * 7 + 384          # b2, bo, bv, two LayerNorms' gamma / beta; bq over the merged 384 columns
+DECODER_BLOCK_TABLES = 256 * 7 + 512          # chain B: bo, bv, b2, two LayerNorms' gamma / beta; bqk over 512 columns
+
+
+def encoder_block_lds_bytes(hidden):
+    """Dynamic LDS of encoder_block_kernel: two 64-row tiles, b1 and the tables."""
+    return 2 * 64 * BLOCK_TILE_STRIDE + 4 * (hidden + ENCODER_BLOCK_TABLES)
+
+
+def decoder_block_lds_bytes(hidden, tile_rows):
+    """Dynamic LDS of chain B (decoder_block_kernel<tile_rows, true>): four tiles, b1 and the tables.  Chain A has no hidden layer
+    and fits at both heights."""
+    return 4 * tile_rows * BLOCK_TILE_STRIDE + 4 * (hidden + DECODER_BLOCK_TABLES)
+
+
 def encoder_block_supported(src, w1, w2, *vectors, heads=8, levels=4, points=4, value_weight=None):
     """What :func:`encoder_block` takes: a bf16 CUDA (N, S, 256) ``src`` outside autograd (:func:`fusable`), FFN weights
-    :func:`ffn256` takes, 8 heads and L = P = 4, a value projection :func:`value_proj_head_major` takes (when the next layer's
-    projections are asked for) and every bias / LayerNorm vector in ``vectors`` present."""
+    :func:`ffn256` takes with a hidden width whose LDS frame fits (:func:`encoder_block_lds_bytes`: up to 21888), 8 heads and
+    L = P = 4, a value projection :func:`value_proj_head_major` takes (when the next layer's projections are asked for) and every
+    bias / LayerNorm vector in ``vectors`` present."""
     if not (fusable(src, w1, w2, value_weight, *vectors) and src.dtype == torch.bfloat16 and src.dim() == 3 and src.shape[-1] == 256
-            and src.numel() > 0 and ffn256_supported(src, w1, w2) and heads == 8 and levels == 4 and points == 4
-            and all(v is not None for v in vectors)):
+            and src.numel() > 0 and ffn256_supported(src, w1, w2) and encoder_block_lds_bytes(w1.shape[0]) <= BLOCK_LDS_LIMIT
+            and heads == 8 and levels == 4 and points == 4 and all(v is not None for v in vectors)):
         return False
     return value_weight is None or value_proj_head_major_supported(src, value_weight, heads)
 
@@ -1719,7 +1740,7 @@ def encoder_block(src, w1, b1, w2, b2, norm2, tail=None, nxt=None):
     _no_autograd("encoder_block", src, w1, b1, w2, b2, *norm2[:2], *(tail or ())[:5], *(nxt or ()))
     if not encoder_block_supported(src, w1, w2, b1, b2, norm2[0], norm2[1]):
         raise RuntimeError("encoder_block: needs a bf16 CUDA (N, S, 256) src outside autograd, bf16 FFN weights with a hidden width "
-                           "that is a multiple of 256, and every bias")
+                           "that is a multiple of 256 and whose LDS frame fits (up to 21888), and every bias")
     N, S, C = src.shape
     dt, dev = src.dtype, src.device
     src = src.contiguous()
@@ -1771,12 +1792,14 @@ def decoder_block_enabled():
     return os.environ.get("ALO_DEC_BLOCK", "on").lower() not in ("off", "0")
 
 
-def decoder_block_supported(tgt, *operands):
+def decoder_block_supported(tgt, *operands, hidden=None):
     """What :func:`decoder_block_a` / :func:`decoder_block_b` take: a bf16 CUDA (N, Lq, 256) ``tgt`` outside autograd and every
-    tensor in ``operands`` (weights, biases, LayerNorm vectors, ``query_pos``) present, bf16 and on its device."""
+    tensor in ``operands`` (weights, biases, LayerNorm vectors, ``query_pos``) present, bf16 and on its device.  ``hidden``: chain
+    B's hidden width; its LDS frame must fit at the 32-row height (:func:`decoder_block_lds_bytes`: up to 21760)."""
     return (all(t is not None for t in operands) and fusable(tgt, *operands) and tgt.dtype == torch.bfloat16 and tgt.dim() == 3
             and tgt.shape[-1] == 256 and tgt.numel() > 0
-            and all(t.dtype == tgt.dtype and t.device == tgt.device for t in operands))
+            and all(t.dtype == tgt.dtype and t.device == tgt.device for t in operands)
+            and (hidden is None or decoder_block_lds_bytes(hidden, 32) <= BLOCK_LDS_LIMIT))
 
 
 # The fewest rows (batch x queries) the decoder takes the fused chains at: the smallest count tools/decbench.py timed them against
@@ -1792,9 +1815,11 @@ def decoder_block_routed(tgt):
 _CU_COUNT = {}
 
 
-def decoder_block_tile_rows(rows, device):
+def decoder_block_tile_rows(rows, device, hidden=0):
     """The tile height the decoder chains run at (the rule of include/alo_encoder_block.h): 32 rows while 64-row tiles would leave
-    compute units without work, else 64."""
+    compute units without work or, with chain B's ``hidden`` width, while their LDS frame does not fit; else 64."""
+    if decoder_block_lds_bytes(hidden, 64) > BLOCK_LDS_LIMIT:
+        return 32
     index = torch.device(device).index
     index = torch.cuda.current_device() if index is None else index
     if index not in _CU_COUNT:
@@ -1828,7 +1853,7 @@ def _decoder_block(name, flag, attn_out, tgt, pos, tail, ffn, nxt, tile_rows):
             raise RuntimeError(f"{name}: {label} must be a {shape} tensor of tgt's dtype on its device")
     if tile_rows not in (None, 32, 64):
         raise RuntimeError(f"{name}: tile_rows must be 32, 64 or None")
-    tile_rows = tile_rows or decoder_block_tile_rows(rows, dev)
+    tile_rows = tile_rows or decoder_block_tile_rows(rows, dev, Fh)
     out = torch.empty_like(tgt, memory_format=torch.contiguous_format)
     query = torch.empty((N, L, qc), dtype=dt, device=dev)
     nbytes = 2.0 * rows * (256 * (4 + (ffn is not None)) + qc)   # attn_out, tgt, pos, out (+ value), the projected query
@@ -1859,8 +1884,10 @@ def decoder_block_b(attn_out, tgt1, pos, wo, bo, norm1, w1, b1, w2, b2, norm3, w
     ``v = linear(out, wv, bv)`` (row-major, as ``linear_auto`` writes it) and ``qk = linear(out + pos, wqk, bqk)`` with the
     (512, 256) [q; k] rows of its ``in_proj_weight``.  -> (out, v (N, Lq, 256), qk (N, Lq, 512))"""
     _no_autograd("decoder_block_b", attn_out, tgt1, pos, wo, bo, *norm1[:2], w1, b1, w2, b2, *norm3[:2], wv, bv, wqk, bqk)
-    if not decoder_block_supported(tgt1, attn_out, pos, wo, bo, norm1[0], norm1[1], w1, b1, w2, b2, norm3[0], norm3[1], wv, bv, wqk, bqk):
-        raise RuntimeError("decoder_block_b: needs bf16 CUDA (N, Lq, 256) tensors outside autograd and every weight, bias and pos")
+    if not decoder_block_supported(tgt1, attn_out, pos, wo, bo, norm1[0], norm1[1], w1, b1, w2, b2, norm3[0], norm3[1], wv, bv, wqk, bqk,
+                                   hidden=None if w1 is None else w1.shape[0]):
+        raise RuntimeError("decoder_block_b: needs bf16 CUDA (N, Lq, 256) tensors outside autograd, every weight, bias and pos, and "
+                           "a hidden width whose LDS frame fits (up to 21760)")
     return _decoder_block("decoder_block_b", ALO_BLOCK_DECODER_NEXT, attn_out, tgt1, pos, (wo, bo, *norm1), (w1, b1, w2, b2, *norm3),
                           (wv, bv, wqk, bqk), tile_rows)
 

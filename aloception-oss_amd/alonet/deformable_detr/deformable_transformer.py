@@ -345,8 +345,8 @@ class DeformableTransformerDecoderLayer(nn.Module):
 
     def block_supported(self, tgt, query_pos, src):
         """Whether this layer's two row-local chains fit the fused kernels (alo_hip.decoder_block_a / _b): stock forward methods,
-        bf16 with d_model = 256, 8 heads, L = P = 4, ReLU, every bias, and what the separate launches of ``decoder_layer_forward``
-        and of the head-major attention path ask for."""
+        bf16 with d_model = 256, 8 heads, L = P = 4, ReLU, every bias, a hidden width whose LDS frame fits, and what the separate
+        launches of ``decoder_layer_forward`` and of the head-major attention path ask for."""
         mha, attn, cls = self.self_attn, self.cross_attn, DeformableTransformerDecoderLayer
         stock = all(getattr(type(self), name) is getattr(cls, name) for name in ("forward", "pre_process_tgt", "decoder_layer_forward"))
         return (stock and self.activation is F.relu and mha._qkv_same_embed_dim and mha.embed_dim == 256 and mha.num_heads == 8
@@ -356,7 +356,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
                     tgt, query_pos, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias,
                     attn.output_proj.weight, attn.output_proj.bias, self.linear1.weight, self.linear1.bias, self.linear2.weight,
                     self.linear2.bias, self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, self.norm3.weight,
-                    self.norm3.bias))
+                    self.norm3.bias, hidden=self.linear1.out_features))
 
     def forward_block(self, tgt, qk, v, query_pos, reference_points, src, src_spatial_shapes, level_start_index,
                       src_padding_mask=None, next_layer=None):

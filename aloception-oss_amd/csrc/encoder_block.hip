@@ -605,10 +605,15 @@ decoder_block_kernel(const DecBlockArgs p) {
     }
 }
 
+// the LDS frame of decoder_block_kernel<rows, next>: its four tiles and the fp32 tables behind them
+constexpr size_t decoder_block_lds(int rows, bool next, int F) {
+    return 4 * (size_t)rows * kTileStride + (next ? (size_t)F + 256 * 7 + 512 : 256 * 3 + kQueryCols) * sizeof(float);
+}
+
 template <int ROWS, bool NEXT>
 int launch_decoder_block(DecBlockArgs& a, int cus, hipStream_t stream) {
     a.tiles = (int)((a.M + ROWS - 1) / ROWS);
-    const size_t lds = 4 * (size_t)ROWS * kTileStride + (NEXT ? (size_t)a.F + 256 * 7 + 512 : 256 * 3 + kQueryCols) * sizeof(float);
+    const size_t lds = decoder_block_lds(ROWS, NEXT, a.F);
     ALO_REQUIRE(lds <= (size_t)kLdsLimit, ALO_ERR_UNSUPPORTED, "alo_encoder_block: hidden width %d needs %zu bytes of LDS", a.F, lds);
     const int gx = a.tiles < cus ? a.tiles : cus;  // persistent: one workgroup per CU (its four tiles take most of the LDS at 64 rows)
     void* args[] = {&a};
@@ -669,8 +674,11 @@ int decoder_block(const void* attn_out, const void* wo_packed, const void* bo, c
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
         return fail(ALO_ERR_LAUNCH, "%s: cannot read the device's compute unit count", what);
-    // few rows: 32-row tiles while the 64-row ones would leave compute units without work
-    const bool rows32 = (flags & kTiles) ? (flags & ALO_BLOCK_TILE_32) != 0 : (long)((rows + 63) / 64) < (long)cus;
+    // few rows: 32-row tiles while the 64-row ones would leave compute units without work; and whenever the 64-row frame does not
+    // fit (chain B with a hidden width above 4864), since a row's bits do not depend on the height.  A forced height is taken as it
+    // is and refused by launch_decoder_block when its frame does not fit.
+    const bool rows32 = (flags & kTiles) ? (flags & ALO_BLOCK_TILE_32) != 0
+                                         : (long)((rows + 63) / 64) < (long)cus || decoder_block_lds(64, next, a.F) > (size_t)kLdsLimit;
     if (next) return rows32 ? launch_decoder_block<32, true>(a, cus, stream) : launch_decoder_block<64, true>(a, cus, stream);
     return rows32 ? launch_decoder_block<32, false>(a, cus, stream) : launch_decoder_block<64, false>(a, cus, stream);
 }

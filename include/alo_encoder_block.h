@@ -55,11 +55,13 @@ extern "C" {
  *     Every pointer is required except padding_mask, which must be NULL.
  * Both equal the alo_linear_shortk / alo_add_layernorm (with pos) / alo_ffn256 launches they stand in for bit for bit.  Rows are
  * worked on in tiles of 64, or of 32 while ceil(rows / 64) is below the device's compute unit count (few rows: more compute units get
- * work); a row's bits do not depend on the tile height.  ALO_BLOCK_TILE_32 / ALO_BLOCK_TILE_64 (with one of the two flags above only)
- * fix the height instead.  Refused before anything is enqueued, the message naming the flag or the argument: a bit above the low byte
- * that is none of these (ALO_ERR_UNSUPPORTED), both chains or both heights at once, a height without a chain, a pointer that is
- * NULL or non-NULL against the lists above (ALO_ERR_INVALID_ARGUMENT), a flag with another dtype than ALO_BF16 (ALO_ERR_UNSUPPORTED).
- * Without a flag the call is the encoder's, as above.
+ * work) or while the 64-row LDS frame does not fit (chain B with F > 4864; the 32-row frame fits up to F = 21760); a row's bits do
+ * not depend on the tile height.  ALO_BLOCK_TILE_32 / ALO_BLOCK_TILE_64 (with one of the two flags above only) fix the height
+ * instead; a fixed height whose frame does not fit is ALO_ERR_UNSUPPORTED.  Refused before anything is enqueued, the message
+ * naming the flag or the argument: a bit above the low byte that is none of these (ALO_ERR_UNSUPPORTED), both chains or both
+ * heights at once, a height without a chain, a pointer that is NULL or non-NULL against the lists above
+ * (ALO_ERR_INVALID_ARGUMENT), a flag with another dtype than ALO_BF16 (ALO_ERR_UNSUPPORTED).  Without a flag the call is the
+ * encoder's, as above.
  */
 #define ALO_BLOCK_NO_FFN 0x100
 #define ALO_BLOCK_DECODER_NEXT 0x200

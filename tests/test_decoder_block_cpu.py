@@ -145,3 +145,47 @@ def test_the_route_is_switched_per_call(monkeypatch):
         assert not alo_hip.decoder_block_enabled()
     monkeypatch.setenv("ALO_DEC_BLOCK", "on")
     assert alo_hip.decoder_block_enabled()
+
+
+# ---- the hidden widths the gates admit are the ones whose LDS frame fits ------------------------------------------------------------
+def _csrc_int(header, name):
+    """``constexpr int <name> = <arithmetic>;`` of a csrc header, evaluated."""
+    import re
+
+    text = open(f"{alo_hip.CSRC_DIR}/{header}").read()
+    return eval(re.search(rf"constexpr int {name} = ([0-9 *+]+);", text).group(1))
+
+
+def test_the_lds_formulas_use_the_kernels_constants():
+    assert alo_hip.BLOCK_LDS_LIMIT == _csrc_int("common.hpp", "kLdsLimit") == 160 * 1024
+    assert alo_hip.BLOCK_TILE_STRIDE == _csrc_int("mfma_tile.hpp", "kTileStride") == 528
+    # the tables as the kernels lay them out: encoder b2, bo, bv, g1, e1, g2, e2 + 384 of bq; chain B bo, g1, e1, bv, b2, g2, e2 + 512 of bqk
+    assert alo_hip.ENCODER_BLOCK_TABLES == 7 * 256 + 384 and alo_hip.DECODER_BLOCK_TABLES == 7 * 256 + 512
+    assert alo_hip.encoder_block_lds_bytes(1024) == 2 * 64 * 528 + 4 * (1024 + 2176)
+    assert alo_hip.decoder_block_lds_bytes(1024, 32) == 4 * 32 * 528 + 4 * (1024 + 2304)
+    assert alo_hip.decoder_block_lds_bytes(1024, 64) == 4 * 64 * 528 + 4 * (1024 + 2304)
+
+
+FRAMES = {   # the widest hidden layer each frame takes, the next width the issue of the gates names, and the frame's bytes
+    "decoder64": (4864, 5120, lambda F: alo_hip.decoder_block_lds_bytes(F, 64)),     # chain B at 64 rows
+    "decoder32": (21760, 22016, lambda F: alo_hip.decoder_block_lds_bytes(F, 32)),   # chain B at 32 rows: the widest the route takes
+    "encoder": (21888, 22144, lambda F: alo_hip.encoder_block_lds_bytes(F)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FRAMES))
+def test_each_frame_fits_up_to_its_boundary_and_not_beyond(name):
+    fits, over, frame = FRAMES[name]
+    assert frame(fits) == alo_hip.BLOCK_LDS_LIMIT          # the boundary is exact: one more hidden unit does not fit
+    assert frame(fits + 1) > alo_hip.BLOCK_LDS_LIMIT and frame(over) > alo_hip.BLOCK_LDS_LIMIT
+    assert frame(fits - 256) < alo_hip.BLOCK_LDS_LIMIT
+
+
+def test_the_predicted_tile_height_follows_the_frame(monkeypatch):
+    monkeypatch.setitem(alo_hip._CU_COUNT, 0, 256)         # no device is asked
+    few, many = 2400, 64 * 256 + 37
+    for hidden, at_many in ((0, 64), (256, 64), (1024, 64), (4864, 64), (5120, 32), (21760, 32)):
+        assert alo_hip.decoder_block_tile_rows(few, "cuda:0", hidden) == 32, hidden
+        assert alo_hip.decoder_block_tile_rows(many, "cuda:0", hidden) == at_many, hidden
+    # without a width the rule is the one existing callers know: 64 rows from ceil(rows / 64) = compute units on
+    assert alo_hip.decoder_block_tile_rows(64 * 255, "cuda:0") == 32 and alo_hip.decoder_block_tile_rows(64 * 255 + 1, "cuda:0") == 64
