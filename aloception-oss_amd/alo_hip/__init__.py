@@ -1262,28 +1262,59 @@ def ffn_f32(x, w1, b1, w2, b2):
     return y.view(x.shape)
 
 
+ALO_CONV_DILATION_2 = 0x800   # include/alo_hotpath.h: OR-ed into alo_conv3x3_nhwc's stride (stride 1, dilation 2, padding 2)
+_CONV3X3_GEOMETRIES = (((1, 1), (1, 1), (1, 1)), ((2, 2), (1, 1), (1, 1)), ((1, 1), (2, 2), (2, 2)))   # (stride, padding, dilation)
+
+
 def _conv3x3_gate(dtype, x, weight, stride, padding, dilation, groups):
-    """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last CUDA activation of ``dtype``, Cin % 64 == 0, Cout % 64 == 0."""
+    """3x3 convolution — padding 1 at stride 1 or 2, or dilation 2 with padding 2 at stride 1 — of a channels-last CUDA activation of
+    ``dtype``, Cin % 64 == 0, Cout % 64 == 0."""
     return (x.is_cuda and x.dtype == dtype and weight.dtype == dtype and x.dim() == 4 and weight.dim() == 4
-            and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) in ((1, 1), (2, 2)) and tuple(padding) == (1, 1)
-            and tuple(dilation) == (1, 1) and groups == 1 and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0
+            and tuple(weight.shape[2:]) == (3, 3) and (tuple(stride), tuple(padding), tuple(dilation)) in _CONV3X3_GEOMETRIES
+            and groups == 1 and weight.shape[1] == x.shape[1] and x.shape[1] % 64 == 0
             and weight.shape[0] % 64 == 0 and x.is_contiguous(memory_format=torch.channels_last)
             and not torch.is_grad_enabled())
 
 
 def conv3x3_supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
-    """3x3 / padding 1 / stride 1 or 2 convolution of a channels-last bf16 CUDA activation, Cin % 64 == 0, Cout % 64 == 0."""
+    """3x3 / padding 1 / stride 1 or 2 convolution, or 3x3 / dilation 2 / padding 2 / stride 1, of a channels-last bf16 CUDA
+    activation, Cin % 64 == 0, Cout % 64 == 0."""
     return _conv3x3_gate(torch.bfloat16, x, weight, stride, padding, dilation, groups)
 
 
-def conv3x3(x, weight, bias=None, relu=False, stride=1):
-    """``act(F.conv2d(x, weight, bias, stride, 1))`` for a channels-last bf16 ``x`` (N, Cin, H, W): implicit GEMM on MFMA with
-    the bias and the ReLU in its epilogue.  Returns a channels-last (N, Cout, Ho, Wo) tensor."""
-    _no_autograd("conv3x3", x, weight, bias)
+# Whether a model's dilated 3x3 (layer4.1 / layer4.2 conv2 of a DC5 backbone) takes the kernel instead of MIOpen + bias_act_: set by
+# the measurement at 8 x 512 x 50 x 84 and 1 x 512 x 50 x 84 (tools/convbench.py --dilated, tools/convbench_f32.py --only dilated;
+# docs/experiments.md, "Dilated 3x3"): 0.53 and 0.49 of the stock route in bf16 (198 against 374 us, 48 against 97), 0.54 and 0.45 in fp32
+# (752 against 1381 us, 224 against 495), every difference above the larger spread.  The wrappers serve the dilated call either way.
+CONV3X3_DILATED_ROUTED = True
+CONV3X3_F32_DILATED_ROUTED = True
+
+
+def conv3x3_dilated_routed(dtype=torch.bfloat16):
+    """Whether ``conv_bn`` sends a dilated 3x3 of ``dtype`` to :func:`conv3x3` / :func:`conv3x3_f32`: measured to win, and
+    ``ALO_CONV3X3_DILATED=off`` (read per call: A/B runs and tests) not set."""
+    routed = CONV3X3_F32_DILATED_ROUTED if dtype == torch.float32 else CONV3X3_DILATED_ROUTED
+    return routed and os.environ.get("ALO_CONV3X3_DILATED", "on").lower() not in ("off", "0")
+
+
+def _conv3x3_geometry(stride, dilation):
+    """(stride, dilation) as ints, the ``stride`` argument of alo_conv3x3_nhwc and the tag's suffix for them."""
     stride = stride[0] if isinstance(stride, (tuple, list)) else stride
-    if not conv3x3_supported(x, weight, (stride, stride)):
+    dilation = dilation[0] if isinstance(dilation, (tuple, list)) else dilation
+    if dilation == 1:
+        return stride, dilation, stride, f"s={stride}"
+    return stride, dilation, stride | ALO_CONV_DILATION_2, f"s={stride}/d={dilation}"
+
+
+def conv3x3(x, weight, bias=None, relu=False, stride=1, dilation=1):
+    """``act(F.conv2d(x, weight, bias, stride, dilation, dilation))`` for a channels-last bf16 ``x`` (N, Cin, H, W): implicit GEMM on
+    MFMA with the bias and the ReLU in its epilogue; ``dilation`` 2 (padding 2) at stride 1 only.  Returns a channels-last
+    (N, Cout, Ho, Wo) tensor."""
+    _no_autograd("conv3x3", x, weight, bias)
+    stride, dilation, flagged, suffix = _conv3x3_geometry(stride, dilation)
+    if not conv3x3_supported(x, weight, (stride, stride), (dilation, dilation), (dilation, dilation)):
         raise RuntimeError("conv3x3: needs a channels-last bf16 CUDA activation, a (Cout, Cin, 3, 3) weight, Cin % 64 == 0, "
-                           "Cout % 64 == 0, stride 1 or 2, no autograd")
+                           "Cout % 64 == 0, stride 1 or 2 (dilation 2: stride 1), no autograd")
     n, cin, h, w_ = x.shape
     cout = weight.shape[0]
     # (Cout, ky, kx, Cin) row-major = the channels-last memory of the weight; pack it as a (Cout, 9 Cin) matrix
@@ -1292,10 +1323,10 @@ def conv3x3(x, weight, bias=None, relu=False, stride=1):
     ho, wo = (h - 1) // stride + 1, (w_ - 1) // stride + 1
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.contiguous()
-    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, stride)   # split-K partial sums (few-tile shapes only)
+    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, flagged)   # split-K partial sums (few-tile shapes only)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
-    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3/C={cin}/s={stride}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
-            x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_BF16)
+    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3/C={cin}/{suffix}", 2.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
+            x, packed, bias_c, y, ws, n, h, w_, cin, cout, flagged, 1 if relu else 0, ALO_BF16)
     return y
 
 
@@ -1328,15 +1359,16 @@ def _split_weight(weight):
                       k.view(torch.uint8).flatten()])
 
 
-def conv3x3_f32(x, weight, bias=None, relu=False, stride=1):
-    """``act(F.conv2d(x, weight, bias, stride, 1))`` for a channels-last fp32 ``x`` (N, Cin, H, W) and an fp32 weight, on the fp16
-    matrix cores at fp32-class accuracy (csrc/conv_f32.hip: two-term split of both operands, a power of two per image and per
-    output channel, fp32 accumulation).  Returns a channels-last fp32 (N, Cout, Ho, Wo) tensor."""
+def conv3x3_f32(x, weight, bias=None, relu=False, stride=1, dilation=1):
+    """``act(F.conv2d(x, weight, bias, stride, dilation, dilation))`` for a channels-last fp32 ``x`` (N, Cin, H, W) and an fp32 weight,
+    on the fp16 matrix cores at fp32-class accuracy (csrc/conv_f32.hip: two-term split of both operands, a power of two per image and
+    per output channel, fp32 accumulation); ``dilation`` 2 (padding 2) at stride 1 only.  Returns a channels-last fp32
+    (N, Cout, Ho, Wo) tensor."""
     _no_autograd("conv3x3_f32", x, weight, bias)
-    stride = stride[0] if isinstance(stride, (tuple, list)) else stride
-    if not conv3x3_f32_supported(x, weight, (stride, stride)):
+    stride, dilation, flagged, suffix = _conv3x3_geometry(stride, dilation)
+    if not conv3x3_f32_supported(x, weight, (stride, stride), (dilation, dilation), (dilation, dilation)):
         raise RuntimeError("conv3x3_f32: needs a channels-last fp32 CUDA activation, an fp32 (Cout, Cin, 3, 3) weight, Cin % 64 == 0, "
-                           "Cout % 64 == 0, stride 1 or 2, no autograd")
+                           "Cout % 64 == 0, stride 1 or 2 (dilation 2: stride 1), no autograd")
     n, cin, h, w_ = x.shape
     cout = weight.shape[0]
     packed = derived(weight, "conv3x3_f32_b", (weight,), lambda: _split_weight(weight))
@@ -1344,10 +1376,10 @@ def conv3x3_f32(x, weight, bias=None, relu=False, stride=1):
     y = torch.empty((n, cout, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     bias_c = None if bias is None else bias.float().contiguous()
     # the split-K bytes of the bf16 call (unused by this kernel) + the per-image magnitudes, rounded up to 256 bytes
-    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, stride) + (4 * n + 255) // 256 * 256
+    ws_bytes = lib().alo_conv3x3_workspace_bytes(n, h, w_, cin, cout, flagged) + (4 * n + 255) // 256 * 256
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device)
-    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3_f32/C={cin}/s={stride}", 4.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
-            x, packed, bias_c, y, ws, n, h, w_, cin, cout, stride, 1 if relu else 0, ALO_F32)
+    _launch("alo_conv3x3_nhwc", x.device, f"conv3x3_f32/C={cin}/{suffix}", 4.0 * (x.numel() + y.numel()), 2.0 * 9 * cin * y.numel(),
+            x, packed, bias_c, y, ws, n, h, w_, cin, cout, flagged, 1 if relu else 0, ALO_F32)
     return y
 
 

@@ -79,6 +79,13 @@ def folded_conv_bn(conv, bn):
     return alo_hip.derived(conv, "folded", (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), fold)
 
 
+def dilation_of(conv):
+    """The ``dilation`` keyword a 3x3 wrapper (``alo_hip.conv3x3``, ``alo_hip.conv3x3_f32``) must get for ``conv`` once the gate has said
+    yes to the layer's own dilation.  Named only for a dilated layer: an undilated call is the five-argument call it always was, also
+    for a function that stands in for the wrapper."""
+    return {} if tuple(conv.dilation) == (1, 1) else {"dilation": conv.dilation}
+
+
 def conv_bn(x, conv, bn, relu=False, residual=None):
     """``act(bn(conv(x)) [+ residual])`` with the frozen batch-norm folded into the convolution's weight and bias.
 
@@ -105,15 +112,19 @@ def conv_bn(x, conv, bn, relu=False, residual=None):
                     return conv1x1_as_gemm(x, w, b, conv.stride, relu=relu, residual=residual)
                 out = conv1x1_as_gemm(x, w, None, conv.stride)
                 return alo_hip.bias_act_(out, b, residual, relu)
-            if residual is None and alo_hip.conv3x3_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
+            # a dilated 3x3 (DC5: layer4.1 / layer4.2 conv2) goes to the kernels where that was measured to win, and ALO_CONV3X3_DILATED=off
+            # keeps it on MIOpen + bias_act_
+            dilated_ok = conv.dilation == (1, 1) or alo_hip.conv3x3_dilated_routed(x.dtype)
+            if (residual is None and dilated_ok
+                    and alo_hip.conv3x3_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups)):
                 # the bottleneck's 3x3: implicit GEMM on MFMA, bias + ReLU in its epilogue (2-3.5x MIOpen at these shapes)
-                return alo_hip.conv3x3(x, w, b, relu, conv.stride)
-            if (residual is None and alo_hip.f32_layers_split() and not (conv.stride == (2, 2) and w.shape[1] == 256)
+                return alo_hip.conv3x3(x, w, b, relu, conv.stride, **dilation_of(conv))
+            if (residual is None and dilated_ok and alo_hip.f32_layers_split() and not (conv.stride == (2, 2) and w.shape[1] == 256)
                     and alo_hip.conv3x3_f32_supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups)):
                 # ALO_F32_LAYERS=split: the fp32 bottleneck's 3x3 on the fp16 matrix cores, bias + ReLU in its epilogue: 0.27-0.79 of
                 # MIOpen + bias_act_ at six of the seven shapes of the fp32 headline (tools/gemmbench_f32.py; docs/experiments.md,
                 # "`linear_f32`").  Off the route: layer3.0.conv2, 256 channels at stride 2 on 100 x 167, 462 us against 416 (1.11)
-                return alo_hip.conv3x3_f32(x, w, b, relu, conv.stride)
+                return alo_hip.conv3x3_f32(x, w, b, relu, conv.stride, **dilation_of(conv))
             if relu or residual is not None:
                 # bias (+ identity) + ReLU are ONE in-place pass over the convolution output instead of MIOpen's separate
                 # bias kernel followed by add / relu kernels

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 from torch import nn
 
 import alo_hip
-from alonet.detr.backbone import conv1x1_as_gemm
+from alonet.detr.backbone import conv1x1_as_gemm, dilation_of
 
 
 def _expand(tensor, length):
@@ -125,5 +125,5 @@ class FPNstyleCNN(nn.Module):
             return alo_hip.conv3x3_small(x, lay)
         if (fast and lay.kernel_size == (3, 3) and lay.groups == 1 and lay.padding_mode == "zeros"
                 and alo_hip.conv3x3_supported(x, lay.weight, lay.stride, lay.padding, lay.dilation)):
-            return alo_hip.conv3x3(x, lay.weight, lay.bias, False, lay.stride)
+            return alo_hip.conv3x3(x, lay.weight, lay.bias, False, lay.stride, **dilation_of(lay))
         return lay(x)

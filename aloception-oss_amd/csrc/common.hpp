@@ -113,7 +113,7 @@ int conv1x1_chain(const void* mid, const void* w_chain, const void* res_or_x0, v
 
 // conv_f32.hip: the fp32 flavour of alo_conv3x3_nhwc on checked arguments (w_split and image_mag: alo_hotpath.h); image_mag holds N words.
 int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,
-                int stride, int relu, hipStream_t stream);
+                int stride, int dilation, int relu, hipStream_t stream);   // dilation 2 (ALO_CONV_DILATION_2): stride 1, padding 2
 // the five-tap flavours behind ALO_CONV_TAPS_1X5 (vertical = 0) / ALO_CONV_TAPS_5X1 (vertical = 1): stride 1, w_split of the (Cout, 5 Cin) matrix
 int conv_taps_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,
                   int vertical, int relu, hipStream_t stream);

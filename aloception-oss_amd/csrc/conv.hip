@@ -16,6 +16,8 @@
 //   * Cout == 64 (ResNet layer1) would leave the second wave without columns: there the two waves split K instead (each takes
 //     every other weight batch) and the partial sums meet in LDS.
 //     Cin == Cout == 64 at stride 1 goes to conv3x3_c64_kernel, the same split on four waves with the weights kept in registers.
+//   * ALO_CONV_DILATION_2 in `stride` (dilation 2, padding 2, stride 1: layer4 of a DC5 backbone) goes to conv3x3_d2_kernel, the
+//     stride-1 loop over runs of 68 pixels two rows apart with the taps two slots apart.
 #include <cstdlib>
 #include <cstring>
 
@@ -417,6 +419,215 @@ conv3x3_c64_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, 
     }
 }
 
+// ---- dilation 2, padding 2, stride 1 (layer4.1 / layer4.2 conv2 of a DC5 backbone): the nine taps sit two pixels apart ----------------
+// conv3x3_kernel<1, KSPLIT>'s loop over another halo: three runs of kPix + 4 consecutive input pixels (rows y - 2, y, y + 2; flattened
+// index p - 2 .. p + 65), tap (dy, dx) of tile pixel m reads slot kRun dy + 2 dx + m, and the tap mask is built from y + 2 (dy - 1),
+// x + 2 (dx - 1).  The weights, their order, the K split, split-K and the epilogue are that kernel's.  It is a kernel of its own: as a
+// third template argument of conv3x3_kernel the geometry would rename the existing instantiations, and <1, false> sits at 256 registers.
+struct GeoD2 {
+    static constexpr int kChunk = Geo<1>::kChunk;
+    static constexpr int kBpt = kChunk / 32;                 // weight batches (two k-steps each) per tap and chunk
+    static constexpr int kRun = kPix + 4;                    // staged pixels per tap row
+    static constexpr int kSlots = 3 * kRun;
+    static constexpr int kPixStride = Geo<1>::kPixStride;
+    static constexpr int kPieces = kSlots * (kChunk / 8);    // 16-byte pieces per chunk
+    static constexpr int kIters = (kPieces + kThreads - 1) / kThreads;
+    static constexpr int kLds = kSlots * kPixStride;
+    static_assert(kLds >= kRedOffset + 64 * 64 * 4, "the epilogue's staging aliases the halo");
+    static_assert(kIters == Geo<1>::kIters, "as many halo registers in flight as conv3x3_kernel<1>");
+};
+
+// flattened input pixel (clamped into the image) behind staging slot `slot` of the tile whose first output pixel is p0
+__device__ __forceinline__ int slot_pixel_d2(int slot, int p0, const ConvDims& dm) {
+    const int run = slot / GeoD2::kRun, pix = slot - run * GeoD2::kRun;
+    const int q = p0 + (run - 1) * 2 * dm.W - 2 + pix;
+    const int last = dm.H * dm.W - 1;
+    return q < 0 ? 0 : (q > last ? last : q);
+}
+
+template <bool KSPLIT>
+__global__ void __launch_bounds__(kThreads, 2)
+conv3x3_d2_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, const bf16_t* __restrict__ bias,
+                  bf16_t* __restrict__ Y, float* __restrict__ partial, const ConvDims dm) {
+    using G = GeoD2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const halo = smem;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nl = lane & 31, kg = lane >> 5;
+    const int HW = dm.H * dm.W;
+    const int col0 = KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128 + wave * 64;  // this wave's 64 output channels
+    const bool has_cols = col0 < dm.Cout;                               // Cout % 64 == 0
+    float* const bias_s = reinterpret_cast<float*>(smem + G::kLds);     // the workgroup's 128 (K-split: 64) bias values, fp32
+    {
+        const int c = (KSPLIT ? blockIdx.y * 64 : blockIdx.y * 128) + tid;
+        bias_s[tid] = (bias != nullptr && c < dm.Cout && (!KSPLIT || tid < 64)) ? bf16_to_f32(bias[c].bits) : 0.f;
+    }
+
+    // persistent workgroups, one contiguous eighth of the tiles per XCD (see conv3x3_kernel)
+    const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
+    const int tile_end = range.end, lanes_per_xcd = range.step;
+    int tile = range.first;
+    if (tile >= tile_end) return;
+
+    const int ksteps_per_tap = dm.Cin / 16;
+    const size_t ctile_stride = (size_t)9 * ksteps_per_tap * 512;      // elements between the packed column tiles
+    const bf16_t* wfrag = Wp + (size_t)(col0 / 32) * ctile_stride + lane * 8;
+
+    // this wave's weight batches of a chunk: all 9 kBpt of them, or every other one when the two waves split K
+    constexpr int kBatches = 9 * G::kBpt;
+    const int my_batches = KSPLIT ? (kBatches - wave + 1) / 2 : kBatches;
+    auto batch = [&](int i) { return KSPLIT ? wave + 2 * i : i; };
+
+    // halo pieces travel through registers and are requested one (tile, chunk) AHEAD of their use
+    u32x4 stage[G::kIters];
+    auto load_halo = [&](int tl, int c0) {
+        const int im = tl / dm.tiles_per_image, first = (tl - im * dm.tiles_per_image) * kPix;
+        const bf16_t* ximg = X + (size_t)im * HW * dm.Cin + c0;
+#pragma unroll
+        for (int it = 0; it < G::kIters; ++it) {
+            const int i = tid + it * kThreads;
+            const int piece = i % (G::kChunk / 8), slot = i / (G::kChunk / 8);
+            if (i < G::kPieces)
+                stage[it] = *reinterpret_cast<const u32x4*>(ximg + (size_t)slot_pixel_d2(slot, first, dm) * dm.Cin + piece * 8);
+        }
+    };
+    const int cbeg = blockIdx.z * dm.cin_per_z, cend = cbeg + dm.cin_per_z;
+    load_halo(tile, cbeg);
+
+    for (; tile < tile_end; tile += lanes_per_xcd) {
+        const int img = tile / dm.tiles_per_image;
+        const int p0 = (tile - img * dm.tiles_per_image) * kPix;       // first output pixel of the tile inside the image
+
+        // which of the 9 taps exist for this lane's two pixels (row tiles a = 0, 1: output pixel p0 + 32 a + nl)
+        unsigned tapmask[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int q = p0 + 32 * a + nl;
+            const int y = q / dm.W, x = q - y * dm.W;
+            unsigned m = 0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = y + 2 * (t / 3 - 1), xx = x + 2 * (t % 3 - 1);
+                if (q < HW && yy >= 0 && yy < dm.H && xx >= 0 && xx < dm.W) m |= 1u << t;
+            }
+            tapmask[a] = m;
+        }
+
+        f32x16 acc[2][2];  // [row tile][column tile]
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+
+        for (int c0 = cbeg; c0 < cend; c0 += G::kChunk) {
+            // weights of batch kb of this chunk: tap kb / kBpt, k-steps 2 (kb % kBpt) and + 1 of the chunk
+            auto load_w = [&](WFrag& f, int kb) {
+                const bf16_t* p = wfrag + (size_t)((kb / G::kBpt) * ksteps_per_tap + c0 / 16 + 2 * (kb % G::kBpt)) * 512;
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+                        f.v[j][b] = *reinterpret_cast<const u32x4*>(p + (size_t)j * 512 + b * ctile_stride);
+            };
+            auto compute = [&](const WFrag& f, int kb) {
+                const int t = kb / G::kBpt, dy = t / 3, dx = t - 3 * dy;
+                const int slot = dy * G::kRun + 2 * dx;
+                const bool ok0 = (tapmask[0] >> t) & 1u, ok1 = (tapmask[1] >> t) & 1u;
+                const unsigned char* a_base = halo + (slot + nl) * G::kPixStride + kg * 16 + (kb % G::kBpt) * 64;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    u32x4 a0 = *reinterpret_cast<const u32x4*>(a_base + j * 32);
+                    u32x4 a1 = *reinterpret_cast<const u32x4*>(a_base + 32 * G::kPixStride + j * 32);
+                    if (!ok0) a0 = u32x4{0u, 0u, 0u, 0u};
+                    if (!ok1) a1 = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        acc[0][b] = mfma_32x32x16<bf16_t>(f.v[j][b], a0, acc[0][b]);
+                        acc[1][b] = mfma_32x32x16<bf16_t>(f.v[j][b], a1, acc[1][b]);
+                    }
+                }
+            };
+            WFrag w0, w1;
+            if (has_cols) load_w(w0, batch(0));
+
+#pragma unroll
+            for (int it = 0; it < G::kIters; ++it) {
+                const int i = tid + it * kThreads;
+                const int piece = i % (G::kChunk / 8), slot = i / (G::kChunk / 8);
+                if (i < G::kPieces) *reinterpret_cast<u32x4*>(halo + slot * G::kPixStride + piece * 16) = stage[it];
+            }
+            __syncthreads();
+            if (c0 + G::kChunk < cend) load_halo(tile, c0 + G::kChunk);
+            else if (tile + lanes_per_xcd < tile_end) load_halo(tile + lanes_per_xcd, cbeg);
+
+            if (has_cols) {
+#pragma unroll 1
+                for (int i = 0; i < my_batches; i += 2) {
+                    if (i + 1 < my_batches) load_w(w1, batch(i + 1));
+                    compute(w0, batch(i));
+                    if (i + 2 < my_batches) load_w(w0, batch(i + 2));
+                    if (i + 1 < my_batches) compute(w1, batch(i + 1));
+                }
+            }
+            __syncthreads();  // the halo is overwritten by the next channel chunk (and by the epilogue's staging)
+        }
+
+        if (KSPLIT) {  // wave 1 hands its partial sums to wave 0
+            float* red = reinterpret_cast<float*>(smem + kRedOffset);
+            ALO_KSPLIT_HANDOFF(acc, red, wave, lane);
+        }
+
+        if (!KSPLIT && dm.zsplit > 1) {
+            // split-K: raw fp32 partial sums to partial[z][pixel][channel] for conv_splitk_finalize_kernel (see conv3x3_kernel)
+            if (has_cols) {
+                float* pz = partial + ((size_t)blockIdx.z * dm.N + img) * HW * dm.Cout + col0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    const int q = p0 + 32 * a + nl;
+                    if (q < HW) {
+#pragma unroll
+                        for (int b = 0; b < 2; ++b)
+#pragma unroll
+                            for (int qd = 0; qd < 4; ++qd)
+                                *reinterpret_cast<f32x4*>(pz + (size_t)q * dm.Cout + 32 * b + 8 * qd + 4 * kg) =
+                                    f32x4{acc[a][b][4 * qd], acc[a][b][4 * qd + 1], acc[a][b][4 * qd + 2], acc[a][b][4 * qd + 3]};
+                    }
+                }
+            }
+        } else if (has_cols && !(KSPLIT && wave == 1)) {
+            unsigned char* const obuf = smem + (KSPLIT ? 0 : wave) * (kPix * kOutStride);
+            // lane = output pixel 32 a + nl, registers 4 q .. 4 q + 3 = channels col0 + 32 b + 8 q + 4 kg .. + 3 (see conv3x3_kernel)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = 32 * b + 8 * q + 4 * kg;
+                    const f32x4 bb = *reinterpret_cast<const f32x4*>(bias_s + (KSPLIT ? 0 : wave) * 64 + c);
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) {
+                        float v0 = acc[a][b][4 * q] + bb[0], v1 = acc[a][b][4 * q + 1] + bb[1];
+                        float v2 = acc[a][b][4 * q + 2] + bb[2], v3 = acc[a][b][4 * q + 3] + bb[3];
+                        if (dm.relu) { v0 = relu_keep_nan(v0); v1 = relu_keep_nan(v1); v2 = relu_keep_nan(v2); v3 = relu_keep_nan(v3); }
+                        *reinterpret_cast<u32x2*>(obuf + (32 * a + nl) * kOutStride + c * 2) = u32x2{pack_bf16x2(v0, v1), pack_bf16x2(v2, v3)};
+                    }
+                }
+            wave_lds_fence();
+            // 64 pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction
+#pragma unroll
+            for (int pass = 0; pass < 8; ++pass) {
+                const int row = pass * 8 + (lane >> 3);
+                const int q = p0 + row;
+                if (q < HW)
+                    *reinterpret_cast<u32x4*>(Y + ((size_t)img * HW + q) * dm.Cout + col0 + (lane & 7) * 8) =
+                        *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
+            }
+        }
+        __syncthreads();  // the staging is read out before the next tile's halo lands on it
+    }
+}
+
 // y[p][c] = act(sum_z partial[z][p][c] + bias[c]) -> bf16; one thread per 8 channels
 __global__ void __launch_bounds__(256)
 conv_splitk_finalize_kernel(const float* __restrict__ partial, const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y, long rows,
@@ -459,6 +670,15 @@ int launch_conv(const void* x, const void* w, const void* bias, void* y, void* p
     return launch<conv3x3_kernel<STRIDE, KSPLIT>>(dim3(gx, gy, (unsigned)dm.zsplit), kThreads, lds, stream, "alo_conv3x3_nhwc", args);
 }
 
+template <bool KSPLIT>
+int launch_conv_d2(const void* x, const void* w, const void* bias, void* y, void* partial, const ConvDims& dm, hipStream_t stream) {
+    constexpr int lds = GeoD2::kLds + kThreads * 4;
+    void* args[] = {&x, &w, &bias, &y, &partial, const_cast<ConvDims*>(&dm)};
+    const unsigned gy = KSPLIT ? dm.Cout / 64 : (dm.Cout + 127) / 128;
+    const unsigned gx = xcd_grid(dm.tiles_per_image * dm.N, 128);   // as launch_conv
+    return launch<conv3x3_d2_kernel<KSPLIT>>(dim3(gx, gy, (unsigned)dm.zsplit), kThreads, lds, stream, "alo_conv3x3_nhwc", args);
+}
+
 int launch_conv_c64(const void* x, const void* w, const void* bias, void* y, const ConvDims& dm, hipStream_t stream) {
     void* args[] = {&x, &w, &bias, &y, const_cast<ConvDims*>(&dm)};
     const unsigned gx = xcd_grid(dm.tiles_per_image * dm.N, 64);   // 32 CUs per XCD x 2 resident workgroups (the weights take the registers of a third)
@@ -472,6 +692,7 @@ using namespace alo;
 
 extern "C" size_t alo_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride) {
     // a stride that carries a five-tap flag (ALO_F32 only, conv_f32.hip) answers 0 here as well: those kernels never split K
+    if (stride == (1 | ALO_CONV_DILATION_2)) stride = 1;   // the dilated flavour: the same output, the same split
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return 0;
     const long hwo = (long)((H - 1) / stride + 1) * ((W - 1) / stride + 1);
     const int z = conv_zsplit((int)((hwo + kPix - 1) / kPix) * N, Cin, Cout);
@@ -482,13 +703,17 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
                                 int W, int Cin, int Cout, int stride, int relu, int dtype, void* stream) {
     ALO_REQUIRE(x && w_packed && y, ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: null pointer argument");
     ALO_REQUIRE(N > 0 && H > 0 && W > 0, ALO_ERR_INVALID_ARGUMENT, "alo_conv3x3_nhwc: N, H, W must be positive");
-    // ALO_CONV_TAPS_1X5 / ALO_CONV_TAPS_5X1 ride above the stride's low byte (a negative stride is no flagged one)
-    const int taps = stride > 0 ? stride & ~0xff : 0;
-    if (taps) stride &= 0xff;
+    // ALO_CONV_TAPS_1X5 / ALO_CONV_TAPS_5X1 / ALO_CONV_DILATION_2 ride above the stride's low byte (a negative stride is no flagged one)
+    const int flags = stride > 0 ? stride & ~0xff : 0;
+    const int dil2 = flags & ALO_CONV_DILATION_2, taps = flags & ~ALO_CONV_DILATION_2;
+    if (flags) stride &= 0xff;
     ALO_REQUIRE(stride == 1 || stride == 2, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: stride must be 1 or 2 (got %d)", stride);
     ALO_REQUIRE(!taps || taps == ALO_CONV_TAPS_1X5 || taps == ALO_CONV_TAPS_5X1, ALO_ERR_UNSUPPORTED,
-                "alo_conv3x3_nhwc: stride carries 0x%x above its low byte: one of ALO_CONV_TAPS_1X5, ALO_CONV_TAPS_5X1 (five taps) or nothing", taps);
+                "alo_conv3x3_nhwc: stride carries 0x%x above its low byte: one of ALO_CONV_TAPS_1X5, ALO_CONV_TAPS_5X1 (five taps), ALO_CONV_DILATION_2 or nothing", taps);
     ALO_REQUIRE(!taps || stride == 1, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: the five-tap flavours (ALO_CONV_TAPS_*) are stride 1 only");
+    ALO_REQUIRE(!dil2 || stride == 1, ALO_ERR_UNSUPPORTED, "alo_conv3x3_nhwc: the dilated flavour (ALO_CONV_DILATION_2) is stride 1 only");
+    ALO_REQUIRE(!dil2 || !taps, ALO_ERR_UNSUPPORTED,
+                "alo_conv3x3_nhwc: ALO_CONV_DILATION_2 does not combine with the five-tap flavours (ALO_CONV_TAPS_*)");
     ALO_REQUIRE(Cin >= 64 && Cin % 64 == 0 && Cout >= 64 && Cout % 64 == 0, ALO_ERR_UNSUPPORTED,
                 "alo_conv3x3_nhwc: Cin and Cout must be multiples of 64 (Cin=%d Cout=%d)", Cin, Cout);
     // ALO_F32 (conv_f32.hip) is held to the checks of a bf16 call; every other dtype meets the refusal it always met
@@ -505,7 +730,7 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
         hipStream_t s = static_cast<hipStream_t>(stream);
         if (taps) return conv_taps_f32(x, w_packed, bias, y, workspace, N, H, W, Cin, Cout, taps == ALO_CONV_TAPS_5X1, relu, s);
         void* const image_mag = static_cast<char*>(workspace) + alo_conv3x3_workspace_bytes(N, H, W, Cin, Cout, stride);
-        return conv3x3_f32(x, w_packed, bias, y, image_mag, N, H, W, Cin, Cout, stride, relu, s);
+        return conv3x3_f32(x, w_packed, bias, y, image_mag, N, H, W, Cin, Cout, stride, dil2 ? 2 : 1, relu, s);
     }
     ConvDims dm;
     dm.N = N; dm.H = H; dm.W = W; dm.Cin = Cin; dm.Cout = Cout; dm.relu = relu;
@@ -518,10 +743,11 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
     // ALO_CONV3X3_C64 = "stream" keeps the 64 -> 64 stride-1 shape on conv3x3_kernel<1, true> (measurement knob; read per call: a test
     // flips it inside one process)
     const char* knob = getenv("ALO_CONV3X3_C64");
-    if (stride == 1 && Cin == 64 && Cout == 64 && dm.zsplit == 1 && !(knob && !strcmp(knob, "stream")))
+    if (!dil2 && stride == 1 && Cin == 64 && Cout == 64 && dm.zsplit == 1 && !(knob && !strcmp(knob, "stream")))
         return launch_conv_c64(x, w_packed, bias, y, dm, s);
     const bool ksplit = Cout == 64;
-    const int rc = stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
+    const int rc = dil2 ? (ksplit ? launch_conv_d2<true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv_d2<false>(x, w_packed, bias, y, workspace, dm, s))
+                 : stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
                                : (ksplit ? launch_conv<2, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<2, false>(x, w_packed, bias, y, workspace, dm, s));
     if (rc != ALO_OK || dm.zsplit == 1) return rc;
     const long rows = (long)N * dm.Ho * dm.Wo;

@@ -19,6 +19,9 @@
 // is written over the plan; conv3x3_f32_kernel keeps its own copy of it: as an instantiation of the shared loop over a 3x3 plan its
 // code changes (stride 1: 2422 -> 2441 instructions, stride 2: 4225 -> 4238, tools/isa_diff.py), and the rule of mfma_tile.hpp is that
 // a kernel's code moves only with a measurement.
+//
+// The dilated 3x3 (ALO_CONV_DILATION_2: dilation 2, padding 2, stride 1; conv3x3_d2_f32_kernel) is that shared loop over a nine-tap plan
+// (Plan3x3D2) and the undilated call's (Cout, 9 Cin) matrix.
 #include "mfma_tile.hpp"
 #include "split_f16.hpp"
 
@@ -264,6 +267,27 @@ struct Plan5 {
     }
 };
 
+// The dilated 3x3 (ALO_CONV_DILATION_2: dilation 2, zero padding 2, stride 1) is a third plan: three runs of 64 + 4 pixels, 2 W pixels
+// apart (rows y - 2, y, y + 2; flattened index p - 2 .. p + 65); tap t = 3 dy + dx at row y + 2 (dy - 1), column x + 2 (dx - 1) begins at
+// slot kRun dy + 2 dx.  The weight is the undilated call's (Cout, 9 Cin) matrix.
+struct Plan3x3D2 {
+    static constexpr int kTaps = 9;
+    static constexpr int kRun = kPix + 4;
+    static constexpr int kSlots = 3 * kRun;
+    static constexpr int kMinBlocks = 2;
+    static __device__ __forceinline__ int slot_pixel(int slot, int p0, const ConvF32Dims& dm) {
+        const int run = slot / kRun, pix = slot - run * kRun;
+        const int q = p0 + (run - 1) * 2 * dm.W - 2 + pix;
+        const int last = dm.H * dm.W - 1;
+        return q < 0 ? 0 : (q > last ? last : q);
+    }
+    static __device__ __forceinline__ int tap_slot(int t) { return (t / 3) * kRun + 2 * (t % 3); }
+    static __device__ __forceinline__ bool tap_inside(int t, int y, int x, const ConvF32Dims& dm) {
+        const int yy = y + 2 * (t / 3 - 1), xx = x + 2 * (t % 3 - 1);
+        return yy >= 0 && yy < dm.H && xx >= 0 && xx < dm.W;
+    }
+};
+
 // conv3x3_f32_kernel's loop over halo plan P
 template <class P, bool KSPLIT>
 __device__ __forceinline__ void conv_f32_tiles(const float* __restrict__ X, const f16_t* __restrict__ Wp, const float* __restrict__ bias,
@@ -417,6 +441,13 @@ conv_taps_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, 
     conv_f32_tiles<Plan5<VERTICAL>, KSPLIT>(X, Wp, bias, Y, mag, dm);
 }
 
+template <bool KSPLIT>
+__global__ void __launch_bounds__(kThreads, Plan3x3D2::kMinBlocks)
+conv3x3_d2_f32_kernel(const float* __restrict__ X, const f16_t* __restrict__ Wp, const float* __restrict__ bias, float* __restrict__ Y,
+                      const unsigned* __restrict__ mag, const ConvF32Dims dm) {
+    conv_f32_tiles<Plan3x3D2, KSPLIT>(X, Wp, bias, Y, mag, dm);
+}
+
 template <class G, auto KERNEL, bool KSPLIT>
 int launch_conv_f32(const void* x, const void* w, const void* bias, void* y, const void* mag, const ConvF32Dims& dm, hipStream_t stream) {
     constexpr int lds = G::kLds + kThreads * 8;
@@ -439,7 +470,7 @@ int image_magnitudes(const void* x, void* image_mag, int N, long per_image, hipS
 }  // namespace
 
 int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,
-                int stride, int relu, hipStream_t stream) {
+                int stride, int dilation, int relu, hipStream_t stream) {
     ConvF32Dims dm;
     dm.N = N; dm.H = H; dm.W = W; dm.Cin = Cin; dm.Cout = Cout; dm.relu = relu;
     dm.Ho = (H - 1) / stride + 1;
@@ -448,6 +479,9 @@ int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, v
     const int rc = image_magnitudes(x, image_mag, N, (long)H * W * Cin, stream);
     if (rc != ALO_OK) return rc;
     const bool ksplit = Cout == 64;
+    if (dilation == 2)   // stride 1 (checked by the caller)
+        return ksplit ? launch_conv_f32<Staging<Plan3x3D2::kSlots>, conv3x3_d2_f32_kernel<true>, true>(x, w_split, bias, y, image_mag, dm, stream)
+                      : launch_conv_f32<Staging<Plan3x3D2::kSlots>, conv3x3_d2_f32_kernel<false>, false>(x, w_split, bias, y, image_mag, dm, stream);
     return stride == 1 ? (ksplit ? launch_conv_f32<Geo<1>, conv3x3_f32_kernel<1, true>, true>(x, w_split, bias, y, image_mag, dm, stream)
                                  : launch_conv_f32<Geo<1>, conv3x3_f32_kernel<1, false>, false>(x, w_split, bias, y, image_mag, dm, stream))
                        : (ksplit ? launch_conv_f32<Geo<2>, conv3x3_f32_kernel<2, true>, true>(x, w_split, bias, y, image_mag, dm, stream)

@@ -445,12 +445,20 @@ int alo_conv3x3_small_nhwc(const void* x, const void* w_frag, const void* bias32
  * convolutions of RAFT's SepConvGRU (alonet/raft/update.py:94-133) on the same arithmetic — 1x5 with zero padding (0, 2), or 5x1 with
  * zero padding (2, 0); stride 1, y (N, H, W, Cout).  w_packed is the fp32 flavour's buffer of the (Cout, 5 * Cin) tap-major matrix
  * w[o][t * Cin + c] (= the channels-last memory order of a (Cout, Cin, 1, 5) or (Cout, Cin, 5, 1) weight).  The flags sit above the low
- * byte, which still holds the stride.  A flag with ALO_BF16, with stride 2, both flags at once or any other bit above the low byte is
- * refused (ALO_ERR_UNSUPPORTED, the message names the taps); every other check is the 3x3 call's.  alo_conv3x3_workspace_bytes takes the
- * same flagged stride (it answers 0: no split-K; the 4 * N bytes of magnitudes come on top as above).
+ * byte, which still holds the stride.  A tap flag with ALO_BF16, with stride 2, both tap flags at once or any bit above the low byte
+ * that is none of the three flags here is refused (ALO_ERR_UNSUPPORTED, the message names the taps); every other check is the 3x3
+ * call's.  alo_conv3x3_workspace_bytes takes the same flagged stride (it answers 0: no split-K; the 4 * N bytes of magnitudes come on top
+ * as above).
+ *
+ * ALO_CONV_DILATION_2 OR-ed into `stride` (stride = 1 | ALO_CONV_DILATION_2), ALO_BF16 or ALO_F32: the 3x3 convolution with dilation 2
+ * and zero padding 2 at stride 1, y (N, H, W, Cout) — layer4.1 / layer4.2 conv2 of a "DC5" ResNet (replace_stride_with_dilation =
+ * (False, False, True)).  The nine taps sit at offsets {-2, 0, 2}^2; w_packed, bias, the workspace rules and every check are the
+ * undilated call's, and alo_conv3x3_workspace_bytes(..., 1 | ALO_CONV_DILATION_2) answers what stride 1 answers.  The flag with stride 2
+ * or together with a tap flag is refused (ALO_ERR_UNSUPPORTED, the message names ALO_CONV_DILATION_2).
  */
 #define ALO_CONV_TAPS_1X5 0x100
 #define ALO_CONV_TAPS_5X1 0x200
+#define ALO_CONV_DILATION_2 0x800
 size_t alo_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride);
 int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void* bias, void* y, void* workspace, int N, int H, int W, int Cin,
                      int Cout, int stride, int relu, int dtype, void* stream);

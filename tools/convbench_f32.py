@@ -1,7 +1,7 @@
 """alo_hip.conv3x3_f32 against MIOpen's fp32 F.conv2d, layer by layer: the six 3x3 convolutions of RAFT's update block at B = 4,
 90 x 160 (720p / 8) and the 64- and 128-channel stride-1 shapes of RAFT's encoders.
 
-    python tools/convbench_f32.py [--rounds 5] [--reps 20] [--only conv3x3|gru]
+    python tools/convbench_f32.py [--rounds 5] [--reps 20] [--only conv3x3|gru|dilated]
 
 Per shape the two sides alternate `rounds` times in one process (same box, same minute), each round timing `reps` calls between
 device events after a warm-up of every shape; printed are the median round and the spread (min - max) in microseconds per call.
@@ -10,6 +10,9 @@ is what the stock route launches: F.conv2d without bias on NCHW, then alo_hip.bi
 --only gru (or no --only): also the four five-tap launches of SepConvGRU per iteration at the same size, alo_hip.conv_taps_f32 +
 the channels-last gate pass against what the fused route launches in their place (F.conv2d without bias on NCHW + the planar gate
 pass), each shown with and without its gate pass.
+--only dilated (or no --only): also the dilated 3x3 of a DC5 backbone (layer4.1 / layer4.2 conv2: 512 -> 512, dilation 2, padding 2, at
+1/16 of 800 x 1333) at batch 8 and batch 1, alo_hip.conv3x3_f32(..., dilation=2) against the stock route of
+alonet.detr.backbone.conv_bn: F.conv2d on channels-last + alo_hip.bias_act_.
 One JSON line per shape."""
 import argparse
 import json
@@ -112,16 +115,38 @@ def gru_launches(rounds, reps):
         print(json.dumps(row), flush=True)
 
 
+DILATED = [("DC5 layer4.x.conv2 (d=2)", (8, 512, 50, 84), 512), ("DC5 layer4.x.conv2 (d=2), batch 1", (1, 512, 50, 84), 512)]
+
+
+def dilated_layers(rounds, reps):
+    for name, (n, cin, h, w), cout in DILATED:
+        x = torch.randn(n, cin, h, w, device="cuda").contiguous(memory_format=torch.channels_last)
+        wt = (torch.randn(cout, cin, 3, 3, device="cuda") / (9 * cin) ** 0.5).contiguous(memory_format=torch.channels_last)
+        b = torch.randn(cout, device="cuda")
+        sides = {
+            "kernel": lambda: alo_hip.conv3x3_f32(x, wt, b, relu=True, dilation=2),
+            "miopen": lambda: F.conv2d(x, wt, None, 1, 2, 2),
+            "miopen+bias_act": lambda: alo_hip.bias_act_(F.conv2d(x, wt, None, 1, 2, 2), b, None, True),
+        }
+        got, want = sides["kernel"](), sides["miopen+bias_act"]()
+        err = (got - want).abs().max().item() / want.abs().max().item()
+        times = measure(sides, rounds, reps)
+        row = report({"layer": name, "shape": [n, cin, h, w], "cout": cout, "max_diff_over_max": err}, times)
+        row["kernel_tflops_fp32_equivalent"] = round(2.0 * 9 * cin * n * h * w * cout / row["kernel_us"] / 1e6, 1)
+        row["kernel_over_stock"] = round(row["kernel_us"] / row["miopen+bias_act_us"], 3)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--only", choices=["conv3x3", "gru"], default=None)
+    ap.add_argument("--only", choices=["conv3x3", "gru", "dilated"], default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("convbench_f32: needs the GPU (a timing taken anywhere else says nothing)")
     torch.manual_seed(0)
-    for name, (n, cin, h, w), cout in LAYERS if args.only != "gru" else []:
+    for name, (n, cin, h, w), cout in LAYERS if args.only in (None, "conv3x3") else []:
         pad = (cout + 63) // 64 * 64
         x = torch.randn(n, cin, h, w, device="cuda")
         x_cl = x.contiguous(memory_format=torch.channels_last)
@@ -142,9 +167,12 @@ def main():
         flops = 2.0 * 9 * cin * n * h * w * pad
         row["kernel_tflops_fp32_equivalent"] = round(flops / row["kernel_us"] / 1e6, 1)
         print(json.dumps(row), flush=True)
-    if args.only != "conv3x3":
+    if args.only in (None, "gru"):
         with torch.no_grad():
             gru_launches(args.rounds, args.reps)
+    if args.only in (None, "dilated"):
+        with torch.no_grad():
+            dilated_layers(args.rounds, args.reps)
 
 
 if __name__ == "__main__":
