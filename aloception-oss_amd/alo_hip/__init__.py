@@ -105,6 +105,7 @@ _SIGNATURES = {
     "alo_msda_backward": (_ip, [_vp] * 9 + [_ip] * 9 + [_vp]),
     "alo_msda_backward_hinted": (_ip, [_vp] * 9 + [_ip] * 9 + [_i32p, _vp]),
     "alo_msda_backward_path": (_ip, [_ip] * 9 + [_i32p]),
+    "alo_msda_generic_plan": (_ip, [_ip] * 9 + [_i32p] + [_ip] * 4 + [_ipp]),
     "alo_corr_level_shape": (None, [_ip, _ip, _ip, _ipp, _ipp]),
     "alo_corr_build_workspace_bytes": (_size, [_ip] * 5),
     "alo_corr_build": (_ip, [_vp, _vp, _vpp, _vp, _size] + [_ip] * 5 + [_vp]),

@@ -1858,6 +1858,7 @@ struct FwdArgs {
 // WAVE / WAVE_HM: msda_fwd_bf16_mfma_kernel on a pixel-major (bf16) / head-major (bf16, fp16) value; RESIDENT:
 // msda_fwd_bf16_resident_kernel (bf16 only: fp16 takes WAVE_HM under either policy), with `rd`.
 enum FwdRoute { FWD_NONE, FWD_GENERIC, FWD_WAVE, FWD_WAVE_HM, FWD_RESIDENT };
+static_assert(FWD_GENERIC == ALO_MSDA_FWD_GENERIC && FWD_WAVE == ALO_MSDA_FWD_WAVE, "alo_msda_generic_plan reports these two by number");
 
 // What a plan hands to the launch: the route and the dims of the kernel it names.
 struct LaunchPlan {
@@ -1875,6 +1876,9 @@ LaunchPlan plan_forward(const Shape& s, const FwdArgs& a) {
     const auto [N, S, M, D, L, Lq, P, vdt] = s;
     LaunchPlan fp;
     fp.plan = make_plan(D, L, P, s.elem(), a.aligned);
+    // the L * P = 16 stage reads a location pair in ONE load (ld2: 8 bytes fp32, 16 fp64, 4 for fused 2-byte offsets), which only
+    // 16-byte aligned loc / attn / ref guarantee; without that the row with the same lanes and element-wise loads serves the launch
+    if (!a.in_aligned) fp.plan.lp16 = false;
     // bf16 rows go to the matrix pipe untouched, one wave per 16 pairs (see msda_fwd_bf16_mfma_kernel); fp16 rows only when they are
     // head-major: pixel-major, the fp16 wave kernel measured level with the generic one (encoder launch, N = 8: 0.255 against 0.255 ms
     // on the ring, 0.304 against 0.303 trained-like), head-major it is 16 % / 24 % ahead of it (docs/experiments.md)
@@ -2099,4 +2103,26 @@ extern "C" int alo_msda_backward_path(int N, int S, int M, int D, int L, int Lq,
                                       const int32_t* host_spatial_shapes) {
     const Shape s{N, S, M, D, L, Lq, P, value_dtype};
     return validate(s, loc_dtype) ? -1 : plan_backward(s, host_spatial_shapes, true, true).route;
+}
+
+// The whole plan of a launch, nothing enqueued: the route, and for the generic kernels the table row and the block shape.  Forward:
+// the pixel-major entry points (alo_msda_forward, alo_msda_forward_fused with `fused`); `aligned` and `all_aligned` are what
+// forward_impl / alo_msda_backward_hinted compute from the pointers.
+extern "C" int alo_msda_generic_plan(int N, int S, int M, int D, int L, int Lq, int P, int value_dtype, int loc_dtype,
+                                     const int32_t* host_spatial_shapes, int backward, int fused, int aligned, int all_aligned, int* out) {
+    const Shape s{N, S, M, D, L, Lq, P, value_dtype};
+    if (!out || validate(s, loc_dtype)) return -1;
+    FwdArgs a;
+    a.ref_dim = fused ? 2 : 0;
+    a.fused = fused != 0;
+    a.aligned = aligned != 0;
+    a.in_aligned = all_aligned != 0;
+    const LaunchPlan lp = backward ? plan_backward(s, host_spatial_shapes, aligned != 0, aligned && all_aligned) : plan_forward(s, a);
+    const bool generic = lp.route == (backward ? (int)ALO_MSDA_BWD_GENERIC : (int)FWD_GENERIC);
+    for (int i = 0; i < 6; ++i) out[i] = 0;   // the other kernels have no row (and the tiled / wide ones no Dims)
+    if (generic) {
+        out[0] = lp.plan.vec; out[1] = lp.plan.g; out[2] = lp.plan.lp16;
+        out[3] = lp.dm.iters_per_block; out[4] = lp.dm.blocks_per_batch; out[5] = lp.dm.runs_per_batch;
+    }
+    return lp.route;
 }

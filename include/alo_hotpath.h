@@ -35,7 +35,10 @@ extern "C" {
 #endif
 
 #define ALO_HOTPATH_ABI_VERSION 3   /* 3: the entry points of alo_two_stage.h and alo_encoder_block.h are part of this library;
-                                          their own version functions and *_ABI_VERSION macros are gone */
+                                          their own version functions and *_ABI_VERSION macros are gone.
+                                          The number changes when an entry point goes or changes its signature or meaning.  An added
+                                          entry point (alo_msda_generic_plan) or a new value of an existing argument keeps it: a
+                                          consumer finds a library that lacks an entry point by name */
 
 typedef enum alo_status {
     ALO_OK = 0,
@@ -224,6 +227,27 @@ int alo_msda_backward_hinted(const void* value, const int32_t* spatial_shapes, c
 #define ALO_MSDA_BWD_WIDE 2
 int alo_msda_backward_path(int N, int S, int M, int D, int L, int Lq, int P, int value_dtype, int loc_dtype,
                            const int32_t* host_spatial_shapes);
+
+/*
+ * The whole plan of an MSDA launch, without enqueuing anything: which kernel, and for the generic kernels (msda_fwd_kernel /
+ * msda_bwd_kernel, one table of instantiations in csrc/msda.hip) which row of the table and which block shape.
+ *   backward = 0: alo_msda_forward (fused = 0) or alo_msda_forward_fused (fused = 1) on a pixel-major value; returns
+ *                 ALO_MSDA_FWD_GENERIC or ALO_MSDA_FWD_WAVE (the matrix-core kernel: bf16, L = P = 4, D % 8 == 0, D <= 32, every pointer
+ *                 aligned).  host_spatial_shapes is not read.
+ *   backward = 1: alo_msda_backward_hinted with this hint; returns ALO_MSDA_BWD_* as alo_msda_backward_path does (fused is not read).
+ *   aligned:      value and out (backward: value and grad_out) are on 16 bytes.
+ *   all_aligned:  every other tensor is (forward: sampling_loc / offsets, attn_weight / logits, reference_points; backward:
+ *                 sampling_loc, attn_weight and the three gradients).  The launches compute both flags from their pointers.
+ * out[6] = {vec, g, lp16, iters_per_block, blocks_per_batch, iters_total} when the route is the generic kernel, zeros otherwise:
+ * g lanes x vec channels serve a (query, head) pair, so a workgroup of 256 threads handles runs of 256 / g pairs; lp16 = 1 is the
+ * instantiation with L * P = 16 unrolled; a batch item is iters_total runs, shared out as iters_per_block (1 ... 4) runs to each of its
+ * blocks_per_batch workgroups.  Returns -1 (out untouched) for a launch the library refuses, as alo_msda_backward_path does, and for
+ * out == NULL.  The launches and this query read one plan, so they cannot disagree.
+ */
+#define ALO_MSDA_FWD_GENERIC 1
+#define ALO_MSDA_FWD_WAVE 2
+int alo_msda_generic_plan(int N, int S, int M, int D, int L, int Lq, int P, int value_dtype, int loc_dtype,
+                          const int32_t* host_spatial_shapes, int backward, int fused, int aligned, int all_aligned, int* out);
 
 /* Size of level l of the correlation pyramid of an (H, W) feature grid: level 0 = (H, W), level l+1 = floor(level l / 2)
  * (F.avg_pool2d(2, stride=2), corr.py:25-27). */

@@ -76,7 +76,8 @@ ROLES = {
 }
 
 # Entries of alo_hip._SIGNATURES that enqueue nothing: queries answered on the host.
-HOST_ONLY = {"alo_abi_version", "alo_last_error", "alo_corr_level_shape", "alo_msda_resident_levels", "alo_msda_backward_path"}
+HOST_ONLY = {"alo_abi_version", "alo_last_error", "alo_corr_level_shape", "alo_msda_resident_levels", "alo_msda_backward_path",
+             "alo_msda_generic_plan"}
 # Entry points the header documents as another entry point with fixed arguments, and that alo_hip never calls: {name: reason}.
 NEVER_LAUNCHED = {
     "alo_msda_backward": "include/alo_hotpath.h: 'alo_msda_backward is this call [alo_msda_backward_hinted] with a NULL hint'; "

@@ -119,17 +119,18 @@ def test_g17_the_reference_trt_plugin_test_case_at_full_size(golden):
 
 
 # ---- oracle on seeded inputs: every kernel variant ---------------------------------------------------------------
-CASES = [  # (N, M, D, Lq, shapes, P, fp32 backward)   which plan it exercises (fp32)
-    (2, 8, 32, 77, [(16, 21), (8, 11), (4, 6), (2, 3)], 4, TILED),  # vec4 / group 8 / unrolled LP=16  (the DETR shape)
-    (1, 8, 32, 300, [(20, 27), (10, 14), (5, 7), (3, 4)], 4, TILED),  # decoder-like query count
-    (2, 4, 16, 33, [(9, 7), (5, 4)], 8, PER_CORNER),  # vec4 / group 4 / unrolled LP=16
-    (1, 2, 64, 19, [(6, 5), (3, 3), (2, 2)], 2, PER_CORNER),  # vec4 / group 16 / runtime LP
+CASES = [  # (N, M, D, Lq, shapes, P, fp32 backward)   the forward plan it exercises in fp32; in fp64 (vec2: twice the lanes) where it differs,
+          # as alo_msda_generic_plan reports both (tests/msda_plan_cases.py pins every row of the table in every dtype)
+    (2, 8, 32, 77, [(16, 21), (8, 11), (4, 6), (2, 3)], 4, TILED),  # vec4 / group 8 / unrolled LP=16  (the DETR shape); fp64: vec2 / group 16 / unrolled
+    (1, 8, 32, 300, [(20, 27), (10, 14), (5, 7), (3, 4)], 4, TILED),  # decoder-like query count, same plans
+    (2, 4, 16, 33, [(9, 7), (5, 4)], 8, PER_CORNER),  # vec4 / group 4 / unrolled LP=16; fp64: vec2 / group 8 / unrolled
+    (1, 2, 64, 19, [(6, 5), (3, 3), (2, 2)], 2, PER_CORNER),  # vec4 / group 16 / runtime LP; fp64: vec2 / group 64
     (1, 1, 256, 9, [(5, 5)], 3, PER_CORNER),  # vec4 / group 64
     (1, 2, 512, 5, [(4, 6)], 2, PER_CORNER),  # vec4 / group 64, two channel chunks
-    (1, 3, 30, 21, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path (D % 4 != 0), group 64
+    (1, 3, 30, 21, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path (D % 4 != 0), group 64; fp64: vec2 / group 16 / runtime LP (D % 2 == 0)
     (2, 2, 71, 11, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path, two chunks
-    (1, 2, 2, 2, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path, group 8 (the reference test's D)
-    (1, 2, 8, 13, [(7, 3)], 1, PER_CORNER),  # vec4 / group 4, L*P = 1
+    (1, 2, 2, 2, [(6, 4), (3, 2)], 2, PER_CORNER),  # scalar path, group 8 (the reference test's D); fp64: vec2 / group 4 / runtime LP
+    (1, 2, 8, 13, [(7, 3)], 1, PER_CORNER),  # vec4 / group 4, L*P = 1; fp64: vec2 / group 4
     (2, 8, 32, 454, [(16, 21), (8, 11), (4, 6), (2, 3)], 4, WIDE),  # Lq == S: the wide backward's 16x16 query blocks
     (1, 4, 32, 130, [(9, 13), (5, 7), (3, 4), (2, 2)], 4, TILED),  # tiled backward, 16-query runs with a ragged tail, 4 heads
     (1, 6, 32, 168, [(9, 13), (5, 7), (3, 4), (2, 2)], 4, WIDE),  # wide backward, Lq == S, a head count that is not a power of two
