@@ -16,6 +16,8 @@
 //   * Cout == 64 (ResNet layer1) would leave the second wave without columns: there the two waves split K instead (each takes
 //     every other weight batch) and the partial sums meet in LDS.
 //     Cin == Cout == 64 at stride 1 goes to conv3x3_c64_kernel, the same split on four waves with the weights kept in registers.
+//   * stride 1 with Cout >= 128 and no split-K goes to conv3x3_pipe_kernel: this arithmetic on four waves per halo, with the LDS reads
+//     and the weight requests issued ahead of the MFMAs that use them.
 //   * ALO_CONV_DILATION_2 in `stride` (dilation 2, padding 2, stride 1: layer4 of a DC5 backbone) goes to conv3x3_d2_kernel, the
 //     stride-1 loop over runs of 68 pixels two rows apart with the taps two slots apart.
 #include <cstdlib>
@@ -628,6 +630,201 @@ conv3x3_d2_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, c
     }
 }
 
+// ---- stride 1, Cout >= 128, no split-K: conv3x3_kernel<1, false>'s arithmetic with its requests issued ahead of their use ------------
+// In conv3x3_kernel<1, false> every A fragment is read from LDS right in front of the MFMAs that take it, the weights are requested one
+// batch (8 MFMAs) ahead, each chunk starts its weights cold, and __syncthreads drains what is in flight.  Here
+//   * four waves share one halo.  Cout >= 256: a tile of 96 pixels x 256 channels, a wave = RT = 3 row tiles of 32 pixels x 64 channels, so
+//     a weight fragment feeds three MFMAs, not two: the weight stream through the vector cache is what a wave waits for most (without
+//     it the kernel runs 1.4-1.6 times faster, without its LDS reads 1.1 times; docs/experiments.md), and 96-pixel tiles deal the
+//     headline's layer3 in one round (352 workgroups on 512 slots).  Four row tiles per wave need one wave per SIMD and lose.
+//     Cout = 128 / 192: 128 pixels x 128 channels, RT = 2, wave 2 c + h = pixel half h of column half c;
+//   * the A fragments of k-step s + 1 are read before the MFMAs of k-step s;
+//   * the weights stream through a ring of k-step fragments (six at RT = 2, four at RT = 3), requested about 20 MFMAs ahead.  The ring
+//     runs on across chunks and tiles: the weights depend on neither, so the first k-steps of the next chunk are requested before the
+//     barriers, not behind them;
+//   * the barriers wait for LDS alone (pipe_lds_barrier) and the epilogue orders its staging with ALO_WAVE_LDS_ORDER: neither drains the
+//     ring or the staged halo.  Weights and halo come through loads in the global address space, which LDS waits do not count.
+// An accumulator sees the k-steps in conv3x3_kernel's order (chunk, tap, channel), one MFMA each, from zero, with the same masking,
+// bias, ReLU and rounding, and a lane of the MFMA owns one pixel: the output is that kernel's bit for bit whatever RT is.  The chunk
+// body is unrolled (36 k-steps, whole turns of the ring: a ring slot has to be a register name).  Byte offsets inside an image are
+// 32-bit (the host checks).
+template <int PIX, int RT>   // pixels per workgroup tile; 32-pixel row tiles per wave
+struct GeoPipe {
+    static constexpr int kWavePix = 32 * RT;                 // pixels per wave
+    static_assert(PIX == kWavePix || PIX == 2 * kWavePix, "four waves: 1 x 4 or 2 x 2 (pixels x columns)");
+    static constexpr int kCols = PIX == kWavePix ? 256 : 128;   // output channels per workgroup
+    static constexpr int kChunk = Geo<1>::kChunk;
+    static constexpr int kSteps = 9 * (kChunk / 16);         // k-steps per chunk
+    static constexpr int kRing = RT == 3 ? 4 : 6;            // weight fragments (one k-step, two column tiles) in the ring: ~20 MFMAs ahead
+    static_assert(kSteps % kRing == 0, "a chunk is a whole number of turns: a slot is the same register name in every chunk");
+    static constexpr int kRun = PIX + 2;
+    static constexpr int kSlots = 3 * kRun;
+    static constexpr int kPixStride = Geo<1>::kPixStride;
+    static constexpr int kPieces = kSlots * (kChunk / 8);
+    static constexpr int kIters = (kPieces + 255) / 256;     // halo pieces per thread: 10 (PIX = 96), 13 (128)
+    static constexpr int kHalo = kSlots * kPixStride;
+    static constexpr int kOut = 4 * kWavePix * kOutStride;   // four waves' bf16 output blocks; aliases the halo
+    static constexpr int kLds = kHalo > kOut ? kHalo : kOut;
+};
+constexpr int kPipeThreads = 256;
+
+// waits for this wave's LDS traffic only, then the workgroup barrier (encoder_block.hip's lds_barrier)
+__device__ __forceinline__ void pipe_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <int PIX, int RT>
+__global__ void __launch_bounds__(kPipeThreads, 2)
+conv3x3_pipe_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, const bf16_t* __restrict__ bias,
+                    bf16_t* __restrict__ Y, const ConvDims dm) {   // dm.tiles_per_image counts tiles of PIX pixels
+    using G = GeoPipe<PIX, RT>;
+    typedef const u32x4 __attribute__((address_space(1))) * global_u32x4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const halo = smem;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // wave: known uniform to the compiler
+    const int nl = lane & 31, kg = lane >> 5;
+    const int wcol = PIX == G::kWavePix ? wave : wave >> 1;              // this wave's 64 columns of the workgroup's
+    const int pbase = PIX == G::kWavePix ? 0 : G::kWavePix * (wave & 1);   // and its pixels of the tile
+    const int HW = dm.H * dm.W;
+    const int col0 = blockIdx.y * G::kCols + wcol * 64;
+    const bool has_cols = col0 < dm.Cout;                  // Cout % 64 == 0
+    float* const bias_s = reinterpret_cast<float*>(smem + G::kLds);   // the workgroup's bias values, fp32; read after the tile's barriers
+    {
+        const int c = blockIdx.y * G::kCols + tid;
+        bias_s[tid] = (bias != nullptr && tid < G::kCols && c < dm.Cout) ? bf16_to_f32(bias[c].bits) : 0.f;
+    }
+
+    // persistent workgroups, one contiguous eighth of the tiles per XCD (see conv3x3_kernel)
+    const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
+    const int tile_end = range.end, lanes_per_xcd = range.step;
+    int tile = range.first;
+    if (tile >= tile_end) return;
+
+    const int ksteps_per_tap = dm.Cin / 16;
+    const size_t ctile_stride = (size_t)9 * ksteps_per_tap * 512;      // elements between the packed column tiles
+    const bf16_t* const wcols = Wp + (size_t)(has_cols ? col0 / 32 : 0) * ctile_stride;   // uniform; + this lane's 16 bytes of a fragment
+    const unsigned lane_bytes = lane * 16;
+    // k-step s of the chunk at channel c0: tap s / 4, channels c0 + 16 (s % 4) .. (conv3x3_kernel's order), both column tiles
+    auto load_w = [&](u32x4 (&f)[2], int c0, int s) {
+        const bf16_t* p = wcols + (size_t)((s >> 2) * ksteps_per_tap + (c0 >> 4) + (s & 3)) * 512;
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+            f[b] = *(global_u32x4)(uintptr_t)(reinterpret_cast<const unsigned char*>(p + b * ctile_stride) + lane_bytes);
+    };
+
+    // The halo travels through registers, requested one (tile, chunk) ahead.  Piece i = tid + 256 it is 16 bytes (tid & 7) of staging
+    // slot i >> 3 (slots past the last one repeat it and are not parked); every request is made, in-range by clamping.
+    u32x4 stage[G::kIters];
+    const unsigned piece_bytes = (tid & 7) * 16, row_bytes = dm.Cin * 2;
+    auto load_halo = [&](int tl, int c0) {
+        const int im = tl / dm.tiles_per_image, first = (tl - im * dm.tiles_per_image) * PIX;
+        const unsigned char* ximg = reinterpret_cast<const unsigned char*>(X + (size_t)im * HW * dm.Cin + c0);   // uniform
+#pragma unroll
+        for (int it = 0; it < G::kIters; ++it) {
+            int slot = (tid >> 3) + it * (kPipeThreads / 8);
+            slot = slot < G::kSlots ? slot : G::kSlots - 1;
+            const int run = slot / G::kRun;
+            int q = first + (run - 1) * dm.W - 1 + (slot - run * G::kRun);
+            q = q < 0 ? 0 : (q > HW - 1 ? HW - 1 : q);
+            stage[it] = *(global_u32x4)(uintptr_t)(ximg + ((unsigned)q * row_bytes + piece_bytes));   // H W Cin < 2^30
+        }
+    };
+    load_halo(tile, 0);
+
+    // k-step n of the wave's stream (kSteps = 36 per chunk, chunks and tiles on end) lives in ring[n % kRing]; a chunk is a whole number
+    // of turns, so a slot is the same register name in every chunk.  A wave without columns streams column tile 0 and stores nothing: no branch
+    // around the requests, whose count the compiler's waits rely on.
+    u32x4 ring[G::kRing][2];   // [slot][column tile]
+#pragma unroll
+    for (int s = 0; s < G::kRing - 1; ++s) load_w(ring[s], 0, s);
+    __builtin_amdgcn_sched_barrier(0);
+
+    const unsigned char* const a_lane = halo + (pbase + nl) * G::kPixStride + kg * 16;
+    unsigned char* const obuf = smem + wave * (G::kWavePix * kOutStride);
+
+    for (; tile < tile_end; tile += lanes_per_xcd) {
+        const int img = tile / dm.tiles_per_image;
+        const int p0 = (tile - img * dm.tiles_per_image) * PIX + pbase;   // this wave's first output pixel inside the image
+        const int next_tile = tile + lanes_per_xcd < tile_end ? tile + lanes_per_xcd : tile;
+
+        // which of the 9 taps exist for this lane's pixels (row tile a: output pixel p0 + 32 a + nl)
+        unsigned tapmask[RT];
+#pragma unroll
+        for (int a = 0; a < RT; ++a) {
+            const int q = p0 + 32 * a + nl;
+            const int y = q / dm.W, x = q - y * dm.W;
+            unsigned m = 0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = y + t / 3 - 1, xx = x + t % 3 - 1;
+                if (q < HW && yy >= 0 && yy < dm.H && xx >= 0 && xx < dm.W) m |= 1u << t;
+            }
+            tapmask[a] = m;
+        }
+
+        f32x16 acc[RT][2];  // [row tile][column tile]
+        zero_acc(acc);
+
+#pragma unroll 1
+        for (int c0 = 0; c0 < dm.Cin; c0 += G::kChunk) {
+#pragma unroll
+            for (int it = 0; it < G::kIters; ++it) {
+                const int i = tid + it * kPipeThreads;
+                if (it < G::kPieces / kPipeThreads || i < G::kPieces)
+                    *reinterpret_cast<u32x4*>(halo + (i >> 3) * G::kPixStride + (i & 7) * 16) = stage[it];
+            }
+            pipe_lds_barrier();
+            // the next chunk, of this tile or of the next one (the last tile asks for its own first chunk again: no branch around requests)
+            const bool last_chunk = c0 + G::kChunk >= dm.Cin;
+            const int c0_next = last_chunk ? 0 : c0 + G::kChunk;
+            load_halo(last_chunk ? next_tile : tile, c0_next);
+            __builtin_amdgcn_sched_barrier(0);
+
+            u32x4 af[2][RT];   // [k-step parity][row tile]: the fragments of k-step s + 1 are read before the MFMAs of k-step s
+#pragma unroll
+            for (int a = 0; a < RT; ++a) af[0][a] = *reinterpret_cast<const u32x4*>(a_lane + 32 * a * G::kPixStride);
+#pragma unroll
+            for (int s = 0; s < G::kSteps; ++s) {   // k-step of the chunk: tap s / 4, channels 16 (s % 4) ..
+                // k-step s + kAhead of the stream takes the slot k-step s - 1 left
+                constexpr int kAhead = G::kRing - 1;
+                if (s + kAhead < G::kSteps) load_w(ring[(s + kAhead) % G::kRing], c0, s + kAhead);
+                else load_w(ring[(s + kAhead) % G::kRing], c0_next, s + kAhead - G::kSteps);
+                if (s + 1 < G::kSteps) {
+                    const int tn = (s + 1) >> 2, slot = (tn / 3) * G::kRun + tn % 3;
+#pragma unroll
+                    for (int a = 0; a < RT; ++a)
+                        af[(s + 1) & 1][a] = *reinterpret_cast<const u32x4*>(a_lane + (slot + 32 * a) * G::kPixStride + ((s + 1) & 3) * 32);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const int t = s >> 2;
+                u32x4 am[RT];
+#pragma unroll
+                for (int a = 0; a < RT; ++a) am[a] = ((tapmask[a] >> t) & 1u) ? af[s & 1][a] : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int a = 0; a < RT; ++a) acc[a][b] = mfma_32x32x16<bf16_t>(ring[s % G::kRing][b], am[a], acc[a][b]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            pipe_lds_barrier();  // the halo is overwritten by the next channel chunk (and by the epilogue's staging)
+        }
+
+        if (has_cols) {
+            // lane = output pixel 32 a + nl, registers 4 q .. 4 q + 3 = channels col0 + 32 b + 8 q + 4 kg .. + 3 (see conv3x3_kernel)
+            stage_quads<bf16_t, true>(obuf, kOutStride, acc, bias_s + wcol * 64, dm.relu, nl, 0, kg);
+            ALO_WAVE_LDS_ORDER();
+            // the wave's pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction
+#pragma unroll
+            for (int pass = 0; pass < G::kWavePix / 8; ++pass) {
+                const int row = pass * 8 + (lane >> 3);
+                const int q = p0 + row;
+                if (q < HW)
+                    *reinterpret_cast<u32x4*>(Y + ((size_t)img * HW + q) * dm.Cout + col0 + (lane & 7) * 8) =
+                        *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
+            }
+        }
+        pipe_lds_barrier();  // the staging is read out before the next tile's halo lands on it
+    }
+}
+
 // y[p][c] = act(sum_z partial[z][p][c] + bias[c]) -> bf16; one thread per 8 channels
 __global__ void __launch_bounds__(256)
 conv_splitk_finalize_kernel(const float* __restrict__ partial, const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y, long rows,
@@ -683,6 +880,17 @@ int launch_conv_c64(const void* x, const void* w, const void* bias, void* y, con
     void* args[] = {&x, &w, &bias, &y, const_cast<ConvDims*>(&dm)};
     const unsigned gx = xcd_grid(dm.tiles_per_image * dm.N, 64);   // 32 CUs per XCD x 2 resident workgroups (the weights take the registers of a third)
     return launch<conv3x3_c64_kernel>(dim3(gx), kC64Threads, kC64Lds, stream, "alo_conv3x3_nhwc", args);
+}
+
+template <int PIX, int RT>
+int launch_conv_pipe(const void* x, const void* w, const void* bias, void* y, const ConvDims& dm, hipStream_t stream) {
+    using G = GeoPipe<PIX, RT>;
+    ConvDims dp = dm;
+    dp.tiles_per_image = (dm.H * dm.W + PIX - 1) / PIX;
+    void* args[] = {&x, &w, &bias, &y, &dp};
+    const unsigned gx = xcd_grid(dp.tiles_per_image * dm.N, 64);   // 32 CUs per XCD x 2 resident workgroups of four waves
+    const unsigned gy = (dm.Cout + G::kCols - 1) / G::kCols;
+    return launch<conv3x3_pipe_kernel<PIX, RT>>(dim3(gx, gy), kPipeThreads, G::kLds + kPipeThreads * 4, stream, "alo_conv3x3_nhwc", args);
 }
 
 }  // namespace
@@ -745,6 +953,20 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
     const char* knob = getenv("ALO_CONV3X3_C64");
     if (!dil2 && stride == 1 && Cin == 64 && Cout == 64 && dm.zsplit == 1 && !(knob && !strcmp(knob, "stream")))
         return launch_conv_c64(x, w_packed, bias, y, dm, s);
+    // ALO_CONV3X3_PIPE = "off" keeps the stride-1 shapes of 128 and more output channels on conv3x3_kernel<1, false> (measurement knob,
+    // read per call like ALO_CONV3X3_C64); the two kernels agree bit for bit.  Measured in the headline's graph replay, knob off then on
+    // (profiles/conv3x3_pipe_{parent,change}_kernel_stats.csv, split by grid in the traces; avg (min-max) over 37 passes, us):
+    //   128 ch 100 x 167: 62.9 (60.4-69.0) -> 54.7 (52.4-62.3);  256 ch 50 x 84: 73.3 (68.3-82.8) -> 50.3 (47.6-59.4);
+    //   512 ch 25 x 42: 77.4 (67.2-86.8) -> 60.7 (58.9-70.3).  Faster in every one of the 37 passes, and max below min over the 30
+    //   timed passes for all three (56.1 < 60.7, 53.5 < 70.3, 62.7 < 74.7); over all 37 passes max is below min for 256 channels only:
+    //   at 128 and 512 the new kernel's slowest warm-up launch (pass 1) is above the old kernel's fastest eager launch (pass 0).
+    //   Eager, per tag (LaunchTimer, the backbone alone, 10 forwards per leg): 128 ch 65.4 (63.7-68.4) -> 58.2 (56.7-61.2), 256 ch 75.5
+    //   (73.4-79.9) -> 53.1 (52.0-57.2), 512 ch 79.5 (77.9-81.9) -> 63.9 (62.1-67.8): max below min for all three.
+    // Tile shapes tried at 256 / 512 channels (us per launch, back to back): 64 x 256 two row tiles 57.9 / 62.5, 128 x 128 two row
+    // tiles 61.7 / 66.5, 128 x 256 four row tiles (one wave per SIMD) 83 / 77, 96 x 256 three row tiles 49.3 / 56: the last is routed.
+    const char* pipe = getenv("ALO_CONV3X3_PIPE");
+    if (!dil2 && stride == 1 && Cout >= 128 && dm.zsplit == 1 && (long)H * W * Cin < (1L << 30) && !(pipe && !strcmp(pipe, "off")))
+        return Cout >= 256 ? launch_conv_pipe<96, 3>(x, w_packed, bias, y, dm, s) : launch_conv_pipe<128, 2>(x, w_packed, bias, y, dm, s);
     const bool ksplit = Cout == 64;
     const int rc = dil2 ? (ksplit ? launch_conv_d2<true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv_d2<false>(x, w_packed, bias, y, workspace, dm, s))
                  : stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
