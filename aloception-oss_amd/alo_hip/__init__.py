@@ -25,7 +25,8 @@ RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.
 # fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
 # value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
 # (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32, stem_conv_pool_f32, linear_f32
-# and conv1x1_strided_f32 are the fp32 flavours of four of them, each behind a gate of its own).  fp16 is opt-in per call site: `fusable`
+# and conv1x1_strided_f32 are the fp32 flavours of four of them, each behind a gate of its own; upsample_flow rides upsample_add's
+# entry point with ALO_F32).  fp16 is opt-in per call site: `fusable`
 # and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
 # fp16 kernels do (the transformer's layers), so an fp16 tensor never reaches a kernel that lacks it
 _DTYPE_CODE = {torch.float32: ALO_F32, torch.float64: ALO_F64, torch.bfloat16: ALO_BF16, torch.float16: ALO_F16}
@@ -1627,6 +1628,33 @@ def upsample_add(x_low, fpn):
     if out.numel():
         _launch("alo_upsample_add_nhwc", x_low.device, f"upsample_add/C={c_}", 2.0 * (out.numel() + x_low.numel() + fpn.numel()), 0.0,
                 x_low, fpn, out, bq, bq // b_, c_, h, w_, H, W, ALO_BF16)
+    return out
+
+
+def upsample_flow_supported(flow, mask=None):
+    """``upsample_flow`` covers: a contiguous fp32 CUDA flow (N, C, h, w) with 1 <= C <= 8, 16-byte aligned, and a contiguous fp32
+    mask (N, 576, h, w) on the same device, 16-byte aligned, or ``None`` (bilinear); no autograd on either."""
+    if not (flow.dim() == 4 and flow.is_cuda and flow.dtype == torch.float32 and flow.is_contiguous() and 1 <= flow.shape[1] <= 8
+            and flow.data_ptr() % 16 == 0 and not needs_autograd(flow, mask)):
+        return False
+    return mask is None or (mask.dim() == 4 and mask.device == flow.device and mask.dtype == torch.float32 and mask.is_contiguous()
+                            and tuple(mask.shape) == (flow.shape[0], 576, flow.shape[2], flow.shape[3]) and mask.data_ptr() % 16 == 0)
+
+
+def upsample_flow(flow, mask=None):
+    """RAFT's x8 flow up-sampling in one launch (csrc/upsample_flow.hip), (N, C, h, w) -> (N, C, 8h, 8w) fp32.  With the
+    (N, 576, h, w) mask logits of the update block (channel k * 64 + i * 8 + j): the convex combination of
+    ``RAFTBase.upsample_flow`` — softmax over the 9 taps k, zero-padded 3x3 neighbours of ``8 * flow``.  With ``mask=None``:
+    ``8 * F.interpolate(flow, scale 8, mode="bilinear", align_corners=True)`` (``upflow8``).  Forward only."""
+    _no_autograd("upsample_flow", flow, mask)
+    if not upsample_flow_supported(flow, mask):
+        raise RuntimeError("upsample_flow: needs a contiguous fp32 CUDA flow (N, C, h, w) with 1 <= C <= 8 and a contiguous fp32 mask "
+                           "(N, 576, h, w) or None, both 16-byte aligned, no autograd")
+    n, c_, h, w_ = flow.shape
+    out = torch.empty((n, c_, 8 * h, 8 * w_), dtype=flow.dtype, device=flow.device)
+    if out.numel():
+        nbytes = 4.0 * (flow.numel() + out.numel() + (0 if mask is None else mask.numel()))
+        _launch("alo_upsample_add_nhwc", flow.device, "upsample_flow", nbytes, 0.0, flow, mask, out, n, 1, c_, h, w_, 8 * h, 8 * w_, ALO_F32)
     return out
 
 

@@ -7,10 +7,13 @@ are multiples of 8; the result is a list (one dict per iteration) with ``flow`` 
 convex up-sampling).  The correlation volume is built once by ``corr_block`` (default: the HIP ``CorrBlock``) and
 looked up once per iteration.
 """
+import os
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+import alo_hip
 from aloscene import Flow
 from alonet.common import load_weights
 
@@ -18,6 +21,13 @@ from .corr import CorrBlock
 from .extractor import BasicEncoder
 from .update import BasicUpdateBlock
 from .utils.utils import coords_grid, upflow8
+
+
+def _upsample_fused_route(flow, mask):
+    """``ALO_RAFT_UPSAMPLE=fused``: ``upsample_flow`` is one launch of ``alo_hip.upsample_flow`` (the mask is read once; bilinear
+    without a mask) when grad mode is off and the kernel's gate admits the tensors.  Opt-in; read per call."""
+    return (os.environ.get("ALO_RAFT_UPSAMPLE") == "fused" and not torch.is_grad_enabled()
+            and alo_hip.upsample_flow_supported(flow, mask))
 
 
 class RAFTBase(nn.Module):
@@ -67,6 +77,8 @@ class RAFTBase(nn.Module):
     def upsample_flow(self, flow, mask):
         """(N, 2, H, W) -> (N, 2, 8H, 8W): each fine pixel is a softmax-weighted (convex) mix of its 3x3 coarse
         neighbourhood; bilinear when no mask is predicted."""
+        if _upsample_fused_route(flow, mask):
+            return alo_hip.upsample_flow(flow, mask)
         if mask is None:
             return upflow8(flow)
         N, _, H, W = flow.shape

@@ -137,6 +137,10 @@ int stem_conv_pool_f32(const void* x, const void* w_split, const void* bias, voi
 int instancenorm_f32(const void* x, void* y, void* workspace, int B, int HW, int C, float eps, long y_batch_stride, int relu,
                      hipStream_t stream, const char* what);
 
+// upsample_flow.hip: the fp32 flavour of alo_upsample_add_nhwc on checked arguments (planar flow and mask: alo_hotpath.h); mask NULL is
+// the bilinear mode; refuses a map whose mask planes of one image reach 4 GiB.
+int upsample_flow_f32(const void* flow, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream, const char* what);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

@@ -55,7 +55,7 @@ typedef enum alo_status {
  * fp16 range becomes +-inf (no clamp).  Every other entry point that takes a dtype refuses it: alo_encoder_block, the backbone and
  * input-projection kernels (alo_conv1x1_nhwc, alo_conv3x3_*, alo_stem_conv_pool, alo_groupnorm_*, alo_upsample_add_nhwc) are bf16 only
  * (alo_conv3x3_nhwc, alo_stem_conv_pool, alo_linear_packed, alo_conv1x1_nhwc and alo_ffn256 also serve ALO_F32, and
- * alo_groupnorm_rows_act serves it as an InstanceNorm: see there).
+ * alo_groupnorm_rows_act serves it as an InstanceNorm and alo_upsample_add_nhwc as RAFT's flow up-sampling: see there).
  * Every entry point checks its dtype first; an fp16 call then meets the argument checks of a bf16 call. */
 typedef enum alo_dtype {
     ALO_F32 = 0,
@@ -539,6 +539,19 @@ int alo_groupnorm_rows_act(const void* x, const void* weight, const void* bias, 
  * `_expand(adapter(fpn), Q) + F.interpolate(x, size=(H, W), mode="nearest")` of the mask decoder's FPN steps (FPNstyle.py:60-84) in
  * one pass — without the per-query copy of the adapter output, the up-sampled copy and the add.  Index arithmetic of ATen's nearest
  * kernel (scale = float(in) / out, src = min(int(floorf(dst * scale)), in - 1)); fp32 add, one rounding: bit-identical to the stock ops.
+ *
+ * dtype = ALO_F32: RAFT's x8 flow up-sampling (alonet/raft/raft.py RAFTBase.upsample_flow, utils.upflow8), forward only, in one launch.
+ * Here the maps are PLANAR (NCHW), fp32, contiguous: x_low is the coarse flow (BQ, C, h, w), out (BQ, C, H, W) with H = 8 h, W = 8 w,
+ * Q = 1, 1 <= C <= 8 (2 for a flow field).  fpn is the update block's mask logits (BQ, 576, h, w), channel = k * 64 + i * 8 + j:
+ *   out[n, c, 8y + i, 8x + j] = sum_k softmax_k(fpn[n, k * 64 + i * 8 + j, y, x]) * 8 * x_low[n, c, y + k / 3 - 1, x + k % 3 - 1]
+ * (k = 0..8; max-subtracted softmax in fp32).  A neighbour outside the image has value 0 and keeps its weight, as F.unfold's zero
+ * padding gives it: nothing is renormalised over the in-image taps.  The mask is read once; nothing of its size is written.
+ * fpn = NULL: out = 8 * F.interpolate(x_low, (H, W), mode="bilinear", align_corners=True) in ATen's arithmetic (source coordinate =
+ * dst * (in - 1) / (out - 1), the quotient formed in fp32).  Non-finite values go where that arithmetic sends them: nine -inf logits
+ * or one +inf logit make their own fine pixel NaN, a -inf logit is weight 0, a NaN flow value reaches the fine pixels of the cells it
+ * neighbours; a weight below 2^-126 is 0.  An fp32 call is recognised by its dtype before any check of the bf16 call and is held to
+ * its own, in this order: x_low and out non-null, BQ > 0, Q == 1, 1 <= C <= 8 (ALO_ERR_UNSUPPORTED), h, w > 0, H == 8 h and
+ * W == 8 w, every given pointer 16-byte aligned; a map whose 576 mask planes of one image reach 4 GiB is ALO_ERR_UNSUPPORTED.
  */
 int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* out, int BQ, int Q, int C, int h, int w, int H, int W, int dtype,
                           void* stream);
