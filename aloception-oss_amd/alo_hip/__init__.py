@@ -1658,6 +1658,78 @@ def upsample_flow(flow, mask=None):
     return out
 
 
+ALO_UPSAMPLE_GRAD = 0x100   # include/alo_hotpath.h: OR-ed into alo_upsample_add_nhwc's dtype (ALO_F32): the convex mode's backward
+
+
+def _upsample_flow_operands_ok(flow, mask):
+    return (flow.dim() == 4 and flow.is_cuda and flow.dtype == torch.float32 and flow.is_contiguous() and 1 <= flow.shape[1] <= 8
+            and flow.data_ptr() % 16 == 0 and mask is not None and mask.dim() == 4 and mask.device == flow.device
+            and mask.dtype == torch.float32 and mask.is_contiguous()
+            and tuple(mask.shape) == (flow.shape[0], 576, flow.shape[2], flow.shape[3]) and mask.data_ptr() % 16 == 0)
+
+
+def upsample_flow_autograd_supported(flow, mask):
+    """``upsample_flow_autograd`` covers what ``upsample_flow`` covers in its convex mode, whether or not autograd records: a
+    contiguous fp32 CUDA flow (N, C, h, w) with 1 <= C <= 8 and a contiguous fp32 mask (N, 576, h, w) on the same device, both
+    16-byte aligned.  The mask is required: the bilinear mode has no fused backward."""
+    return _upsample_flow_operands_ok(flow, mask)
+
+
+def upsample_flow_grad(flow, mask, grad_up):
+    """The backward of ``upsample_flow(flow, mask)`` (convex mode) in one launch (csrc/upsample_flow.hip, ALO_UPSAMPLE_GRAD):
+    ``grad_up`` (N, C, 8h, 8w) -> ``(grad_flow (N, C, h, w), grad_mask (N, 576, h, w))``.  No atomics: the same bits on every run.
+    ``grad_up`` may be any fp32 view (expanded, strided): it is copied once into the launch's input buffer, behind the flow.  The
+    kernel writes ``grad_mask`` and, per coarse pixel, the nine tap sums of every channel (the columns of ``F.unfold``'s adjoint);
+    ``F.fold`` of those, a tensor 1 / 32 of the mask's size, is ``grad_flow``.  The results are views of one buffer."""
+    if not _upsample_flow_operands_ok(flow, mask):
+        raise RuntimeError("upsample_flow_grad: needs a contiguous fp32 CUDA flow (N, C, h, w) with 1 <= C <= 8 and a contiguous fp32 "
+                           "mask (N, 576, h, w), both 16-byte aligned")
+    n, c_, h, w_ = flow.shape
+    if not (grad_up.dtype == torch.float32 and grad_up.device == flow.device and tuple(grad_up.shape) == (n, c_, 8 * h, 8 * w_)):
+        raise RuntimeError(f"upsample_flow_grad: grad_up must be fp32 ({n}, {c_}, {8 * h}, {8 * w_}) on {flow.device}, got "
+                           f"{tuple(grad_up.shape)} {grad_up.dtype} on {grad_up.device}")
+    nf = flow.numel()
+    start = (nf + 3) // 4 * 4
+    packed = torch.empty((start + 64 * nf,), dtype=torch.float32, device=flow.device)
+    out = torch.empty((n * (576 + 9 * c_) * h * w_,), dtype=torch.float32, device=flow.device)
+    grad_mask = out[:mask.numel()].view(mask.shape)
+    taps = out[mask.numel():].view(n, 9 * c_, h * w_)
+    if nf:
+        with torch.no_grad():
+            packed[:nf].copy_(flow.detach().reshape(-1))
+            packed[nf:start].zero_()
+            packed[start:].view(grad_up.shape).copy_(grad_up.detach())
+        nbytes = 4.0 * (packed.numel() + mask.numel() + out.numel())
+        _launch("alo_upsample_add_nhwc", flow.device, "upsample_flow_grad", nbytes, 0.0, packed, mask.detach(), out, n, 1, c_, h, w_,
+                8 * h, 8 * w_, ALO_F32 | ALO_UPSAMPLE_GRAD)
+    with torch.no_grad():
+        grad_flow = torch.nn.functional.fold(taps, (h, w_), 3, padding=1) if nf else torch.zeros_like(flow)
+    return grad_flow, grad_mask
+
+
+class _UpsampleFlow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, mask):
+        ctx.save_for_backward(flow, mask)
+        return upsample_flow(flow, mask)       # grad mode is off in here
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_up):
+        flow, mask = ctx.saved_tensors
+        grad_flow, grad_mask = upsample_flow_grad(flow, mask, grad_up)
+        return (grad_flow if ctx.needs_input_grad[0] else None), (grad_mask if ctx.needs_input_grad[1] else None)
+
+
+def upsample_flow_autograd(flow, mask):
+    """``upsample_flow(flow, mask)`` (convex mode) that autograd can differentiate once: the forward is that launch, the backward
+    ``upsample_flow_grad``.  An input that does not require grad gets ``None``."""
+    if not upsample_flow_autograd_supported(flow, mask):
+        raise RuntimeError("upsample_flow_autograd: needs a contiguous fp32 CUDA flow (N, C, h, w) with 1 <= C <= 8 and a contiguous "
+                           "fp32 mask (N, 576, h, w), both 16-byte aligned")
+    return _UpsampleFlow.apply(flow, mask)
+
+
 def groupnorm_rows(x, weight, bias, groups, eps=1e-5, out=None):
     """``F.group_norm`` over channels-last rows: x (B, HW, C) contiguous -> out (B, HW, C), which may be a slice
     ``flat[:, start:start + HW]`` of a larger (B, S, C) buffer (rows contiguous, any batch stride)."""

@@ -1,5 +1,6 @@
 from .corr import AlternateCorrBlock, CorrBlock
+from .criterion import RAFTCriterion
 from .raft import RAFT, RAFTBase
 from .raft_small import RAFTSmall
 
-__all__ = ["AlternateCorrBlock", "CorrBlock", "RAFT", "RAFTBase", "RAFTSmall"]
+__all__ = ["AlternateCorrBlock", "CorrBlock", "RAFT", "RAFTBase", "RAFTCriterion", "RAFTSmall"]

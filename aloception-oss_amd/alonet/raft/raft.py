@@ -24,10 +24,19 @@ from .utils.utils import coords_grid, upflow8
 
 
 def _upsample_fused_route(flow, mask):
-    """``ALO_RAFT_UPSAMPLE=fused``: ``upsample_flow`` is one launch of ``alo_hip.upsample_flow`` (the mask is read once; bilinear
-    without a mask) when grad mode is off and the kernel's gate admits the tensors.  Opt-in; read per call."""
-    return (os.environ.get("ALO_RAFT_UPSAMPLE") == "fused" and not torch.is_grad_enabled()
+    """``ALO_RAFT_UPSAMPLE=fused`` (or ``train``, below): ``upsample_flow`` is one launch of ``alo_hip.upsample_flow`` (the mask is
+    read once; bilinear without a mask) when grad mode is off and the kernel's gate admits the tensors.  Opt-in; read per call."""
+    return (os.environ.get("ALO_RAFT_UPSAMPLE") in ("fused", "train") and not torch.is_grad_enabled()
             and alo_hip.upsample_flow_supported(flow, mask))
+
+
+def _upsample_train_route(flow, mask):
+    """``ALO_RAFT_UPSAMPLE=train``: what ``fused`` is with grad mode off; with grad mode on the convex mode (a mask is predicted) is
+    ``alo_hip.upsample_flow_autograd`` — the same forward launch, one backward launch plus an ``F.fold`` of a tensor 1 / 32 of the
+    mask's size, nothing mask-sized kept for autograd but the logits themselves.  The bilinear mode under grad mode and CPU tensors
+    keep the stock ops.  Opt-in; read per call."""
+    return (os.environ.get("ALO_RAFT_UPSAMPLE") == "train" and torch.is_grad_enabled() and mask is not None
+            and alo_hip.upsample_flow_autograd_supported(flow, mask))
 
 
 class RAFTBase(nn.Module):
@@ -79,6 +88,8 @@ class RAFTBase(nn.Module):
         neighbourhood; bilinear when no mask is predicted."""
         if _upsample_fused_route(flow, mask):
             return alo_hip.upsample_flow(flow, mask)
+        if _upsample_train_route(flow, mask):
+            return alo_hip.upsample_flow_autograd(flow, mask)
         if mask is None:
             return upflow8(flow)
         N, _, H, W = flow.shape

@@ -140,6 +140,9 @@ int instancenorm_f32(const void* x, void* y, void* workspace, int B, int HW, int
 // upsample_flow.hip: the fp32 flavour of alo_upsample_add_nhwc on checked arguments (planar flow and mask: alo_hotpath.h); mask NULL is
 // the bilinear mode; refuses a map whose mask planes of one image reach 4 GiB.
 int upsample_flow_f32(const void* flow, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream, const char* what);
+// its convex mode's backward (ALO_UPSAMPLE_GRAD) on checked arguments: x_low = flow then grad_up, out = grad_mask then taps (alo_hotpath.h)
+int upsample_flow_grad_f32(const void* flow_and_grad, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream,
+                           const char* what);
 
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)

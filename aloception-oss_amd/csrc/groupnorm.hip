@@ -322,6 +322,23 @@ extern "C" int alo_groupnorm_rows_act(const void* x, const void* weight, const v
 
 extern "C" int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* out, int BQ, int Q, int C, int h, int w, int H, int W,
                                      int dtype, void* stream) {
+    if (dtype & ~0xFF) {   // ALO_UPSAMPLE_GRAD rides above the dtype's low byte: the backward of the fp32 convex up-sampling
+        const char* what = "alo_upsample_add_nhwc";
+        ALO_REQUIRE(dtype == (ALO_F32 | ALO_UPSAMPLE_GRAD), ALO_ERR_UNSUPPORTED,
+                    "%s: dtype carries 0x%x above its low byte: ALO_UPSAMPLE_GRAD (0x100) with ALO_F32, or nothing (dtype=0x%x)", what,
+                    (unsigned)dtype & ~0xFFu, (unsigned)dtype);
+        ALO_REQUIRE(x_low && out, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: x_low and out must not be null", what);
+        ALO_REQUIRE(fpn, ALO_ERR_INVALID_ARGUMENT,
+                    "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: fpn (the mask logits) must not be null: the bilinear mode has no fused backward", what);
+        ALO_REQUIRE(BQ > 0, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: BQ must be positive (BQ=%d)", what, BQ);
+        ALO_REQUIRE(Q == 1, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: Q must be 1 (Q=%d)", what, Q);
+        ALO_REQUIRE(C >= 1 && C <= 8, ALO_ERR_UNSUPPORTED, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: C must be 1 to 8 flow channels (C=%d)", what, C);
+        ALO_REQUIRE(h > 0 && w > 0, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: h and w must be positive (h=%d w=%d)", what, h, w);
+        ALO_REQUIRE(H == 8L * h && W == 8L * w, ALO_ERR_INVALID_ARGUMENT,
+                    "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: H and W must be 8 h and 8 w (h=%d w=%d H=%d W=%d)", what, h, w, H, W);
+        ALO_REQUIRE(aligned16(x_low, fpn, out), ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32 | ALO_UPSAMPLE_GRAD: pointers must be 16-byte aligned", what);
+        return upsample_flow_grad_f32(x_low, fpn, out, BQ, C, h, w, static_cast<hipStream_t>(stream), what);
+    }
     if (dtype == ALO_F32) {   // RAFT's flow up-sampling (upsample_flow.hip): planar fp32, fpn = the mask logits or NULL, C = 2 there
         const char* what = "alo_upsample_add_nhwc";
         ALO_REQUIRE(x_low && out, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_F32: x_low and out must not be null (fpn may: bilinear)", what);

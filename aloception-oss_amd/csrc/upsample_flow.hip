@@ -1,5 +1,5 @@
 // RAFT's flow up-sampling (alonet/raft/raft.py RAFTBase.upsample_flow, utils.upflow8): the fp32 flavour of alo_upsample_add_nhwc.
-// Planar (NCHW) fp32 in and out, x8 in both directions, forward only.
+// Planar (NCHW) fp32 in and out, x8 in both directions; the convex mode has a backward (ALO_UPSAMPLE_GRAD, below).
 //
 // Convex (mask given): every fine pixel is a softmax-weighted mix of the 3x3 coarse neighbourhood of its cell,
 //   out[n, c, 8y+i, 8x+j] = sum_k softmax_k(mask[n, k*64 + i*8 + j, y, x]) * 8 * flow[n, c, y + k/3 - 1, x + k%3 - 1]
@@ -142,6 +142,129 @@ upsample_flow_bilinear_kernel(const float* __restrict__ flow, float* __restrict_
     *reinterpret_cast<f32x4*>(out + idx * 4) = f32x4{o[0], o[1], o[2], o[3]};
 }
 
+// ---- the backward of the convex mode (ALO_UPSAMPLE_GRAD) ----------------------------------------------------------------------------
+// With w_k the forward's weights (the same max-subtracted softmax, the same exp and reciprocal) and G_c = grad_up[n, c, 8y+i, 8x+j]:
+//   t_k                                = sum_c G_c * 8 * flow[n, c, y + k/3 - 1, x + k%3 - 1]
+//   grad_mask[n, k*64 + i*8 + j, y, x] = w_k * (t_k - sum_k' w_k' t_k')
+//   taps[n, c*9 + k, y, x]             = 8 * sum_{i, j} w_k * G_c        (the columns of F.unfold's adjoint: the caller folds them)
+// The forward's access pattern: lanes run over the flattened coarse pixel, a thread owns one (n, p, sub-row i), 72 mask loads and 72
+// grad_mask stores through buffer resources with the plane offset in a scalar register, grad_up as two 16-byte loads per channel,
+// out-of-image neighbours as the zero of a buffer load past its resource.
+//   * All channels of a thread's grad_up sub-row and flow neighbours stay in registers (NC = 1, 2, 4 or 8 >= C, the rest zeros), so
+//     t_k is formed column by column and never stored.
+//   * The sum over i of `taps` is what the forward has no counterpart for.  A workgroup is the eight sub-rows of PX pixels; the
+//     partial sums of a pixel meet in LDS, two channels at a time, and are added in the order i = 0..7: no atomics, the same bits on
+//     every run.  A thread that owned all eight sub-rows would need no LDS, but a training crop (6 x 46 x 62 = 17k coarse pixels)
+//     would then be 270 waves on 256 CUs; this way it is 2160.  Measured (docs/experiments.md): that variant is 14 % faster on
+//     4 x 90 x 160 maps and 25 % slower on the crop.
+//   * PX = 64 (512 threads, wave i is sub-row i) for C <= 4; PX = 32 (256 threads) for C > 4, where a wave then has the whole
+//     register file and nothing goes to scratch.
+//   * A lane past the map's end works on the last pixel's values and stores nothing.
+
+// grad_up[n, c, 8y+i, 8x .. 8x+7] for c < NC; a channel past C reads the last one's row (in bounds) and counts as 0
+template <int NC>
+__device__ __forceinline__ void load_grad_rows(const float* __restrict__ grow, const UpFlowDims& dm, float (&g)[NC][8]) {
+    const long cstride = 64L * dm.hw;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const bool in = c < dm.C;
+        const float* const pg = grow + (in ? c : dm.C - 1) * cstride;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(pg), b = *reinterpret_cast<const f32x4*>(pg + 4);
+        const float r[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g[c][j] = in ? r[j] : 0.f;
+    }
+}
+
+template <int NC, int PX>
+__global__ void __launch_bounds__(8 * PX)
+upsample_flow_grad_kernel(const float* __restrict__ flow, const float* __restrict__ grad_up, const float* __restrict__ mask,
+                          float* __restrict__ grad_mask, float* __restrict__ taps, const UpFlowDims dm) {
+    constexpr int PC = NC < 2 ? NC : 2;   // channels per pass through LDS
+    __shared__ float part[8][9 * PC][PX];
+    const unsigned b = blockIdx.x;
+    const int chunk = b % dm.chunks;
+    const long n = b / dm.chunks;
+    const int i = threadIdx.x / PX, lane = threadIdx.x % PX;
+    const bool active = chunk * PX + lane < dm.hw;
+    const int p = active ? chunk * PX + lane : dm.hw - 1;
+    const int y = p / dm.w, x = p - y * dm.w;
+
+    const __amdgpu_buffer_rsrc_t mask_r = make_rsrc(mask + n * 576 * dm.hw, 576u * (unsigned)dm.hw * 4u);
+    const __amdgpu_buffer_rsrc_t gmask_r = make_rsrc(grad_mask + n * 576 * dm.hw, 576u * (unsigned)dm.hw * 4u);
+    const __amdgpu_buffer_rsrc_t flow_r = make_rsrc(flow + n * dm.C * dm.hw, (unsigned)(dm.C * dm.hw) * 4u);
+    const float* const grow = grad_up + ((n * dm.C * 8 * dm.h + 8 * y + i) * (8L * dm.w) + 8 * x);
+
+    float e[9][8];   // logits, then the weights
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            e[k][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mask_r, (unsigned)p * 4u, (int)((unsigned)(k * 64 + i * 8 + j) * (unsigned)dm.hw * 4u), 0));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float m = e[0][j];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) m = fmaxf(m, e[k][j]);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            e[k][j] = __expf(e[k][j] - m);
+            s += e[k][j];
+        }
+        const float rs = __builtin_amdgcn_rcpf(s);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k][j] *= rs;
+    }
+
+    float v[NC][9], g[NC][8];
+    load_neighbours<NC>(flow_r, dm, 0, y, x, v);
+    load_grad_rows<NC>(grow, dm, g);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float t[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            t[k] = g[0][j] * v[0][k];
+#pragma unroll
+            for (int c = 1; c < NC; ++c) t[k] = fmaf(g[c][j], v[c][k], t[k]);
+        }
+        float s = e[0][j] * t[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) s = fmaf(e[k][j], t[k], s);
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e[k][j] * (t[k] - s)), gmask_r, (unsigned)p * 4u,
+                                                      (int)((unsigned)(k * 64 + i * 8 + j) * (unsigned)dm.hw * 4u), 0);
+        }
+    }
+
+    float* const timg = taps + n * 9 * dm.C * dm.hw;
+#pragma unroll
+    for (int c0 = 0; c0 < NC; c0 += PC) {
+        if (c0 >= dm.C) break;   // uniform
+#pragma unroll
+        for (int c = 0; c < PC; ++c)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                float acc = e[k][0] * g[c0 + c][0];
+#pragma unroll
+                for (int j = 1; j < 8; ++j) acc = fmaf(e[k][j], g[c0 + c][j], acc);
+                part[i][c * 9 + k][lane] = 8.f * acc;
+            }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < 9 * PC * PX; idx += 8 * PX) {
+            const int ck = idx / PX, l = idx % PX;
+            float s = part[0][ck][l];
+#pragma unroll
+            for (int r = 1; r < 8; ++r) s += part[r][ck][l];
+            if (c0 * 9 + ck < 9 * dm.C && chunk * PX + l < dm.hw) timg[(long)(c0 * 9 + ck) * dm.hw + chunk * PX + l] = s;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 int upsample_flow_f32(const void* flow, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream, const char* what) {
@@ -166,6 +289,27 @@ int upsample_flow_f32(const void* flow, const void* mask, void* out, int BQ, int
     args[0] = &flow; args[1] = &mask; args[2] = &out; args[3] = &dm;
     return C % 2 == 0 ? launch<upsample_flow_convex_kernel<2>>((unsigned)blocks, kUpThreads, 0, stream, what, args)
                       : launch<upsample_flow_convex_kernel<1>>((unsigned)blocks, kUpThreads, 0, stream, what, args);
+}
+
+int upsample_flow_grad_f32(const void* flow_and_grad, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream, const char* what) {
+    const long hw = (long)h * w;
+    ALO_REQUIRE(hw * 576 * 4 < (1L << 32), ALO_ERR_UNSUPPORTED, "%s: the mask of one image must stay below 4 GiB (h=%d w=%d)", what, h, w);
+    UpFlowDims dm;
+    dm.C = C; dm.h = h; dm.w = w; dm.hw = (int)hw; const int px = C <= 4 ? 64 : 32;   // coarse pixels per workgroup
+    dm.chunks = (int)((hw + px - 1) / px);
+    const long blocks = (long)dm.chunks * BQ;
+    ALO_REQUIRE(blocks < (1L << 31), ALO_ERR_UNSUPPORTED, "%s: map too large (BQ=%d C=%d h=%d w=%d)", what, BQ, C, h, w);
+    // x_low: flow, then grad_up from the next multiple of 4 elements; out: grad_mask, then taps
+    const float* flow = static_cast<const float*>(flow_and_grad);
+    const float* grad_up = flow + ((long)BQ * C * hw + 3) / 4 * 4;
+    float* grad_mask = static_cast<float*>(out);
+    float* taps = grad_mask + (long)BQ * 576 * hw;
+    void* args[6] = {&flow, &grad_up, &mask, &grad_mask, &taps, &dm};
+    const unsigned grid = (unsigned)blocks;
+    return C == 1 ? launch<upsample_flow_grad_kernel<1, 64>>(grid, 512, 0, stream, what, args)
+         : C == 2 ? launch<upsample_flow_grad_kernel<2, 64>>(grid, 512, 0, stream, what, args)
+         : C <= 4 ? launch<upsample_flow_grad_kernel<4, 64>>(grid, 512, 0, stream, what, args)
+                  : launch<upsample_flow_grad_kernel<8, 32>>(grid, 256, 0, stream, what, args);
 }
 
 }  // namespace alo

@@ -552,7 +552,22 @@ int alo_groupnorm_rows_act(const void* x, const void* weight, const void* bias, 
  * neighbours; a weight below 2^-126 is 0.  An fp32 call is recognised by its dtype before any check of the bf16 call and is held to
  * its own, in this order: x_low and out non-null, BQ > 0, Q == 1, 1 <= C <= 8 (ALO_ERR_UNSUPPORTED), h, w > 0, H == 8 h and
  * W == 8 w, every given pointer 16-byte aligned; a map whose 576 mask planes of one image reach 4 GiB is ALO_ERR_UNSUPPORTED.
+ *
+ * dtype = ALO_F32 | ALO_UPSAMPLE_GRAD: the backward of that convex mode in one launch, without atomics: the same bits on every run.
+ * As in the chain flavour of alo_conv1x1_nhwc several tensors share a buffer; all are planar fp32, BQ, C, h, w, H, W as in the forward:
+ *   x_low (read)     flow (BQ, C, h, w), then, from the next multiple of 4 elements, grad_up (BQ, C, H, W)
+ *   fpn   (read)     the mask logits (BQ, 576, h, w); required, the bilinear mode has no fused backward
+ *   out   (written)  grad_mask (BQ, 576, h, w), then taps (BQ, 9 C, h, w); every byte of both is written
+ * With w_k = softmax_k(fpn[n, k * 64 + i * 8 + j, y, x]) in the forward's own arithmetic and G_c = grad_up[n, c, 8y + i, 8x + j]:
+ *   t_k                                  = sum_c G_c * 8 * flow[n, c, y + k / 3 - 1, x + k % 3 - 1]          (0 outside the image)
+ *   grad_mask[n, k * 64 + i * 8 + j, y, x] = w_k * (t_k - sum_k' w_k' t_k')
+ *   taps[n, c * 9 + k, y, x]               = 8 * sum_{i, j} w_k(i, j, y, x) * grad_up[n, c, 8y + i, 8x + j]
+ * taps are the columns of F.unfold's adjoint: grad_flow = F.fold(taps.view(BQ, 9 C, h * w), (h, w), 3, padding=1), a tensor 1 / 32 of
+ * the mask's size, which the caller folds.  The checks are the fp32 forward's in the same order plus fpn non-null (after x_low and
+ * out), their messages prefixed "alo_upsample_add_nhwc: ALO_F32 | ALO_UPSAMPLE_GRAD: ".  Any other bit above the dtype's low byte,
+ * or the flag with another dtype, is ALO_ERR_UNSUPPORTED and the message names ALO_UPSAMPLE_GRAD; an unflagged dtype answers as ever.
  */
+#define ALO_UPSAMPLE_GRAD 0x100
 int alo_upsample_add_nhwc(const void* x_low, const void* fpn, void* out, int BQ, int Q, int C, int h, int w, int H, int W, int dtype,
                           void* stream);
 
