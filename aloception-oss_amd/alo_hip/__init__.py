@@ -24,7 +24,8 @@ ALO_F32, ALO_F64, ALO_BF16, ALO_F16 = 0, 1, 2, 3
 RESIDENT_AUTO, RESIDENT_ALWAYS = 0, 1   # ALO_RESIDENT_* of include/alo_hotpath.h
 # fp16 is served by the MSDA entry points and the transformer's layer kernels (linear_shortk, linear_packed, ffn256,
 # value_proj_head_major, add_layernorm, bias_act, pos_sine_flat, pack_mfma_b, the two-stage glue); the backbone / projection kernels
-# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (conv3x3_f32, stem_conv_pool_f32, linear_f32
+# (conv*, stem, groupnorm, conv1x1_strided, upsample_add) and encoder_block are bf16 only (attention, on encoder_block's entry point,
+# takes bf16 / fp16 / fp32; conv3x3_f32, stem_conv_pool_f32, linear_f32
 # and conv1x1_strided_f32 are the fp32 flavours of four of them, each behind a gate of its own; upsample_flow rides upsample_add's
 # entry point with ALO_F32).  fp16 is opt-in per call site: `fusable`
 # and the `*_supported` gates answer for fp32 / bf16 unless asked with ``f16=True``, which only the callers whose whole route has
@@ -2023,6 +2024,72 @@ def decoder_block_b(attn_out, tgt1, pos, wo, bo, norm1, w1, b1, w2, b2, norm3, w
                            "a hidden width whose LDS frame fits (up to 21760)")
     return _decoder_block("decoder_block_b", ALO_BLOCK_DECODER_NEXT, attn_out, tgt1, pos, (wo, bo, *norm1), (w1, b1, w2, b2, *norm3),
                           (wv, bv, wqk, bqk), tile_rows)
+
+
+# ---- dense multi-head attention (ALO_BLOCK_ATTENTION of include/alo_encoder_block.h, csrc/attention.hip) ------------------------------
+ALO_BLOCK_ATTENTION, ALO_BLOCK_PACKED_QK = 0x2000, 0x8000   # OR-ed into alo_encoder_block's dtype
+ATTENTION_HEADS, ATTENTION_HEAD_DIM = 8, 32                 # the header's fixed geometry: d_model = 256
+
+
+def attention_routed():
+    """``ALO_ATTENTION=fused`` (read per call, opt-in) sends the dense attention of the Deformable-DETR decoder and of DETR's
+    transformer through :func:`attention`; unset, both keep the stock ops."""
+    return os.environ.get("ALO_ATTENTION", "").lower() == "fused"
+
+
+def _attention_packed(q, k):
+    """Whether q and k are the two 256-column halves of one contiguous (B, L, 512) tensor: chain B's [q; k] matrix, read in place."""
+    return (q.shape == k.shape and q.stride() == k.stride() == (q.shape[1] * 512, 512, 1)
+            and k.data_ptr() == q.data_ptr() + 256 * q.element_size())
+
+
+def attention_supported(q, k, v, key_padding_mask=None):
+    """What :func:`attention` takes: CUDA bf16 / fp16 / fp32 tensors outside autograd, q (B, Lq, 256), k and v (B, Lk, 256) with
+    Lq, Lk > 0, one dtype and device, 16-byte aligned; q and k contiguous or the halves of one (B, L, 512) tensor; a (B, Lk) bool or
+    uint8 mask or none; every operand below 2 GiB."""
+    if not (q.dim() == k.dim() == v.dim() == 3 and fusable(q, k, v, f16=True)):
+        return False
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    if not (E == ATTENTION_HEADS * ATTENTION_HEAD_DIM and k.shape == v.shape == (B, Lk, E) and B > 0 and Lq > 0 and Lk > 0):
+        return False
+    if not all(t.dtype == q.dtype and t.device == q.device and t.data_ptr() % 16 == 0 for t in (k, v)) or q.data_ptr() % 16:
+        return False
+    if not ((q.is_contiguous() and k.is_contiguous()) or _attention_packed(q, k)):
+        return False
+    if key_padding_mask is not None and not (key_padding_mask.shape == (B, Lk) and key_padding_mask.device == q.device
+                                             and key_padding_mask.dtype in (torch.bool, torch.uint8)):
+        return False
+    return B * max(Lq, Lk) * 512 * q.element_size() < 2 ** 31
+
+
+def attention(q, k, v, key_padding_mask=None):
+    """``softmax(q k^T / sqrt(32) + mask) v`` over 8 heads of 32 channels in one kernel, on batch-first tensors as the projections
+    write them (head h = columns 32 h .. 32 h + 31): no head-major reshapes.  q (B, Lq, 256), k and v (B, Lk, 256), bf16 / fp16 /
+    fp32; q and k may be the two halves ``qk[..., :256]`` / ``qk[..., 256:]`` of one (B, L, 512) tensor, which is then read in place.
+    ``key_padding_mask`` (B, Lk) bool / uint8: non-zero keys are ignored; a query with every key masked gets NaN, as
+    ``nn.MultiheadAttention`` gives.  -> (B, Lq, 256), before the output projection."""
+    _no_autograd("attention", q, k, v)
+    if not attention_supported(q, k, v, key_padding_mask):
+        raise RuntimeError("attention: needs CUDA bf16 / fp16 / fp32 (B, Lq, 256) q and (B, Lk, 256) k, v of one dtype outside autograd, "
+                           "q and k contiguous or the halves of one (B, L, 512) tensor, and a (B, Lk) bool / uint8 mask or none")
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    packed = not (q.is_contiguous() and k.is_contiguous())
+    v = v.contiguous()
+    mask = None
+    if key_padding_mask is not None:
+        mask = key_padding_mask.contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    out = torch.empty((B, Lq, E), dtype=q.dtype, device=q.device)
+    es = q.element_size()
+    nbytes = es * E * B * (2.0 * Lq + 2.0 * Lk) + (0 if mask is None else B * Lk)
+    flops = 4.0 * B * Lq * Lk * E
+    _launch("alo_encoder_block", q.device, f"attention/Lq={Lq}/Lk={Lk}", nbytes, flops,
+            v, None, None, None, None, q, None, None, None, None, None, None, out, k, mask, None, None, None, None, None, None,
+            B, Lq, Lk, ATTENTION_HEAD_DIM ** -0.5, 0.0,
+            _DTYPE_CODE[q.dtype] | ALO_BLOCK_ATTENTION | (ALO_BLOCK_PACKED_QK if packed else 0))
+    return out
 
 
 def panoptic_onehot(mask_logits, frame_size, threshold=0.5):

@@ -15,6 +15,7 @@ from torch import nn
 from torch.nn.init import constant_, normal_, xavier_uniform_
 
 import alo_hip
+from alonet.transformers.fused_layers import _add_norm, _attend, _ffn, _fused_ok, _in_proj_rows, _self_attention  # noqa: F401 (re-exported)
 
 from .ops.modules import MSDeformAttn
 from .utils import inverse_sigmoid
@@ -40,65 +41,6 @@ def _level_geometry(shapes, device):
         spatial_shapes._alo_shapes = list(shapes)
         _GEOMETRY[key] = (spatial_shapes, level_start_index)
     return _GEOMETRY[key]
-
-
-def _fused_ok(module, kwargs, *operands):
-    """The one-pass HIP epilogues (alo_add_layernorm) stand in for ``norm(x + dropout(y))`` when nothing is lost: eval mode
-    (dropout is the identity), no autograd graph, CUDA, fp32 / bf16 / fp16, and not the pure-torch export branch.  ``operands``:
-    the activation first, then every tensor and module the fast path behind this gate reads (alo_hip.fusable) — the kernels detach
-    their result, so a trainable parameter or an upstream tensor that requires grad sends the whole route to the stock ops."""
-    return (not module.training and "is_tracing" not in kwargs and alo_hip.fusable(*operands, f16=True)
-            and alo_hip.add_layernorm_supported(operands[0]))
-
-
-def _add_norm(norm, x, residual, pos=None):
-    return alo_hip.add_layernorm(x, residual, norm.weight, norm.bias, norm.eps, pos=pos)
-
-
-def _self_attention(mha, qk_in, v_in):
-    """Inference form of ``nn.MultiheadAttention(q = k = qk_in, v = v_in)`` on batch-first (B, L, E) tensors: the packed
-    input projection as two GEMMs (q and k share their input), ``scaled_dot_product_attention`` over the heads, the output
-    projection — no sequence-first transposes, projections on the short-K MFMA kernel when the shape allows."""
-    (w_qk, b_qk), (w_v, b_v) = _in_proj_rows(mha)
-    qk = alo_hip.linear_auto(qk_in, w_qk, b_qk)
-    v = alo_hip.linear_auto(v_in, w_v, b_v)
-    return alo_hip.linear_auto(_attend(mha, qk, v), mha.out_proj.weight, mha.out_proj.bias)
-
-
-def _in_proj_rows(mha):
-    """((w_qk (2E, E), b_qk), (w_v (E, E), b_v)) of ``mha``'s packed input projection."""
-    E = mha.embed_dim
-    w, b = mha.in_proj_weight, mha.in_proj_bias
-    # the SAME row slices every call (inference only: _fused_ok): what linear_auto derives from a weight rides on the tensor object
-    w_qk, w_v = alo_hip.derived(mha, "in_proj_rows", (w,), lambda: (w[: 2 * E], w[2 * E:]))
-    return (w_qk, None if b is None else b[: 2 * E]), (w_v, None if b is None else b[2 * E:])
-
-
-def _attend(mha, qk, v):
-    """``scaled_dot_product_attention`` over ``mha``'s heads on the projected (B, L, 2E) [q; k] and (B, L, E) v -> (B, L, E),
-    before the output projection."""
-    B, L, E = v.shape
-    H = mha.num_heads
-    heads = lambda t: t.reshape(B, L, H, E // H).transpose(1, 2)  # (B, H, L, E/H)
-    out = F.scaled_dot_product_attention(heads(qk[..., :E]), heads(qk[..., E:]), heads(v))
-    return out.transpose(1, 2).reshape(B, L, E)
-
-
-def _ffn(linear1, activation, linear2, x):
-    """``linear2(act(linear1(x)))``; for ReLU the activation rides in the first GEMM's epilogue (alo_linear_shortk when
-    d_model is 64 / 128 / 256 and the tensors are bf16 / fp16, else hipBLASLt's RELU_BIAS via ``torch._addmm_activation``) instead
-    of a separate pass over the (rows, d_ffn) intermediate.  d_model = 256: one kernel for both layers in bf16 / fp16, and in fp32
-    under ``ALO_F32_LAYERS=split`` at the shapes ``alo_hip.ffn_f32_routed`` admits."""
-    if activation is F.relu and alo_hip.ffn256_supported(x, linear1.weight, linear2.weight, f16=True):
-        # d_model = 256, bf16 / fp16: both layers in one kernel, the hidden activation never leaves the chip
-        return alo_hip.ffn256(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
-    if activation is F.relu and alo_hip.ffn_f32_routed(x, linear1.weight, linear2.weight):
-        # d_model = 256, fp32 under ALO_F32_LAYERS=split, at the shapes it was measured to win: the same block on the fp16 matrix cores
-        return alo_hip.ffn_f32(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
-    if activation is F.relu and linear1.bias is not None:
-        h = alo_hip.linear_auto(x, linear1.weight, linear1.bias, relu=True)
-        return alo_hip.linear_auto(h, linear2.weight, linear2.bias)
-    return linear2(activation(linear1(x)))
 
 
 PROPOSAL_EMBED_DIM = 512   # 4 box components x 128 sine features: fixed by the reference (:131), hence d_model = 256 for two-stage

@@ -3,14 +3,21 @@ queries and keys at every layer; the decoder returns the (normalised) activation
 
 Module tree and parameter names follow alonet/detr/transformer.py:22-440 (``encoder.layers.N.{self_attn, linear1,
 linear2, norm1, norm2}``, ``decoder.layers.N.{self_attn, multihead_attn, linear1, linear2, norm1..3}``, ``decoder.norm``)
-so reference checkpoints load unchanged.  No custom kernel is involved: this is the CPU-runnable plumbing model
-(BASELINE configs[0]).
+so reference checkpoints load unchanged.  On stock ops this is the CPU-runnable plumbing model (BASELINE configs[0]).  Under
+``ALO_ATTENTION=fused`` a post-norm model at d_model 256 with 8 heads runs its inference forward on the library instead
+(``Transformer._forward_fused``): batch-first activations from the flatten to the outputs, every projection a GEMM of
+``alo_hip.linear_auto``, attention with the key padding mask in ``alo_hip.attention``, each residual + LayerNorm in
+``alo_hip.add_layernorm``, the feed-forward block on the ``ffn256`` / ``ffn_f32`` ladder.  Everything outside that gate
+(pre-norm, ``attn_mask``, other widths, training, CPU, overridden hooks) takes the stock ops below unchanged.
 """
 import copy
 
 import torch
 import torch.nn.functional as F
 from torch import nn
+
+import alo_hip
+from alonet.transformers.fused_layers import _add_norm, _attention_ok, _cross_attention, _ffn, _fused_ok, _self_attention
 
 
 def _get_clones(module, n):
@@ -187,9 +194,66 @@ class Transformer(nn.Module):
         self.d_model = d_model
         self.nhead = nhead
 
+    def _fused_route_ok(self, x, mask, query_embed, pos_embed, kwargs):
+        """The gate of :meth:`_forward_fused` on the flattened batch-first activation ``x`` (B, HW, C): the switch, inference
+        outside autograd over the activation and every module the route reads, post-norm layers with the stock forwards and
+        hooks (a subclass that overrides one keeps the stock ops), the attention kernel's geometry, one dtype throughout."""
+        if not alo_hip.attention_routed() or "decoder_outputs" in kwargs:
+            return False
+        if any((k == "mask" or k.endswith("_mask")) and v is not None for k, v in kwargs.items()):
+            return False    # an attn_mask for the encoder (mask), the decoder (tgt_mask) or the cross-attention (memory_mask)
+        enc, dec = self.encoder, self.decoder
+        stock = (type(enc).forward is TransformerEncoder.forward and type(dec).forward is TransformerDecoder.forward
+                 and type(dec).decoder_forward is TransformerDecoder.decoder_forward
+                 and type(dec).pre_process_tgt is TransformerDecoder.pre_process_tgt
+                 and all(type(l).forward is TransformerEncoderLayer.forward and not l.normalize_before for l in enc.layers)
+                 and all(type(l).forward is TransformerDecoderLayer.forward and not l.normalize_before
+                         and type(l).decoder_layer_forward is TransformerDecoderLayer.decoder_layer_forward
+                         and type(l).pre_process_tgt is TransformerDecoderLayer.pre_process_tgt for l in dec.layers))
+        if not stock or len(enc.layers) == 0 or len(dec.layers) == 0 or (dec.return_intermediate and dec.norm is None):
+            return False
+        if mask.dtype != torch.bool or not _fused_ok(self, kwargs, x, mask, query_embed, pos_embed, self):
+            return False
+        mhas = [l.self_attn for l in enc.layers] + [m for l in dec.layers for m in (l.self_attn, l.multihead_attn)]
+        return (all(_attention_ok(m, x) for m in mhas) and query_embed.dtype == x.dtype and pos_embed.dtype == x.dtype
+                and all(p.dtype == x.dtype and p.device == x.device for p in self.parameters()))
+
+    def _forward_fused(self, x, mask, query_embed, pos, shape):
+        """The inference forward on the library: x, pos (B, HW, C) contiguous, mask (B, HW) bool -> the dict of :meth:`forward`,
+        with the shapes and strides the sequence-first stock route gives its outputs."""
+        bs, c, h, w = shape
+        enc, dec = self.encoder, self.decoder
+        qk_in = x + pos
+        for layer in enc.layers:
+            x = _add_norm(layer.norm1, _self_attention(layer.self_attn, qk_in, x, mask), x)
+            x, qk_in = _add_norm(layer.norm2, _ffn(layer.linear1, layer.activation, layer.linear2, x), x, pos=pos)
+        memory, key_in = x, qk_in           # the cross-attention's keys are memory + pos in every decoder layer
+        if enc.norm is not None:
+            memory = _add_norm(enc.norm, memory, None)
+            key_in = memory + pos
+        query_pos = query_embed.unsqueeze(0).expand(bs, -1, -1).contiguous()
+        tgt, tgt_q, hs = torch.zeros_like(query_pos), query_pos, []
+        for layer in dec.layers:
+            tgt, tgt_q = _add_norm(layer.norm1, _self_attention(layer.self_attn, tgt_q, tgt), tgt, pos=query_pos)
+            cross = _cross_attention(layer.multihead_attn, tgt_q, key_in, memory, mask)
+            tgt = _add_norm(layer.norm2, cross, tgt)
+            tgt, tgt_q = _add_norm(layer.norm3, _ffn(layer.linear1, layer.activation, layer.linear2, tgt), tgt, pos=query_pos)
+            if dec.return_intermediate:
+                hs.append(_add_norm(dec.norm, tgt, None))
+        if not dec.return_intermediate:
+            hs = [tgt if dec.norm is None else _add_norm(dec.norm, tgt, None)]
+        # (layers, B, Q, C) and (B, C, H, W) as views of sequence-first storage: what the stock route hands on
+        return {"hs": torch.stack(hs).transpose(1, 2).contiguous().transpose(1, 2),
+                "memory": memory.transpose(0, 1).contiguous().permute(1, 2, 0).view(bs, c, h, w)}
+
     def forward(self, src, mask, query_embed, pos_embed, **kwargs):
         """src (B,C,H,W), mask (B,H,W) bool, query_embed (Q,C), pos_embed (B,C,H,W) -> dict(hs (layers,B,Q,C), memory)."""
         bs, c, h, w = src.shape
+        if alo_hip.attention_routed() and src.is_cuda:
+            x = src.flatten(2).transpose(1, 2)
+            if self._fused_route_ok(x, mask, query_embed, pos_embed, kwargs):
+                return self._forward_fused(x.contiguous(), mask.flatten(1).contiguous(), query_embed,
+                                           pos_embed.flatten(2).transpose(1, 2).contiguous(), (bs, c, h, w))
         src = src.flatten(2).permute(2, 0, 1)
         pos_embed = pos_embed.flatten(2).permute(2, 0, 1)
         query_embed = query_embed.unsqueeze(1).repeat(1, bs, 1)

@@ -144,6 +144,12 @@ int upsample_flow_f32(const void* flow, const void* mask, void* out, int BQ, int
 int upsample_flow_grad_f32(const void* flow_and_grad, const void* mask, void* out, int BQ, int C, int h, int w, hipStream_t stream,
                            const char* what);
 
+// attention.hip: ALO_BLOCK_ATTENTION of alo_encoder_block on checked arguments (alo_encoder_block.h): q (batch, S, .) and k (batch, F, .)
+// with a row pitch of `pitch` elements (256, or 512 for the two halves of a packed [q; k] matrix), v (batch, F, 256), mask (batch, F)
+// or NULL, out (batch, S, 256); dtype ALO_BF16, ALO_F16 or ALO_F32.
+int attention_block(const void* q, const void* k, const void* v, const void* mask, void* out, int batch, int S, int F, int pitch,
+                    float scale, int dtype, hipStream_t stream, const char* what);
+
 // relu x residual -> the four instantiations of a launcher template: ALO_RELU_RES(fn, first, relu, residual, args...) calls
 // fn<first, relu != 0, residual != nullptr>(args...)
 #define ALO_RELU_RES(fn, first, relu, residual, ...)                                                                          \

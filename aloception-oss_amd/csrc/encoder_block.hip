@@ -683,6 +683,62 @@ int decoder_block(const void* attn_out, const void* wo_packed, const void* bo, c
     return rows32 ? launch_decoder_block<32, false>(a, cus, stream) : launch_decoder_block<64, false>(a, cus, stream);
 }
 
+// ALO_BLOCK_ATTENTION (and ALO_BLOCK_PACKED_QK): dense attention on the entry point's pointers, checked by name; the kernel is
+// attention.hip's
+int attention_flagged(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b, const void* src,
+                      const void* w1_packed, const void* b1, const void* w2_packed, const void* b2, const void* norm2_w,
+                      const void* norm2_b, void* src_out, const void* pos, const void* padding_mask, const void* wv_packed, const void* bv,
+                      const void* wq_packed, const void* bq, void* value_hm, void* offsets_logits, int batch, int S, int F, float eps1,
+                      float eps2, int dtype, int flags, hipStream_t stream) {
+    const char* what = "alo_encoder_block";
+    constexpr int kAttn = ALO_BLOCK_ATTENTION | ALO_BLOCK_PACKED_QK;
+    constexpr int kOthers = ALO_BLOCK_NO_FFN | ALO_BLOCK_DECODER_NEXT | ALO_BLOCK_TILE_32 | ALO_BLOCK_TILE_64;
+    ALO_REQUIRE(!(flags & ~(kAttn | kOthers)), ALO_ERR_UNSUPPORTED,
+                "%s: dtype carries 0x%x above its low byte: ALO_BLOCK_NO_FFN, ALO_BLOCK_DECODER_NEXT, ALO_BLOCK_TILE_32 / _64, "
+                "ALO_BLOCK_ATTENTION (with ALO_BLOCK_PACKED_QK) or nothing", what, flags & ~(kAttn | kOthers));
+    ALO_REQUIRE(flags & ALO_BLOCK_ATTENTION, ALO_ERR_INVALID_ARGUMENT, "%s: dtype carries ALO_BLOCK_PACKED_QK without ALO_BLOCK_ATTENTION",
+                what);
+    ALO_REQUIRE(!(flags & kOthers), ALO_ERR_INVALID_ARGUMENT,
+                "%s: dtype carries ALO_BLOCK_ATTENTION together with a chain or tile flag (0x%x): attention is a call of its own", what,
+                flags & kOthers);
+    const bool packed = (flags & ALO_BLOCK_PACKED_QK) != 0;
+    const char* flag = "ALO_BLOCK_ATTENTION";
+    ALO_REQUIRE(dtype == ALO_BF16 || dtype == ALO_F16 || dtype == ALO_F32, ALO_ERR_UNSUPPORTED,
+                "%s: %s takes ALO_BF16, ALO_F16 or ALO_F32 (dtype %d)", what, flag, dtype);
+    const struct { const void* p; const char* name; bool wanted; } ptrs[] = {
+        {attn_out, "attn_out", true}, {wo_packed, "wo_packed", false}, {bo, "bo", false}, {norm1_w, "norm1_w", false},
+        {norm1_b, "norm1_b", false}, {src, "src", true}, {w1_packed, "w1_packed", false}, {b1, "b1", false}, {w2_packed, "w2_packed", false},
+        {b2, "b2", false}, {norm2_w, "norm2_w", false}, {norm2_b, "norm2_b", false}, {src_out, "src_out", true}, {pos, "pos", true},
+        {wv_packed, "wv_packed", false}, {bv, "bv", false}, {wq_packed, "wq_packed", false}, {bq, "bq", false},
+        {value_hm, "value_hm", false}, {offsets_logits, "offsets_logits", false}};   // padding_mask: either way
+    for (const auto& a : ptrs) {
+        ALO_REQUIRE(!a.wanted || a.p, ALO_ERR_INVALID_ARGUMENT, "%s: %s is NULL, %s needs it", what, a.name, flag);
+        ALO_REQUIRE(a.wanted || !a.p, ALO_ERR_INVALID_ARGUMENT, "%s: %s must be NULL with %s", what, a.name, flag);
+    }
+    ALO_REQUIRE(batch > 0 && S > 0 && F > 0, ALO_ERR_INVALID_ARGUMENT,
+                "%s: batch, S (queries) and F (keys) must be positive (batch=%d S=%d F=%d)", what, batch, S, F);
+    ALO_REQUIRE(eps1 > 0.f, ALO_ERR_INVALID_ARGUMENT, "%s: eps1 is the softmax scale with %s and must be positive (%g)", what, flag,
+                (double)eps1);   // also refuses NaN
+    ALO_REQUIRE(eps2 == 0.f, ALO_ERR_INVALID_ARGUMENT, "%s: eps2 must be 0 with %s (%g)", what, flag, (double)eps2);
+    const size_t es = dtype == ALO_F32 ? 4 : 2, pitch = packed ? 512 : 256;
+    ALO_REQUIRE(!packed || F == S, ALO_ERR_INVALID_ARGUMENT, "%s: ALO_BLOCK_PACKED_QK needs F == S (S=%d F=%d)", what, S, F);
+    ALO_REQUIRE(!packed || (const char*)pos == (const char*)src + 256 * es, ALO_ERR_INVALID_ARGUMENT,
+                "%s: ALO_BLOCK_PACKED_QK needs pos == src + 256 elements (the halves of one (rows, 512) matrix)", what);
+    ALO_REQUIRE(aligned16(src, pos, attn_out, src_out), ALO_ERR_INVALID_ARGUMENT, "%s: pointers must be 16-byte aligned", what);
+    // the bytes each operand spans: a packed q or k ends 256 elements into its last row
+    const size_t qrows = (size_t)batch * S, krows = (size_t)batch * F;
+    const size_t qbytes = ((qrows - 1) * pitch + 256) * es, kbytes = ((krows - 1) * pitch + 256) * es, vbytes = krows * 256 * es,
+                 obytes = qrows * 256 * es;
+    constexpr size_t kSlabLimit = (size_t)1 << 31;
+    ALO_REQUIRE(qbytes < kSlabLimit && kbytes < kSlabLimit && vbytes < kSlabLimit && obytes < kSlabLimit, ALO_ERR_UNSUPPORTED,
+                "%s: %s: q, k, v and out must each be below 2 GiB (batch=%d S=%d F=%d)", what, flag, batch, S, F);
+    const struct { const void* p; size_t bytes; } ins[] = {{src, qbytes}, {pos, kbytes}, {attn_out, vbytes}, {padding_mask, krows}};
+    for (const auto& i : ins)
+        ALO_REQUIRE(!i.p || (const char*)src_out + obytes <= (const char*)i.p || (const char*)i.p + i.bytes <= (const char*)src_out,
+                    ALO_ERR_INVALID_ARGUMENT, "%s: src_out (the attention output) overlaps an input", what);
+    return attention_block(src, pos, attn_out, padding_mask, src_out, batch, S, F, (int)pitch, eps1, dtype, stream, what);
+}
+
 }  // namespace
 }  // namespace alo
 
@@ -694,7 +750,11 @@ extern "C" int alo_encoder_block(const void* attn_out, const void* wo_packed, co
                                  const void* wv_packed, const void* bv, const void* wq_packed, const void* bq, void* value_hm,
                                  void* offsets_logits, int batch, int S, int F, float eps1, float eps2, int dtype, void* stream) {
     const char* what = "alo_encoder_block";
-    // ALO_BLOCK_* ride above the dtype's low byte (a negative dtype is no flagged one): the decoder's chains
+    // ALO_BLOCK_* ride above the dtype's low byte (a negative dtype is no flagged one): dense attention, the decoder's chains
+    if (dtype > 0 && (dtype & (ALO_BLOCK_ATTENTION | ALO_BLOCK_PACKED_QK)))
+        return attention_flagged(attn_out, wo_packed, bo, norm1_w, norm1_b, src, w1_packed, b1, w2_packed, b2, norm2_w, norm2_b, src_out, pos,
+                                 padding_mask, wv_packed, bv, wq_packed, bq, value_hm, offsets_logits, batch, S, F, eps1, eps2,
+                                 dtype & 0xff, dtype & ~0xff, static_cast<hipStream_t>(stream));
     if (dtype > 0 && (dtype & ~0xff))
         return decoder_block(attn_out, wo_packed, bo, norm1_w, norm1_b, src, w1_packed, b1, w2_packed, b2, norm2_w, norm2_b, src_out, pos,
                              padding_mask, wv_packed, bv, wq_packed, bq, value_hm, offsets_logits, batch, S, F, eps1, eps2, dtype & 0xff,

@@ -17,7 +17,7 @@
  * Part of libalo_hotpath.so, under its one ABI number (alo_abi_version()), and bound to the conventions of alo_hotpath.h: device
  * pointers on the current HIP device, 16-byte aligned, work enqueued on `stream` (a hipStream_t as void*), no allocation, no
  * synchronisation, ALO_OK or an alo_status_t with a message in alo_last_error(), argument errors detected before anything is
- * enqueued.  Forward only, bf16 only, d_model = 256, 8 heads of 32 channels.
+ * enqueued.  Forward only, bf16 only (ALO_BLOCK_ATTENTION: also fp16 and fp32), d_model = 256, 8 heads of 32 channels.
  */
 #ifndef ALO_ENCODER_BLOCK_H
 #define ALO_ENCODER_BLOCK_H
@@ -62,11 +62,35 @@ extern "C" {
  * heights at once, a height without a chain, a pointer that is NULL or non-NULL against the lists above
  * (ALO_ERR_INVALID_ARGUMENT), a flag with another dtype than ALO_BF16 (ALO_ERR_UNSUPPORTED).  Without a flag the call is the
  * encoder's, as above.
+ *
+ * Dense multi-head attention with a key padding mask: the step between chain B's projections and chain A (or an out_proj), on the
+ * same entry point because it consumes the one's outputs and produces the other's input.  bf16, fp16 or fp32.
+ *   ALO_BLOCK_ATTENTION:  src_out = softmax(q k^T * eps1 + mask) v per head, 8 heads of 32 channels (head h: columns 32 h .. 32 h + 31)
+ *     src      q (batch, S, .), S queries;   pos  k (batch, F, .), F keys (any positive S, F: self- and cross-attention).  Row pitch
+ *              of q and k: 256 elements
+ *     attn_out v (batch, F, 256);   padding_mask (batch, F) uint8 or NULL, non-zero = the key is ignored (key_padding_mask)
+ *     src_out  out (batch, S, 256), fully overwritten: the un-projected attention output chain A and an out_proj take
+ *     eps1     the softmax scale, > 0 (1 / sqrt(32) for the usual attention), applied to the product (in fp32; in fp64 for fp32
+ *              operands), never to the 16-bit operands; eps2 must be 0
+ *     Every other pointer must be NULL.
+ *   ALO_BLOCK_PACKED_QK (with ALO_BLOCK_ATTENTION only): q and k are the two halves of chain B's (rows, 512) [q; k] matrix: row
+ *     pitch 512 elements, pos == src + 256 elements, F == S.
+ *   A key past F does not exist: its memory is not read.  A query all of whose keys are masked gets NaN in its 256 outputs (what
+ *   nn.MultiheadAttention returns); other queries and images are unaffected.  The 16-bit flavours accumulate in fp32 and round the
+ *   probabilities to the storage type before the second product; fp32 operands are widened to fp64 and both products, the
+ *   exponentials and the sums run in fp64, so the fp32 result carries one rounding.
+ *   Refused before anything is enqueued, the message naming the flag or the argument: ALO_BLOCK_PACKED_QK without
+ *   ALO_BLOCK_ATTENTION, with F != S or with another pos; ALO_BLOCK_ATTENTION with a chain or tile flag; a wanted pointer that is
+ *   NULL or another that is not; eps1 <= 0, eps2 != 0; non-positive sizes; pointers off a 16-byte boundary; src_out overlapping an
+ *   input (ALO_ERR_INVALID_ARGUMENT); any other bit above the low byte, a dtype outside the three, a q, k, v or out of 2 GiB or
+ *   more (ALO_ERR_UNSUPPORTED).
  */
 #define ALO_BLOCK_NO_FFN 0x100
 #define ALO_BLOCK_DECODER_NEXT 0x200
 #define ALO_BLOCK_TILE_32 0x400
 #define ALO_BLOCK_TILE_64 0x800
+#define ALO_BLOCK_ATTENTION 0x2000
+#define ALO_BLOCK_PACKED_QK 0x8000
 
 int alo_encoder_block(const void* attn_out, const void* wo_packed, const void* bo, const void* norm1_w, const void* norm1_b,
                       const void* src, const void* w1_packed, const void* b1, const void* w2_packed, const void* b2,
