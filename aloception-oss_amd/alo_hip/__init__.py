@@ -978,13 +978,37 @@ def conv1x1_strided(x, weight2d, bias, stride, relu=False):
     return y
 
 
-# ---- a layer1 bottleneck's last 1x1 convolution with its row-local neighbours (alo_conv1x1_nhwc with a chain buffer) -----------------
+# ---- a bottleneck's last 1x1 convolution with its row-local neighbours (alo_conv1x1_nhwc with a chain buffer) ------------------------
 CONV1X1_CHAIN, CONV1X1_CHAIN_DOWN = 2, 4   # ALO_CONV1X1_CHAIN* of include/alo_hotpath.h
+
+# The two shape families of the entry point, keyed by conv3's input channels: conv3's output channels, the downsample convolution's
+# input channels and the strides it may carry, the widths of the next convolution (csrc/conv1x1_chain.hip, csrc/conv1x1_chain_l2.hip).
+_CHAIN_FAMILIES = {64: (256, 64, (1,), (64, 128)), 128: (512, 256, (1, 2), (128,))}
+
+# The layer2 forms (down, next width) that Bottleneck._chain routes: the ones whose launch was measured faster than the launches it
+# stands in for (docs/experiments.md, "Bottleneck chain for layer2").  The others are built and tested and reached through
+# conv1x1_chain only.
+CHAIN_LAYER2_ROUTED = frozenset({(True, 128), (False, 128), (True, 0)})
+
+
+def _chain_knob():
+    return os.environ.get("ALO_BOTTLENECK_CHAIN", "on").lower()
 
 
 def bottleneck_chain_enabled():
     """``ALO_BOTTLENECK_CHAIN=off`` (read per call) keeps the bottlenecks on their separate launches: for tests and profiling."""
-    return os.environ.get("ALO_BOTTLENECK_CHAIN", "on").lower() not in ("off", "0")
+    return _chain_knob() not in ("off", "0")
+
+
+def bottleneck_chain_routed(channels, down, n2):
+    """Whether ``Bottleneck._chain`` sends a bottleneck whose conv3 has ``channels`` inputs through the chain launch, with its
+    downsample convolution (``down``) and a next convolution of ``n2`` outputs (0: none).  ``ALO_BOTTLENECK_CHAIN=layer1`` (read per
+    call) keeps ``layer2`` on its separate launches, which is the routing before ``layer2`` had a chain: for A/B runs and tests."""
+    if not bottleneck_chain_enabled():
+        return False
+    if channels == 64:
+        return True
+    return channels == 128 and _chain_knob() != "layer1" and (bool(down), int(n2)) in CHAIN_LAYER2_ROUTED
 
 
 def _chain_map(t, channels):
@@ -997,49 +1021,75 @@ def _chain_vectors(*pairs):
                and b is not None and b.dtype == torch.bfloat16 and tuple(b.shape) == (cout,) for w, b, cout, cin in pairs)
 
 
+def _chain_stride(down):
+    return 1 if down is None or len(down) < 4 else int(down[3])
+
+
 def conv1x1_chain_supported(mid, conv3, identity=None, down=None, nxt=None):
-    """What :func:`conv1x1_chain` takes, with grad mode off: channels-last bf16 CUDA maps, ``mid`` (N, 64, H, W),
-    ``conv3 = (w, b)`` with 256 output channels, either ``identity`` (N, 256, H, W) or ``down = (x0, wd, bd)`` with ``x0``
-    (N, 64, H, W) and 256 output channels, and, if given, ``nxt = (w1, b1)`` with 256 input and 64 or 128 output channels; weights
-    (Cout, Cin, 1, 1) or (Cout, Cin), every bias present."""
+    """What :func:`conv1x1_chain` takes, with grad mode off: channels-last bf16 CUDA maps in one of two shape families.  ``layer1``:
+    ``mid`` (N, 64, H, W), ``conv3 = (w, b)`` with 256 output channels, either ``identity`` (N, 256, H, W) or ``down = (x0, wd, bd)``
+    with ``x0`` (N, 64, H, W), and, if given, ``nxt = (w1, b1)`` with 256 input and 64 or 128 output channels.  ``layer2``: ``mid``
+    (N, 128, Ho, Wo), 512 output channels, ``identity`` (N, 512, Ho, Wo) or ``down = (x0, wd, bd[, stride])`` with ``x0``
+    (N, 256, H, W), stride 1 or 2 and Ho = (H - 1) // stride + 1, ``nxt`` 512 -> 128.  Weights (Cout, Cin, 1, 1) or (Cout, Cin),
+    every bias present."""
     if (identity is None) == (down is None) or not bottleneck_chain_enabled() or torch.is_grad_enabled():
         return False
-    other = identity if down is None else down[0]
-    if not (_chain_map(mid, 64) and _chain_map(other, 256 if down is None else 64) and other.shape[0] == mid.shape[0]
-            and other.shape[2:] == mid.shape[2:] and other.device == mid.device):
+    if mid.dim() != 4 or mid.shape[1] not in _CHAIN_FAMILIES:
         return False
-    pairs = [(*conv3, 256, 64)] + ([] if down is None else [(down[1], down[2], 256, 64)])
+    cin = mid.shape[1]
+    cout, cin0, strides, widths = _CHAIN_FAMILIES[cin]
+    stride = _chain_stride(down)
+    if stride not in strides:
+        return False
+    other = identity if down is None else down[0]
+    if not (_chain_map(mid, cin) and _chain_map(other, cout if down is None else cin0) and other.shape[0] == mid.shape[0]
+            and tuple((d - 1) // stride + 1 for d in other.shape[2:]) == tuple(mid.shape[2:]) and other.device == mid.device):
+        return False
+    pairs = [(*conv3, cout, cin)] + ([] if down is None else [(down[1], down[2], cout, cin0)])
     if nxt is not None:
-        if nxt[0].shape[0] not in (64, 128):
+        if nxt[0].shape[0] not in widths:
             return False
-        pairs.append((*nxt, nxt[0].shape[0], 256))
+        pairs.append((*nxt, nxt[0].shape[0], cout))
     return _chain_vectors(*pairs) and fusable(mid, other, *[t for w, b, _, _ in pairs for t in (w, b)])
 
 
 def conv1x1_chain(mid, conv3, identity=None, down=None, nxt=None):
-    """``y = relu(conv1x1(mid, *conv3) + identity)`` with ``identity`` given or ``conv1x1(x0, wd, bd)`` for ``down = (x0, wd, bd)``,
-    and with ``nxt = (w1, b1)`` also ``z = relu(conv1x1(y, w1, b1))``, in one launch; bit for bit the :func:`linear_shortk` launches
-    it stands in for (include/alo_hotpath.h, alo_conv1x1_nhwc with a chain buffer).  -> (y, z | None), channels-last."""
-    _no_autograd("conv1x1_chain", mid, *conv3, identity, *(down or ()), *(nxt or ()))
+    """``y = relu(conv1x1(mid, *conv3) + identity)`` with ``identity`` given or ``conv1x1(x0, wd, bd, stride)`` for
+    ``down = (x0, wd, bd[, stride])``, and with ``nxt = (w1, b1)`` also ``z = relu(conv1x1(y, w1, b1))``, in one launch; bit for bit
+    the launches it stands in for (include/alo_hotpath.h, alo_conv1x1_nhwc with a chain buffer).  -> (y, z | None), channels-last."""
+    _no_autograd("conv1x1_chain", mid, *conv3, identity, *((down or ())[:3]), *(nxt or ()))
     if not conv1x1_chain_supported(mid, conv3, identity, down, nxt):
         raise RuntimeError("conv1x1_chain: needs channels-last bf16 CUDA maps outside autograd, a 64 -> 256 convolution, an identity or "
-                           "a 64 -> 256 downsample convolution, a next convolution 256 -> 64 or 128, and ALO_BOTTLENECK_CHAIN not off")
-    n, _, h, w_ = mid.shape
+                           "a 64 -> 256 downsample convolution, a next convolution 256 -> 64 or 128 (or 128 -> 512, a 256 -> 512 "
+                           "downsample convolution of stride 1 or 2, a next convolution 512 -> 128), and ALO_BOTTLENECK_CHAIN not off")
+    n, cin, h, w_ = mid.shape
+    cout, cin0 = _CHAIN_FAMILIES[cin][:2]
+    stride = _chain_stride(down)
     n2 = 0 if nxt is None else nxt[0].shape[0]
-    parts = [*conv3, *(down[1:] if down is not None else ()), *(nxt or ())]
+    parts = [*conv3, *(down[1:3] if down is not None else ()), *(nxt or ())]
+
+    def chain_buffer():
+        # layer2: the matrices the kernel streams (Wd, W1) go in MFMA fragment order, W3 (resident in registers) as it is (alo_hotpath.h)
+        flat = [p.reshape(-1) for p in parts]
+        if cin == 128:
+            for i in range(2, len(parts), 2):
+                flat[i] = _pack_mfma_b(parts[i].reshape(parts[i].shape[0], -1).contiguous()).reshape(-1)
+        return torch.cat(flat)
+
     # the chain buffer rides on the convolution's (cached, folded) weight and is rebuilt when any part changes
-    buf = derived(conv3[0], f"chain/{down is not None}/{n2}", parts, lambda: torch.cat([p.reshape(-1) for p in parts]))
+    buf = derived(conv3[0], f"chain/{down is not None}/{n2}", parts, chain_buffer)
     rows = n * h * w_
-    out = torch.empty(rows * (256 + n2), dtype=mid.dtype, device=mid.device)   # y, then z: one buffer (alo_hotpath.h)
+    out = torch.empty(rows * (cout + n2), dtype=mid.dtype, device=mid.device)   # y, then z: one buffer (alo_hotpath.h)
     other = identity if down is None else down[0]
-    # what the result needs: mid, the identity or x0, y (+ z)
-    nbytes = 2.0 * rows * (64 + (256 if down is None else 64) + 256 + n2)
-    flops = 2.0 * rows * 256 * (64 * (1 + (down is not None)) + n2)
-    tag = f"conv1x1_chain/{'down' if down is not None else 'res'}{f'+next{n2}' if n2 else ''}"
+    # what the result needs: mid, the identity or the kept pixels of x0, y (+ z)
+    nbytes = 2.0 * rows * (cin + (cout if down is None else cin0) + cout + n2)
+    flops = 2.0 * rows * cout * (cin + (cin0 if down is not None else 0) + n2)
+    form = f"{'down' if down is not None else 'res'}{f'+next{n2}' if n2 else ''}"
+    tag = f"conv1x1_chain/{form}" if cin == 64 else f"bottleneck_chain/C={cin}/{form}"
     _launch("alo_conv1x1_nhwc", mid.device, tag, nbytes, flops, mid, buf, CONV1X1_CHAIN | (CONV1X1_CHAIN_DOWN if down is not None else 0) | n2,
-            None, other, out, n, h, w_, 64, 256, 1, 1, ALO_BF16)
-    y = out[:rows * 256].view(n, h, w_, 256).permute(0, 3, 1, 2)
-    z = None if nxt is None else out[rows * 256:].view(n, h, w_, n2).permute(0, 3, 1, 2)
+            None, other, out, n, other.shape[2], other.shape[3], cin, cout, stride, 1, ALO_BF16)
+    y = out[:rows * cout].view(n, h, w_, cout).permute(0, 3, 1, 2)
+    z = None if nxt is None else out[rows * cout:].view(n, h, w_, n2).permute(0, 3, 1, 2)
     return y, z
 
 

@@ -163,29 +163,37 @@ class Bottleneck(nn.Module):
     def _chain(self, x, mid, nxt):
         """The operands of ``alo_hip.conv1x1_chain`` for this block's conv3 — with its downsample convolution, and with ``nxt``'s conv1
         when that block can take the hand-off — or None when the separate launches run: grad mode on, fp32 / fp16, other widths (only
-        layer1 has a 64 -> 256 conv3), a strided or dilated neighbour, or nothing to fold in (no downsample and no ``nxt``).
+        layer1 has a 64 -> 256 conv3 and only layer2 a 128 -> 512 one), a dilated neighbour or one with a stride the kernel does not
+        address, nothing to fold in (no downsample and no ``nxt``), or a form that was not measured to win
+        (``alo_hip.bottleneck_chain_routed``).
         Also None while the module's ``conv_bn`` is swapped for another function: every convolution of the body goes through that
         name, callers rely on it to see or re-route them all, and the chain is bit for bit three calls of the module's own only."""
-        def pointwise(conv, bn):
-            return (isinstance(bn, FrozenBatchNorm2d) and conv.bias is None and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+        def pointwise(conv, bn, strides=((1, 1),)):
+            return (isinstance(bn, FrozenBatchNorm2d) and conv.bias is None and conv.kernel_size == (1, 1) and tuple(conv.stride) in strides
                     and conv.padding == (0, 0) and conv.groups == 1)
 
         if not (conv_bn is _conv_bn and alo_hip.bottleneck_chain_enabled() and not torch.is_grad_enabled()
                 and x.is_cuda and x.dtype == torch.bfloat16 and pointwise(self.conv3, self.bn3)
                 and alo_hip.fusable(x, mid, self.conv3, self.bn3, self.downsample)):
             return None
+        channels = self.conv3.in_channels
         down = identity = head = None
         if self.downsample is None:
             identity = x
-        elif len(self.downsample) == 2 and pointwise(self.downsample[0], self.downsample[1]):
-            down = (x, *folded_conv_bn(self.downsample[0], self.downsample[1]))
+        elif len(self.downsample) == 2 and pointwise(self.downsample[0], self.downsample[1], ((1, 1), (2, 2))):
+            # the stage's stride rides on the downsample convolution: the kernel's tile loader addresses the kept pixels of x
+            down = (x, *folded_conv_bn(self.downsample[0], self.downsample[1]), self.downsample[0].stride[0])
         else:
             return None
         if isinstance(nxt, Bottleneck) and pointwise(nxt.conv1, nxt.bn1) and alo_hip.fusable(x, nxt.conv1, nxt.bn1):
             head = folded_conv_bn(nxt.conv1, nxt.bn1)
-            if head[0].shape[0] not in (64, 128):
+            if head[0].shape[0] not in ((64, 128) if channels == 64 else (128,)):
                 head = None
+        if head is not None and not alo_hip.bottleneck_chain_routed(channels, down is not None, head[0].shape[0]):
+            head = None   # the form without the hand-off may still be routed
         if down is None and head is None:
+            return None
+        if not alo_hip.bottleneck_chain_routed(channels, down is not None, 0 if head is None else head[0].shape[0]):
             return None
         args = (mid, folded_conv_bn(self.conv3, self.bn3), identity, down, head)
         return args if alo_hip.conv1x1_chain_supported(*args) else None

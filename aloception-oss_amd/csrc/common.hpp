@@ -110,6 +110,10 @@ int linear_shortk_gather(const void* x, const void* weight, const void* bias, co
 // conv1x1_chain.hip: alo_conv1x1_nhwc with a chain buffer on checked arguments (w_chain and the y-then-z output: alo_hotpath.h);
 // res_or_x0 is the (M, 256) identity, or with `down` the (M, 64) input of the downsample convolution; n2 = 0, 64 or 128.
 int conv1x1_chain(const void* mid, const void* w_chain, const void* res_or_x0, void* y, long M, bool down, int n2, hipStream_t stream);
+// conv1x1_chain_l2.hip: the same at layer2's widths, mid (M, 128) -> y (M, 512); res_or_x0 is the (M, 512) identity, or with `down` the
+// (N, H, W, 256) map whose pixels `gather` picks as the downsample convolution's input rows; n2 = 0 or 128.
+int conv1x1_chain_l2(const void* mid, const void* w_chain, const void* res_or_x0, void* y, long M, bool down, int n2, const RowGather& gather,
+                     hipStream_t stream);
 
 // conv_f32.hip: the fp32 flavour of alo_conv3x3_nhwc on checked arguments (w_split and image_mag: alo_hotpath.h); image_mag holds N words.
 int conv3x3_f32(const void* x, const void* w_split, const void* bias, void* y, void* image_mag, int N, int H, int W, int Cin, int Cout,

@@ -173,9 +173,12 @@ extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is
     if (weight_is_packed & ALO_CONV1X1_CHAIN) {   // conv1x1_chain.hip: conv3 (+ downsample) (+ the next conv1) of a layer1 bottleneck
         const bool down = (weight_is_packed & ALO_CONV1X1_CHAIN_DOWN) != 0;
         const int n2 = weight_is_packed & ~(ALO_CONV1X1_CHAIN | ALO_CONV1X1_CHAIN_DOWN);
-        ALO_REQUIRE(dtype == ALO_BF16 && Cin == 64 && Cout == 256 && stride == 1 && relu && (n2 == 0 || n2 == 64 || n2 == 128),
-                    ALO_ERR_UNSUPPORTED,
-                    "alo_conv1x1_nhwc: a chain buffer needs bf16, Cin = 64, Cout = 256, stride 1, relu and a next width of 0, 64 or 128 "
+        const bool l1 = Cin == 64 && Cout == 256 && stride == 1 && (n2 == 0 || n2 == 64 || n2 == 128);
+        // conv1x1_chain_l2.hip: a layer2 bottleneck, whose downsample convolution (256 input channels) may carry the stage's stride
+        const bool l2 = Cin == 128 && Cout == 512 && (stride == 1 || (stride == 2 && down)) && (n2 == 0 || n2 == 128);
+        ALO_REQUIRE(dtype == ALO_BF16 && relu && (l1 || l2), ALO_ERR_UNSUPPORTED,
+                    "alo_conv1x1_nhwc: a chain buffer needs bf16, Cin = 64, Cout = 256, stride 1, relu and a next width of 0, 64 or 128, "
+                    "or Cin = 128, Cout = 512, stride 1 (2 with _DOWN) and a next width of 0 or 128 "
                     "(dtype %d Cin=%d Cout=%d stride=%d relu=%d next=%d)", dtype, Cin, Cout, stride, relu, n2);
         ALO_REQUIRE(residual && !bias, ALO_ERR_INVALID_ARGUMENT,
                     "alo_conv1x1_nhwc: a chain buffer carries its biases (bias must be NULL) and needs the identity, or the downsample "
@@ -183,12 +186,15 @@ extern "C" int alo_conv1x1_nhwc(const void* x, const void* weight, int weight_is
         ALO_REQUIRE((M + 63) / 64 < (1L << 31), ALO_ERR_UNSUPPORTED, "alo_conv1x1_nhwc: too many output pixels");
         // a tile's outputs are written while other tiles' inputs are still to be read: y-then-z may overlap neither input
         const size_t rows = (size_t)M;
-        const struct { const void* p; size_t bytes; } out = {y, rows * 2 * (256 + (size_t)n2)},
-                                                      ins[] = {{x, rows * 128}, {residual, rows * (down ? 128 : 512)}};
+        // (with _DOWN at Cin = 128 the second input is x0's whole (N, H, W, 256) map)
+        const size_t other = !down ? rows * 2 * (size_t)Cout : l1 ? rows * 128 : (size_t)N * H * W * 512;
+        const struct { const void* p; size_t bytes; } out = {y, rows * 2 * ((size_t)Cout + (size_t)n2)},
+                                                      ins[] = {{x, rows * 2 * (size_t)Cin}, {residual, other}};
         for (const auto& i : ins)
             ALO_REQUIRE((const char*)out.p + out.bytes <= (const char*)i.p || (const char*)i.p + i.bytes <= (const char*)out.p,
                         ALO_ERR_INVALID_ARGUMENT, "alo_conv1x1_nhwc: the output of a chain overlaps an input");
-        return conv1x1_chain(x, weight, residual, y, M, down, n2, static_cast<hipStream_t>(stream));
+        if (l1) return conv1x1_chain(x, weight, residual, y, M, down, n2, static_cast<hipStream_t>(stream));
+        return conv1x1_chain_l2(x, weight, residual, y, M, down, n2, row_gather(stride, Ho, Wo, H, W), static_cast<hipStream_t>(stream));
     }
     const RowGather gather = row_gather(stride, Ho, Wo, H, W);
     if (dtype == ALO_F32) {   // gemm_f32.hip behind the same row addressing

@@ -433,6 +433,18 @@ int alo_linear_packed(const void* x, const void* w_packed, const void* bias, con
  * N H W (256 + N2) elements, which may overlap neither x nor residual).  Every intermediate is rounded to bf16 where the separate
  * launches round it, so y and z are bit for bit what alo_linear_shortk gives for (x0, Wd, bd), then (x, W3, b3, relu, residual =
  * that), then (y, W1, b1, relu).  The (N, H, W, 256) identity of _DOWN is never written, and y is not read back to make z.
+ *
+ * The same flags with Cin = 128, Cout = 512 and N2 = 0 or 128 are the chain of a layer2 bottleneck (csrc/conv1x1_chain_l2.hip):
+ *     y = relu(x W3^T + b3 + identity)        identity = residual (N, Ho, Wo, 512), or with _DOWN bf16(x0 Wd^T + bd), Wd (512, 256),
+ *                                             where x0 is the pixel (n, stride yo, stride xo) of residual, an (N, H, W, 256) map
+ *     z = relu(y W1^T + b1)                   with N2 = 128: W1 (128, 512)
+ * With _DOWN stride may be 1 or 2 (without it 1 only) and H, W describe x0's map; x is (N, Ho, Wo, 128) and y receives y
+ * (N, Ho, Wo, 512) then z (N, Ho, Wo, 128), with Ho = (H - 1) / stride + 1 and Wo likewise.  The kept pixels of x0 are addressed by
+ * the kernel's tile loader, as the strided convolution above addresses them; no gathered copy is made.  The buffer holds the parts in
+ * the same order, W3 (512, 128) row-major, b3 (512), [Wd, bd (512)], [W1, b1 (128)], with the two matrices the kernel streams, Wd and
+ * W1, in alo_pack_mfma_b order.  y and z are bit for bit what this entry point gives for (x0, Wd, bd, stride) with unpacked weights,
+ * then alo_linear_shortk for (x, W3, b3, relu, residual = that), then alo_linear_packed for (y, W1 packed, b1, relu).  The output
+ * may overlap neither x nor any part of x0's map.  Any other Cin, Cout, N2 or stride with a chain buffer is ALO_ERR_UNSUPPORTED.
  */
 #define ALO_CONV1X1_CHAIN 2
 #define ALO_CONV1X1_CHAIN_DOWN 4
