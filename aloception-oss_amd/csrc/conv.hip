@@ -18,6 +18,7 @@
 //     Cin == Cout == 64 at stride 1 goes to conv3x3_c64_kernel, the same split on four waves with the weights kept in registers.
 //   * stride 1 with Cout >= 128 and no split-K goes to conv3x3_pipe_kernel: this arithmetic on four waves per halo, with the LDS reads
 //     and the weight requests issued ahead of the MFMAs that use them.
+//   * stride 2 with Cout >= 128 and no split-K goes to conv3x3_pipe_s2_kernel: the same loop over the stride-2 halo, 32 channels per chunk.
 //   * ALO_CONV_DILATION_2 in `stride` (dilation 2, padding 2, stride 1: layer4 of a DC5 backbone) goes to conv3x3_d2_kernel, the
 //     stride-1 loop over runs of 68 pixels two rows apart with the taps two slots apart.
 #include <cstdlib>
@@ -825,6 +826,224 @@ conv3x3_pipe_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp,
     }
 }
 
+// ---- stride 2, Cout >= 128, no split-K: conv3x3_kernel<2, false>'s arithmetic and halo on conv3x3_pipe_kernel's loop ------------------
+// The waves, the tiles, the A fragments one k-step ahead, the weight ring that runs on across chunks and tiles, the barriers and the
+// epilogue are conv3x3_pipe_kernel's.  The halo is conv3x3_kernel<2, ...>'s: 32 channels per chunk (at 64 the 96-pixel halo takes 83 KB
+// and two workgroups no longer share a CU), per tap row a run of PIX + 1 odd-column and a run of PIX even-column pixels of input row
+// 2 y + dy - 1; tap (dy, dx) of tile pixel m reads slot dy kRun + (dx == 0 ? 0 : dx == 1 ? PIX + 1 : 1) + m.  A chunk is 18 k-steps
+// (tap s / 2, channels 16 (s % 2) ..), so the unrolled body is two chunks: 36 k-steps, whole turns of either ring.  The pixel behind
+// a staging slot depends on the tile alone (slot_pixel<2> divides per piece and chunk): its byte offset is worked out once per tile,
+// in the tile's last chunk for the next tile, and kept in registers.  An accumulator sees conv3x3_kernel<2, false>'s k-steps in
+// that kernel's order from zero, with its masking, bias, ReLU and rounding: the output is that kernel's bit for bit.
+template <int PIX, int RT>
+struct GeoPipeS2 {
+    static constexpr int kWavePix = 32 * RT;
+    static_assert(PIX == kWavePix || PIX == 2 * kWavePix, "four waves: 1 x 4 or 2 x 2 (pixels x columns)");
+    static constexpr int kCols = PIX == kWavePix ? 256 : 128;
+    static constexpr int kChunk = Geo<2>::kChunk;
+    static constexpr int kSteps = 9 * (kChunk / 16);         // k-steps per chunk: 18
+    static constexpr int kBody = 2;                          // chunks per unrolled body (Cin % 64 == 0)
+    static constexpr int kRing = GeoPipe<PIX, RT>::kRing;
+    static_assert((kBody * kSteps) % kRing == 0, "a body is a whole number of turns: a slot is the same register name in every body");
+    static constexpr int kRun = 2 * PIX + 1;                 // PIX + 1 odd-column pixels, then PIX even-column ones
+    static constexpr int kSlots = 3 * kRun;
+    static constexpr int kPixStride = Geo<2>::kPixStride;
+    static constexpr int kPieces = kSlots * (kChunk / 8);
+    static constexpr int kIters = (kPieces + 255) / 256;     // halo pieces per thread: 10 (PIX = 96), 13 (128)
+    static constexpr int kHalo = kSlots * kPixStride;        // 46320 B (PIX = 96), 61680 B (128)
+    static constexpr int kOut = 4 * kWavePix * kOutStride;   // four waves' bf16 output blocks; aliases the halo
+    static constexpr int kLds = kHalo > kOut ? kHalo : kOut;
+    static constexpr int kOffsets = kIters * 256 * 4;        // behind the bias values: the halo pieces' byte offsets inside the image
+    static_assert(2 * (kLds + 256 * 4 + kOffsets) <= 160 * 1024, "two workgroups per CU");
+};
+
+// slot_pixel<2> for a tile of PIX pixels
+template <int PIX>
+__device__ __forceinline__ int slot_pixel_s2(int slot, int p0, const ConvDims& dm) {
+    constexpr int kRun = 2 * PIX + 1;
+    const int dy = slot / kRun, r = slot - dy * kRun;
+    const int odd = r < PIX + 1 ? 1 : 0;                         // column parity of this run
+    int f = p0 + (odd ? r - 1 : r - (PIX + 1)) - (dy == 0 ? dm.Wo : 0);   // output-index space: (yo + oy) * Wo + xo + ox
+    const int last = dm.Ho * dm.Wo - 1;
+    f = f < 0 ? 0 : (f > last ? last : f);
+    const int yp = f / dm.Wo, xp = f - yp * dm.Wo;
+    int iy = 2 * yp + (dy == 1 ? 0 : 1), ix = 2 * xp + odd;
+    iy = iy > dm.H - 1 ? dm.H - 1 : iy;
+    ix = ix > dm.W - 1 ? dm.W - 1 : ix;
+    return iy * dm.W + ix;
+}
+
+template <int PIX, int RT>
+__global__ void __launch_bounds__(kPipeThreads, 2)
+conv3x3_pipe_s2_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wp, const bf16_t* __restrict__ bias,
+                       bf16_t* __restrict__ Y, const ConvDims dm) {   // dm.tiles_per_image counts tiles of PIX output pixels
+    using G = GeoPipeS2<PIX, RT>;
+    typedef const u32x4 __attribute__((address_space(1))) * global_u32x4;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const halo = smem;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int nl = lane & 31, kg = lane >> 5;
+    const int wcol = PIX == G::kWavePix ? wave : wave >> 1;              // this wave's 64 columns of the workgroup's
+    const int pbase = PIX == G::kWavePix ? 0 : G::kWavePix * (wave & 1);   // and its pixels of the tile
+    const int HWo = dm.Ho * dm.Wo;
+    const int col0 = blockIdx.y * G::kCols + wcol * 64;
+    const bool has_cols = col0 < dm.Cout;                  // Cout % 64 == 0
+    float* const bias_s = reinterpret_cast<float*>(smem + G::kLds);   // the workgroup's bias values, fp32; read after the tile's barriers
+    {
+        const int c = blockIdx.y * G::kCols + tid;
+        bias_s[tid] = (bias != nullptr && tid < G::kCols && c < dm.Cout) ? bf16_to_f32(bias[c].bits) : 0.f;
+    }
+
+    // persistent workgroups, one contiguous eighth of the tiles per XCD (see conv3x3_kernel)
+    const TileRange range = xcd_tile_range(dm.tiles_per_image * dm.N);
+    const int tile_end = range.end, lanes_per_xcd = range.step;
+    int tile = range.first;
+    if (tile >= tile_end) return;
+
+    const int ksteps_per_tap = dm.Cin / 16;
+    const size_t ctile_stride = (size_t)9 * ksteps_per_tap * 512;      // elements between the packed column tiles
+    const bf16_t* const wcols = Wp + (size_t)(has_cols ? col0 / 32 : 0) * ctile_stride;   // uniform; + this lane's 16 bytes of a fragment
+    const unsigned lane_bytes = lane * 16;
+    // k-step s of the chunk at channel c0: tap s / 2, channels c0 + 16 (s % 2) .. (conv3x3_kernel<2>'s order), both column tiles
+    auto load_w = [&](u32x4 (&f)[2], int c0, int s) {
+        const bf16_t* p = wcols + (size_t)((s >> 1) * ksteps_per_tap + (c0 >> 4) + (s & 1)) * 512;
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+            f[b] = *(global_u32x4)(uintptr_t)(reinterpret_cast<const unsigned char*>(p + b * ctile_stride) + lane_bytes);
+    };
+
+    // The halo travels through registers, requested one (tile, chunk) ahead.  Piece i = tid + 256 it is 16 bytes (tid & 3) of staging
+    // slot i >> 2 (slots past the last one repeat it and are not parked); every request is made, in-range by clamping.  aim_halo
+    // points ximg / hoff at a tile: the image and, per piece, the byte offset of its pixel inside it (H W Cin < 2^30).
+    // The offsets live in LDS, [piece][thread], each thread's own: in registers, next to the staged halo, the ring and the accumulators,
+    // they spill (184 / 224 bytes of scratch at RT = 3 / 2).
+    u32x4 stage[G::kIters];
+    unsigned* const hoff = reinterpret_cast<unsigned*>(smem + G::kLds + kPipeThreads * 4) + tid;
+    const unsigned char* ximg;   // uniform
+    const unsigned piece_bytes = (tid & 3) * 16, row_bytes = dm.Cin * 2;
+    auto aim_halo = [&](int tl) {
+        const int im = tl / dm.tiles_per_image, first = (tl - im * dm.tiles_per_image) * PIX;
+        ximg = reinterpret_cast<const unsigned char*>(X + (size_t)im * dm.H * dm.W * dm.Cin);
+#pragma unroll 1
+        for (int it = 0; it < G::kIters; ++it) {
+            int slot = (tid >> 2) + it * (kPipeThreads / 4);
+            slot = slot < G::kSlots ? slot : G::kSlots - 1;
+            hoff[it * kPipeThreads] = (unsigned)slot_pixel_s2<PIX>(slot, first, dm) * row_bytes + piece_bytes;
+        }
+    };
+    auto load_halo = [&](int c0) {
+        const unsigned char* xc = ximg + c0 * 2;   // uniform
+#pragma unroll
+        for (int it = 0; it < G::kIters; ++it) stage[it] = *(global_u32x4)(uintptr_t)(xc + hoff[it * kPipeThreads]);
+    };
+    aim_halo(tile);
+    load_halo(0);
+
+    // k-step n of the wave's stream (36 per body, bodies and tiles on end) lives in ring[n % kRing] (see conv3x3_pipe_kernel)
+    u32x4 ring[G::kRing][2];   // [slot][column tile]
+#pragma unroll
+    for (int s = 0; s < G::kRing - 1; ++s) load_w(ring[s], 0, s);
+    __builtin_amdgcn_sched_barrier(0);
+
+    const unsigned char* const a_lane = halo + (pbase + nl) * G::kPixStride + kg * 16;
+    unsigned char* const obuf = smem + wave * (G::kWavePix * kOutStride);
+
+    for (; tile < tile_end; tile += lanes_per_xcd) {
+        const int img = tile / dm.tiles_per_image;
+        const int p0 = (tile - img * dm.tiles_per_image) * PIX + pbase;   // this wave's first output pixel inside the image
+        const int next_tile = tile + lanes_per_xcd < tile_end ? tile + lanes_per_xcd : tile;
+
+        // which of the 9 taps exist for this lane's pixels (row tile a: output pixel p0 + 32 a + nl)
+        unsigned tapmask[RT];
+#pragma unroll
+        for (int a = 0; a < RT; ++a) {
+            const int q = p0 + 32 * a + nl;
+            const int y = q / dm.Wo, x = q - y * dm.Wo;
+            unsigned m = 0;
+#pragma unroll
+            for (int t = 0; t < 9; ++t) {
+                const int yy = 2 * y + t / 3 - 1, xx = 2 * x + t % 3 - 1;
+                if (q < HWo && yy >= 0 && yy < dm.H && xx >= 0 && xx < dm.W) m |= 1u << t;
+            }
+            tapmask[a] = m;
+        }
+
+        f32x16 acc[RT][2];  // [row tile][column tile]
+        zero_acc(acc);
+
+#pragma unroll 1
+        for (int c0 = 0; c0 < dm.Cin; c0 += G::kBody * G::kChunk) {
+            const bool last_body = c0 + G::kBody * G::kChunk >= dm.Cin;
+            const int c0_next = last_body ? 0 : c0 + G::kBody * G::kChunk;
+#pragma unroll
+            for (int h = 0; h < G::kBody; ++h) {
+#pragma unroll
+                for (int it = 0; it < G::kIters; ++it) {
+                    const int i = tid + it * kPipeThreads;
+                    if (it < G::kPieces / kPipeThreads || i < G::kPieces)
+                        *reinterpret_cast<u32x4*>(halo + (i >> 2) * G::kPixStride + (i & 3) * 16) = stage[it];
+                }
+                pipe_lds_barrier();
+                // the next chunk, of this tile or of the next one (the last tile asks for its own first chunk again: no branch around
+                // requests; the branch below holds integer arithmetic alone)
+                if (h + 1 < G::kBody) load_halo(c0 + (h + 1) * G::kChunk);
+                else {
+                    if (last_body) aim_halo(next_tile);
+                    load_halo(c0_next);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+
+                u32x4 af[2][RT];   // [k-step parity][row tile]: the fragments of k-step s + 1 are read before the MFMAs of k-step s
+#pragma unroll
+                for (int a = 0; a < RT; ++a) af[0][a] = *reinterpret_cast<const u32x4*>(a_lane + 32 * a * G::kPixStride);
+#pragma unroll
+                for (int s = 0; s < G::kSteps; ++s) {   // k-step of the chunk: tap s / 2, channels 16 (s % 2) ..
+                    // k-step n + kAhead of the body takes the slot k-step n - 1 left
+                    constexpr int kAhead = G::kRing - 1, kBodySteps = G::kBody * G::kSteps;
+                    const int n = h * G::kSteps + s + kAhead;
+                    if (n < kBodySteps) load_w(ring[n % G::kRing], c0 + (n / G::kSteps) * G::kChunk, n % G::kSteps);
+                    else load_w(ring[n % G::kRing], c0_next, n - kBodySteps);
+                    if (s + 1 < G::kSteps) {
+                        const int tn = (s + 1) >> 1, dy = tn / 3, dx = tn % 3;
+                        const int slot = dy * G::kRun + (dx == 0 ? 0 : (dx == 1 ? PIX + 1 : 1));
+#pragma unroll
+                        for (int a = 0; a < RT; ++a)
+                            af[(s + 1) & 1][a] = *reinterpret_cast<const u32x4*>(a_lane + (slot + 32 * a) * G::kPixStride + ((s + 1) & 1) * 32);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    const int t = s >> 1;
+                    u32x4 am[RT];
+#pragma unroll
+                    for (int a = 0; a < RT; ++a) am[a] = ((tapmask[a] >> t) & 1u) ? af[s & 1][a] : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int a = 0; a < RT; ++a)
+                            acc[a][b] = mfma_32x32x16<bf16_t>(ring[(h * G::kSteps + s) % G::kRing][b], am[a], acc[a][b]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                pipe_lds_barrier();  // the halo is overwritten by the next channel chunk (and by the epilogue's staging)
+            }
+        }
+
+        if (has_cols) {
+            // lane = output pixel 32 a + nl, registers 4 q .. 4 q + 3 = channels col0 + 32 b + 8 q + 4 kg .. + 3 (see conv3x3_kernel)
+            stage_quads<bf16_t, true>(obuf, kOutStride, acc, bias_s + wcol * 64, dm.relu, nl, 0, kg);
+            ALO_WAVE_LDS_ORDER();
+            // the wave's pixels x 128 B: 8 lanes x 16 B per pixel, 8 pixels per store instruction
+#pragma unroll
+            for (int pass = 0; pass < G::kWavePix / 8; ++pass) {
+                const int row = pass * 8 + (lane >> 3);
+                const int q = p0 + row;
+                if (q < HWo)
+                    *reinterpret_cast<u32x4*>(Y + ((size_t)img * HWo + q) * dm.Cout + col0 + (lane & 7) * 8) =
+                        *reinterpret_cast<const u32x4*>(obuf + row * kOutStride + (lane & 7) * 16);
+            }
+        }
+        pipe_lds_barrier();  // the staging is read out before the next tile's halo lands on it
+    }
+}
+
 // y[p][c] = act(sum_z partial[z][p][c] + bias[c]) -> bf16; one thread per 8 channels
 __global__ void __launch_bounds__(256)
 conv_splitk_finalize_kernel(const float* __restrict__ partial, const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y, long rows,
@@ -891,6 +1110,17 @@ int launch_conv_pipe(const void* x, const void* w, const void* bias, void* y, co
     const unsigned gx = xcd_grid(dp.tiles_per_image * dm.N, 64);   // 32 CUs per XCD x 2 resident workgroups of four waves
     const unsigned gy = (dm.Cout + G::kCols - 1) / G::kCols;
     return launch<conv3x3_pipe_kernel<PIX, RT>>(dim3(gx, gy), kPipeThreads, G::kLds + kPipeThreads * 4, stream, "alo_conv3x3_nhwc", args);
+}
+
+template <int PIX, int RT>
+int launch_conv_pipe_s2(const void* x, const void* w, const void* bias, void* y, const ConvDims& dm, hipStream_t stream) {
+    using G = GeoPipeS2<PIX, RT>;
+    ConvDims dp = dm;
+    dp.tiles_per_image = (dm.Ho * dm.Wo + PIX - 1) / PIX;
+    void* args[] = {&x, &w, &bias, &y, &dp};
+    const unsigned gx = xcd_grid(dp.tiles_per_image * dm.N, 64);   // as launch_conv_pipe
+    const unsigned gy = (dm.Cout + G::kCols - 1) / G::kCols;
+    return launch<conv3x3_pipe_s2_kernel<PIX, RT>>(dim3(gx, gy), kPipeThreads, G::kLds + kPipeThreads * 4 + G::kOffsets, stream, "alo_conv3x3_nhwc", args);
 }
 
 }  // namespace
@@ -967,6 +1197,18 @@ extern "C" int alo_conv3x3_nhwc(const void* x, const void* w_packed, const void*
     const char* pipe = getenv("ALO_CONV3X3_PIPE");
     if (!dil2 && stride == 1 && Cout >= 128 && dm.zsplit == 1 && (long)H * W * Cin < (1L << 30) && !(pipe && !strcmp(pipe, "off")))
         return Cout >= 256 ? launch_conv_pipe<96, 3>(x, w_packed, bias, y, dm, s) : launch_conv_pipe<128, 2>(x, w_packed, bias, y, dm, s);
+    // Stride 2 of 128 and more output channels goes to conv3x3_pipe_s2_kernel on the same terms; "off" keeps it on conv3x3_kernel<2, false>
+    // as well, and ALO_CONV3X3_PIPE = "stride1" keeps it there alone (stride 1 pipelined: the routing before the stride-2 kernel).
+    // Measured in the headline's graph replay, parent then change (profiles/conv3x3_pipe_s2_{parent,change}_kernel_stats.csv, split by
+    // grid in the traces; avg (min-max) over 37 passes, us):
+    //   128 ch 200 x 334: 111.8 (109.2-115.5) -> 77.9 (75.6-83.0);  256 ch 100 x 167: 105.6 (102.6-115.2) -> 57.7 (55.7-66.9);
+    //   512 ch 50 x 84: 102.6 (93.1-111.8) -> 66.0 (63.4-76.0).  Max below min for all three, over all 37 passes and over the 30 timed
+    //   ones (79.8 < 110.2, 58.1 < 104.1, 67.3 < 99.4): no shape is sent back.  The split-K call (2048 -> 256, 60.5 us) is not the route's.
+    // Back to back at 256 / 512 channels: 128 x 128 two row tiles 77.1 / 79.1, 64 x 256 two row tiles 64.7 / 69.6, 96 x 256 three row
+    // tiles 60.4 / 59.8 (routed); at 128 channels 128 x 128 with a ring of 6 / 4 / 3: 74.6 / 75.6 / 78.8 (docs/experiments.md).
+    if (!dil2 && stride == 2 && Cout >= 128 && dm.zsplit == 1 && (long)H * W * Cin < (1L << 30) &&
+        !(pipe && (!strcmp(pipe, "off") || !strcmp(pipe, "stride1"))))
+        return Cout >= 256 ? launch_conv_pipe_s2<96, 3>(x, w_packed, bias, y, dm, s) : launch_conv_pipe_s2<128, 2>(x, w_packed, bias, y, dm, s);
     const bool ksplit = Cout == 64;
     const int rc = dil2 ? (ksplit ? launch_conv_d2<true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv_d2<false>(x, w_packed, bias, y, workspace, dm, s))
                  : stride == 1 ? (ksplit ? launch_conv<1, true>(x, w_packed, bias, y, workspace, dm, s) : launch_conv<1, false>(x, w_packed, bias, y, workspace, dm, s))
