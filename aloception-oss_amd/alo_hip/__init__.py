@@ -641,9 +641,14 @@ def corr_lookup_backward_coords(levels, coords, grad_out, radius=4):
     return per_level.sum(1)
 
 
-def corr_alt_prepare(fmap1, fmap2_levels):
+ALO_CORR_ALT_GRAD = 0x100   # include/alo_corr_alt.h: OR-ed into num_levels
+
+
+def corr_alt_prepare(fmap1, fmap2_levels, grad=False):
     """AlternateCorrBlock.__init__ (corr.py:63-71): fmap1 (B,C,H,W) and the 2x2-mean chain of fmap2 (level l: (B,C,h_l,w_l)) ->
-    the workspace of :func:`corr_alt_lookup` (uint8 tensor): channels-last copies of fmap1 and of every level, made once."""
+    the workspace of :func:`corr_alt_lookup` (uint8 tensor): channels-last copies of fmap1 and of every level, made once.
+    ``grad``: the workspace also carries the gradient region of :func:`corr_alt_lookup_backward` (``ALO_CORR_ALT_GRAD`` size;
+    not initialised: :func:`corr_alt_grad_views` reaches it)."""
     _require_f32_cuda("fmap1", fmap1, 4)
     for lvl, t in enumerate(fmap2_levels):
         _require_f32_cuda(f"fmap2_levels[{lvl}]", t, 4)
@@ -655,7 +660,8 @@ def corr_alt_prepare(fmap1, fmap2_levels):
     fmap1 = fmap1.contiguous()
     levels = [t.contiguous() for t in fmap2_levels]
     nbytes = lib().alo_corr_alt_workspace_bytes(B, C, H, W, L)   # 0 past the limits: the call below says which
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=fmap1.device)
+    total = lib().alo_corr_alt_workspace_bytes(B, C, H, W, L | ALO_CORR_ALT_GRAD) if grad else nbytes
+    ws = torch.empty((max(total, 16),), dtype=torch.uint8, device=fmap1.device)
     moved = 4.0 * 2 * (fmap1.numel() + sum(t.numel() for t in levels))
     _launch("alo_corr_alt_prepare", fmap1.device, "corr_alt_prepare", moved, 0.0, fmap1, levels, ws, nbytes, B, C, H, W, L)
     return ws
@@ -678,6 +684,67 @@ def corr_alt_lookup(workspace, coords, channels, num_levels, radius=4):
     _launch("alo_corr_alt_lookup", coords.device, "corr_alt_lookup", nbytes, flops, workspace, workspace.numel(), coords, out,
             B, C, H, W, radius, L)
     return out
+
+
+def corr_alt_with_grad_region(workspace, shape, num_levels):
+    """A copy of a prepared ``workspace`` (:func:`corr_alt_prepare` for feature maps of ``shape`` = (B, C, H, W)) with the gradient
+    region of :func:`corr_alt_lookup_backward` behind it (not initialised)."""
+    B, C, H, W = shape
+    total = lib().alo_corr_alt_workspace_bytes(B, C, H, W, num_levels | ALO_CORR_ALT_GRAD)
+    if total == 0 or workspace.numel() != lib().alo_corr_alt_workspace_bytes(B, C, H, W, num_levels):
+        raise RuntimeError("workspace must be the tensor corr_alt_prepare returned for these sizes")
+    out = torch.empty((total,), dtype=torch.uint8, device=workspace.device)
+    out[:workspace.numel()].copy_(workspace)
+    return out
+
+
+def corr_alt_grad_views(workspace, shape, num_levels):
+    """The gradient region of a workspace made with ``grad=True`` for feature maps of ``shape`` = (B, C, H, W), as views (layout:
+    include/alo_corr_alt.h) -> (region, planes, levels): the whole region as uint8 (to zero it), ``num_levels`` float32 planes
+    (B, H*W, Cp) whose sum is grad_fmap1 channels-last, and per level the slice-major (Cp/16, B, h_l*w_l, 16) gradient of fmap2's
+    level.  Works on any device (the layout is arithmetic on the sizes)."""
+    B, C, H, W = shape
+    cp = (C + 15) // 16 * 16
+    pad = lambda n: (n + 255) // 256 * 256   # noqa: E731
+    sizes = [(H, W)]
+    for _ in range(num_levels - 1):
+        sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
+    plane = pad(B * H * W * cp * 4)
+    parts = [pad(B * h * w * cp * 4) for h, w in sizes]
+    start = plane + sum(parts)
+    if workspace.dtype != torch.uint8 or workspace.numel() < start + num_levels * plane + sum(parts):
+        raise RuntimeError("workspace must be the uint8 tensor corr_alt_prepare(..., grad=True) returned for these sizes")
+    at = start
+    planes, levels = [], []
+    for _ in range(num_levels):
+        planes.append(workspace[at:at + B * H * W * cp * 4].view(torch.float32).view(B, H * W, cp))
+        at += plane
+    for (h, w), part in zip(sizes, parts):
+        levels.append(workspace[at:at + B * h * w * cp * 4].view(torch.float32).view(cp // 16, B, h * w, 16))
+        at += part
+    return workspace[start:at], planes, levels
+
+
+def corr_alt_lookup_backward(workspace, coords, grad_out, channels, num_levels, radius=4):
+    """Adds the feature-map gradients of ONE :func:`corr_alt_lookup` to the gradient region of ``workspace``
+    (``corr_alt_prepare(..., grad=True)``; zeroed by the caller before the first lookup whose gradients are to be summed): the
+    adjoint of the lookup with respect to fmap1 and every level of fmap2 (``alo_corr_alt_lookup`` with ``ALO_CORR_ALT_GRAD``).
+    The prepared part of the workspace is only read.  The level gradients are summed with float atomics: their last bits depend
+    on the run.  In place; returns ``workspace``."""
+    _require_f32_cuda("coords", coords, 4)
+    _require_f32_cuda("grad_out", grad_out, 4)
+    if not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.device != coords.device:
+        raise RuntimeError("workspace must be the uint8 CUDA tensor corr_alt_prepare returned, on the device of coords")
+    coords, grad_out = coords.contiguous(), grad_out.contiguous()
+    B, two, H, W = coords.shape
+    L, C, win = num_levels, channels, (2 * radius + 1) ** 2
+    if two != 2 or tuple(grad_out.shape) != (B, L * win, H, W) or grad_out.device != coords.device:
+        raise RuntimeError("corr_alt_lookup_backward: coords must be (B,2,H,W) and grad_out (B, L*(2r+1)^2, H, W)")
+    flops = 4.0 * B * H * W * L * (2 * radius + 2) ** 2 * C          # both adjoints of the lattice's inner products
+    nbytes = 4.0 * B * H * W * (L * win + 2 + 3 * L * C)             # grad_out + coords + fmap1 once and its plane twice per level
+    _launch("alo_corr_alt_lookup", coords.device, "corr_alt_lookup_backward", nbytes, flops, workspace, workspace.numel(), coords,
+            grad_out, B, C, H, W, radius, L | ALO_CORR_ALT_GRAD)
+    return workspace
 
 
 def _grad_tensors(operands):

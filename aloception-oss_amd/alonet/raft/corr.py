@@ -92,13 +92,17 @@ if _graph_task_id is None or _queue_callback is None:
 
 
 class _PyramidState:
-    """What the build node and the lookup nodes of one CorrBlock share: the pyramid and, during a backward pass, the gradient maps
-    the lookups accumulate into."""
+    """What the build node and the lookup nodes of one block share: what the lookups read (CorrBlock: the pyramid;
+    TrainableAlternateCorrBlock: the workspace) and, during a backward pass, the gradient maps the lookups accumulate into.
+    ``new_maps()`` returns the zeroed maps of a pass (default: zeros shaped like the pyramid); ``owner`` names the block in the
+    warning."""
 
-    def __init__(self):
+    def __init__(self, new_maps=None, owner="CorrBlock"):
         self.pyramid = None
         self.grad = None
         self.grad_pass = None
+        self.owner = owner
+        self.new_maps = new_maps if new_maps is not None else (lambda: [torch.zeros_like(p) for p in self.pyramid])
 
     @staticmethod
     def _current_pass():
@@ -113,7 +117,7 @@ class _PyramidState:
         maps tagged by another pass are also discarded here, when the next pass first asks for them."""
         now = self._current_pass()
         if self.grad is None or self.grad_pass != now:
-            self.grad = [torch.zeros_like(p) for p in self.pyramid]
+            self.grad = self.new_maps()
             self.grad_pass = now
             _queue_callback(self._end_of_pass)
         return self.grad
@@ -124,8 +128,8 @@ class _PyramidState:
         self.grad = self.grad_pass = None
         if maps is not None and tag != self._current_pass():
             # lookups ran in another pass than the build node (a nested / re-entrant backward): their maps are not this pass's
-            warnings.warn("CorrBlock: gradient maps accumulated by another autograd pass were discarded; the feature-map gradients of "
-                          "this pass do not include those lookups (re-entrant backward through a CorrBlock is not supported)",
+            warnings.warn(f"{self.owner}: gradient maps accumulated by another autograd pass were discarded; the feature-map gradients "
+                          f"of this pass do not include those lookups (re-entrant backward through a {self.owner} is not supported)",
                           RuntimeWarning, stacklevel=2)
             return None
         return maps
@@ -330,6 +334,116 @@ class AlternateCorrBlock:
 
     def __call__(self, coords):
         return alo_hip.corr_alt_lookup(self._workspace, coords.detach().float(), self._channels, self.num_levels, self.radius)
+
+
+def alt_feature_gradients(planes, levels, shape, need_fmap1=True, need_fmap2=True):
+    """The build node's backward of :class:`TrainableAlternateCorrBlock`, on stock ops (any device): the gradient maps the lookups
+    accumulated, in the layout of the workspace's gradient region (include/alo_corr_alt.h), -> ``(grad_fmap1, grad_fmap2)`` as
+    ``shape`` = (B, C, H, W) tensors (``None`` where not needed).  ``planes``: per level a (B, H*W, Cp) channels-last contribution
+    to grad_fmap1; they are summed.  ``levels``: per level the slice-major (Cp/16, B, h_l*w_l, 16) gradient of fmap2 pooled l
+    times; each goes back through the 2x2-mean chain (floor pooling: an odd last row or column receives nothing from the coarser
+    levels) and they are summed.  Padded channels C..Cp-1 are dropped."""
+    B, C, H, W = shape
+    g1 = g2 = None
+    if need_fmap1:
+        total = planes[0][:, :, :C].clone()
+        for plane in planes[1:]:
+            total += plane[:, :, :C]
+        g1 = total.reshape(B, H, W, C).permute(0, 3, 1, 2).contiguous()
+    if need_fmap2:
+        with torch.enable_grad():   # the chain is linear: its adjoint does not depend on the leaf's values
+            leaf = torch.zeros(shape, dtype=levels[0].dtype, device=levels[0].device, requires_grad=True)
+            chain = _pooled_chain(leaf, len(levels))
+        heads = []
+        for lvl, g in enumerate(levels):
+            h, w = chain[lvl].shape[-2:]
+            heads.append(g.permute(1, 0, 3, 2).reshape(B, -1, h, w)[:, :C])   # (s, b, p, c) -> (b, 16 s + c, y, x)
+        (g2,) = torch.autograd.grad(chain, leaf, heads)
+    return g1, g2
+
+
+class _AltBuildFunction(torch.autograd.Function):
+    """Prepares the workspace (with its gradient region) and returns the scalar token every lookup takes; its backward turns the
+    gradient maps of the pass into the feature-map gradients."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, num_levels, state, prepared):
+        ctx.shape = tuple(fmap1.shape)
+        ctx.num_levels = num_levels
+        ctx.state = state
+        # "pyramid": what the lookups read.  The maps AlternateCorrBlock prepared, with the gradient region behind them
+        state.pyramid = alo_hip.corr_alt_with_grad_region(prepared, ctx.shape, num_levels)
+        return fmap1.new_zeros(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _gtoken):
+        workspace = ctx.state.take_grad_maps()
+        if workspace is None:
+            return None, None, None, None, None
+        _, planes, levels = alo_hip.corr_alt_grad_views(workspace, ctx.shape, ctx.num_levels)
+        g1, g2 = alt_feature_gradients(planes, levels, ctx.shape, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return g1, g2, None, None, None
+
+
+class _AltLookupFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coords, token, channels, num_levels, radius, state):
+        ctx.save_for_backward(coords)
+        ctx.dims = (channels, num_levels, radius)
+        ctx.state = state
+        return alo_hip.corr_alt_lookup(state.pyramid, coords, channels, num_levels, radius)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (coords,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return (None,) * 6
+        alo_hip.corr_alt_lookup_backward(ctx.state.grad_maps(), coords, grad_out, *ctx.dims)
+        return None, coords.new_zeros(()), None, None, None, None
+
+
+class TrainableAlternateCorrBlock(AlternateCorrBlock):
+    """:class:`AlternateCorrBlock` that can be trained through: ``RAFT(corr_block=TrainableAlternateCorrBlock)``.  Same constructor,
+    same call, same values.
+
+    When grad mode is off or neither feature map requires a gradient it IS ``AlternateCorrBlock``: the same two launches, the same
+    bits, no extra memory.  Otherwise it follows :class:`CorrBlock`'s pattern: a build node returns a scalar token, every lookup is
+    an ``autograd.Function`` that takes the token, and a lookup's backward (``corr_alt_lookup_bwd_kernel``, csrc/corr_alt.hip)
+    ACCUMULATES into gradient maps shared by all lookups of the block; the build node's backward turns them into ``grad_fmap1`` and
+    ``grad_fmap2`` (:func:`alt_feature_gradients`).  The maps live in the block's own workspace, behind the prepared feature maps,
+    and are zeroed by the first lookup backward of a pass: memory stays O(HW*C*num_levels); nothing of size (HW)^2 or
+    HW*C*(2r+1)^2 is ever allocated.
+
+    No gradient with respect to the coordinates (RAFT detaches them; :class:`CorrBlock` has one): coordinates that require a
+    gradient under grad mode raise.  No double backward.  ``grad_fmap1`` is bitwise reproducible; ``grad_fmap2`` is summed with
+    float atomics, so its last bits depend on the run (as in the reference's scatter kernels and this library's MSDA backward).
+    """
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        self._state = self._token = None
+        super().__init__(fmap1, fmap2, num_levels, radius)   # the checks, the pyramid, the prepared maps: without gradients, all
+        if not _needs_grad(fmap1, fmap2):
+            return
+        self._shape = tuple(fmap1.shape)
+        self._state = _PyramidState(self._zeroed_maps, owner="TrainableAlternateCorrBlock")
+        self._token = _AltBuildFunction.apply(fmap1.float(), fmap2.float(), num_levels, self._state, self._workspace)
+        self._workspace = self._state.pyramid
+
+    def _zeroed_maps(self):
+        region, _, _ = alo_hip.corr_alt_grad_views(self._workspace, self._shape, self.num_levels)
+        region.zero_()
+        return self._workspace
+
+    def __call__(self, coords):
+        if torch.is_grad_enabled() and coords.requires_grad:
+            raise RuntimeError("TrainableAlternateCorrBlock has no gradient with respect to the coordinates: detach them (RAFT "
+                               "does), or use CorrBlock, which has one")
+        if self._state is None or not torch.is_grad_enabled():
+            return super().__call__(coords)
+        return _AltLookupFunction.apply(coords.detach().float().contiguous(), self._token, self._channels, self.num_levels,
+                                        self.radius, self._state)
 
 
 def lookup_alt_torch(pyramid, coords, num_levels, radius):

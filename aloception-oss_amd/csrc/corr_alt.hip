@@ -20,6 +20,11 @@
 //
 // Arithmetic: exact fp32 (one fmaf chain per lattice point over the channels), so a non-finite feature spoils exactly the
 // lattice points — and through them the taps — that touch it, as in the reference's fp32 arithmetic.
+//
+// Adjoint (alo_corr_alt_lookup with ALO_CORR_ALT_GRAD in num_levels, TrainableAlternateCorrBlock): corr_alt_lookup_bwd_kernel adds
+// the gradients of one lookup with respect to fmap1 and to every level of fmap2 into the GRADIENT REGION the flagged workspace
+// carries behind the prepared maps: one channels-last grad_fmap1 plane per level, then every level's gradient slice-major,
+// (Cp/16, B, h*w, 16).  Same tiles, footprint and staged / direct decision as the lookup; the comment above the kernel has the rest.
 #include "common.hpp"
 
 #include "../../include/alo_corr_alt.h"
@@ -230,6 +235,231 @@ int launch_alt_lookup(AltArgs a, hipStream_t stream) {
     return launch<corr_alt_lookup_kernel<R>>(a.nblocks, kAltThreads, 0, stream, "alo_corr_alt_lookup", args);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The adjoint of one lookup with respect to both feature maps (alo_corr_alt_lookup with ALO_CORR_ALT_GRAD).  Same workgroups, same
+// footprint and same staged / direct decision as the forward.  With gL[k] = the bilinear adjoint of grad_out at lattice point k
+// (times 1/sqrt(C); 0 off the map and for a query that reads an all-zero window), kept in registers like the forward's sums:
+//   dF1[q, :]      += sum_k gL[k] * f2_l[pix(k), :]   the forward's inner loop with gL in place of the accumulators; the four waves'
+//                     partial sums meet in LDS and are added to the level's OWN grad_fmap1 plane with plain loads and stores (a
+//                     (query, level) belongs to one workgroup, launches on one stream are ordered): no atomics, reproducible;
+//   dF2_l[pix(k),:] += gL[k] * f1[q, :]               a scatter.  Many (query, point) pairs of a tile hit the same pixel, so the slice
+//                     of the footprint is summed in LDS (ds_add_f32 on a [channel][pixel] image: lanes = queries = neighbouring
+//                     pixels = neighbouring banks) and every footprint row is flushed once per tile and slice with
+//                     global_atomic_add_f32.  The gradient of a level is stored SLICE-MAJOR, (Cp/16, B, h*w, 16), so that a
+//                     footprint row of a slice is one contiguous run: a wave's atomic instruction covers 256 contiguous bytes.
+// Per 16-channel slice the 48 KB stage buffer is used three times (fmap2 slice -> the waves' dF1 partials -> dF2 accumulator), so the
+// kernel stays under the forward's LDS budget at every radius.  A tile over the footprint budget reads fmap2 and adds into dF2
+// straight in global memory, one atomic per (query, point, channel): slower, the same value up to the order of the sums.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kAltAccPitch = kAltMaxFp + 1;   // accumulator [channel][pixel]: an odd pitch, the flush reads 16 channels of a pixel
+
+struct AltGradArgs {
+    float* g1[kAltMaxLevels];   // level l's plane of grad_fmap1: (B, H*W, Cp)
+    float* g2[kAltMaxLevels];   // gradient of fmap2's level l: (Cp/16, B, h_l*w_l, 16)
+    int B;
+};
+
+template <int R>
+__global__ void __launch_bounds__(kAltThreads)
+corr_alt_lookup_bwd_kernel(const AltArgs a, const AltGradArgs ga) {
+    constexpr int S = 2 * R + 2, WIN = 2 * R + 1, NP = S * S / 4;
+    static_assert(NP <= 64, "lattice mask is 64 bits");
+    constexpr int kLds4 = (kAltAccPitch * kAltCS + 3) / 4;
+    static_assert(kLds4 >= kAltAccPitch * (kAltCS / 4) && kLds4 >= kAltThreads * (kAltCS / 4), "stage buffer and partial sums fit");
+    __shared__ f32x4 lds4[kLds4];
+    float* lds = reinterpret_cast<float*>(lds4);
+
+    const unsigned id = xcd_contiguous_block(blockIdx.x, a.nblocks);
+    const int tile = (int)(id % (unsigned)a.tiles);
+    const int l = (int)((id / (unsigned)a.tiles) % (unsigned)a.num_levels);
+    const int b = (int)(id / (unsigned)a.tiles / (unsigned)a.num_levels);
+    const int tid = threadIdx.x, q = tid & (kAltTQ - 1), wv = tid >> 6;
+    const int tx0 = (tile % a.tiles_x) * kAltTile, ty0 = (tile / a.tiles_x) * kAltTile;
+    const int qx = tx0 + (q & (kAltTile - 1)), qy = ty0 + q / kAltTile;
+    const int h = a.h[l], w = a.w[l];
+    const long HW = (long)a.H * a.W;
+    const bool inside = qx < a.W && qy < a.H;
+    const long qpix = inside ? (long)qy * a.W + qx : 0;
+
+    // the query on this level, its lattice and the tile's footprint: the forward's, line for line
+    const float inv = 1.0f / (float)(1 << l);
+    float cx = 0.f, cy = 0.f;
+    if (inside) {
+        cx = a.coords[((long)b * 2 + 0) * HW + qpix] * inv;
+        cy = a.coords[((long)b * 2 + 1) * HW + qpix] * inv;
+    }
+    const bool valid = inside && fabsf(cx) < 1e6f && fabsf(cy) < 1e6f;
+    const float flx = valid ? floorf(cx) : 0.f, fly = valid ? floorf(cy) : 0.f;
+    const float fx = valid ? cx - flx : 0.f, fy = valid ? cy - fly : 0.f;
+    const int x0 = (int)flx - R, y0 = (int)fly - R;
+    const int xlo = max(x0, 0), xhi = min(x0 + S - 1, w - 1), ylo = max(y0, 0), yhi = min(y0 + S - 1, h - 1);
+    const bool touches = valid && xlo <= xhi && ylo <= yhi;
+    int mnx = touches ? xlo : INT_MAX, mxx = touches ? xhi : INT_MIN;
+    int mny = touches ? ylo : INT_MAX, mxy = touches ? yhi : INT_MIN;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        mnx = min(mnx, __shfl_xor(mnx, o, 64));
+        mxx = max(mxx, __shfl_xor(mxx, o, 64));
+        mny = min(mny, __shfl_xor(mny, o, 64));
+        mxy = max(mxy, __shfl_xor(mxy, o, 64));
+    }
+    if (mnx > mxx) return;   // workgroup-uniform: no window of the tile touches the map, nothing to add
+    const int fw = mxx - mnx + 1, fh = mxy - mny + 1;
+    int F = fw <= 8 ? 8 : ((fw - 9) / 16 + 1) * 16 + 8;
+    if ((long)fh * F > kAltMaxFp) F = fw;
+    const bool staged = (long)fh * F <= kAltMaxFp;
+
+    // this thread's lattice points and their gL: point (row, col) feeds the taps (col - dx, row - dy), dx, dy in {0, 1}, with the
+    // weights the forward mixed them with.  A point off the map, or of a query whose window reads as zero, has no bit and gL = 0
+    const float* gq = a.out + ((long)b * a.num_levels + l) * (WIN * WIN) * HW + qpix;   // grad_out of this query's level
+    const float wx[2] = {1.0f - fx, fx}, wy[2] = {1.0f - fy, fy};
+    auto point_grad = [&](int row, int col) {
+        float s = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ax = col - dx, ay = row - dy;
+                if (ax >= 0 && ax < WIN && ay >= 0 && ay < WIN) s = fmaf(wy[dy] * wx[dx], gq[(long)(ax * WIN + ay) * HW], s);
+            }
+        return s * a.scale;
+    };
+
+    const float* f1q = a.f1 + ((long)b * HW + qpix) * a.Cp;
+    const float* f2b = a.f2[l] + (long)b * h * w * a.Cp;
+    // the plane of grad_fmap1: thread -> query tid / 4, channels 4 (tid & 3) .. + 3 of the slice
+    const int c4s = tid & 3, q2 = tid >> 2;
+    const int q2x = tx0 + (q2 & (kAltTile - 1)), q2y = ty0 + q2 / kAltTile;
+    const bool inside2 = q2x < a.W && q2y < a.H;
+    float* g1q = ga.g1[l] + ((long)b * HW + (inside2 ? (long)q2y * a.W + q2x : 0)) * a.Cp + 4 * c4s;
+    const long slice_stride = (long)ga.B * h * w * kAltCS;                 // floats between two slices of the level's gradient
+    float* g2b = ga.g2[l] + (long)b * h * w * kAltCS;
+
+    // the four waves' partial sums of dF1 meet in LDS; a thread then adds one query's four channels to the plane
+    auto add_f1 = [&](const f32x4 (&p)[kAltCS / 4], int c0) {
+        __syncthreads();   // every wave is done with the buffer's previous contents
+#pragma unroll
+        for (int c = 0; c < kAltCS / 4; ++c) lds4[(wv * (kAltCS / 4) + c) * kAltTQ + q] = p[c];
+        __syncthreads();
+        if (inside2) {
+            f32x4 s = lds4[c4s * kAltTQ + q2];
+#pragma unroll
+            for (int v = 1; v < kAltThreads / kAltTQ; ++v) s += lds4[(v * (kAltCS / 4) + c4s) * kAltTQ + q2];
+            f32x4* dst = reinterpret_cast<f32x4*>(g1q + c0);
+            *dst = *dst + s;
+        }
+    };
+
+    if (staged) {
+        // the points' gL and LDS pixel stay in registers for all slices.  A point off the map, or of a query whose window reads as
+        // zero, has gL = 0 and the spare pixel kAltMaxFp (zero, never flushed): no branch in the loops
+        int off[NP];
+        float gl[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int k = wv + 4 * j, col = k % S, row = k / S, px = x0 + col, py = y0 + row;
+            const bool in = valid && px >= 0 && px < w && py >= 0 && py < h;
+            off[j] = in ? (py - mny) * F + (px - mnx) : kAltMaxFp;
+            gl[j] = in ? point_grad(row, col) : 0.f;
+        }
+        constexpr bool kAhead = R <= 5;   // the next slice's loads in flight during this one's arithmetic, where the registers allow
+        int gpix[kAltStageItems];
+#pragma unroll
+        for (int i = 0; i < kAltStageItems; ++i) {
+            const int pix = (tid >> 2) + 64 * i, py = pix / F, px = pix - py * F;
+            gpix[i] = (py < fh && px < fw) ? (mny + py) * w + mnx + px : -1;
+        }
+        f32x4 st[kAltStageItems];
+        auto load_slice = [&](int c0) {
+#pragma unroll
+            for (int i = 0; i < kAltStageItems; ++i)
+                if (gpix[i] >= 0) st[i] = *reinterpret_cast<const f32x4*>(f2b + (long)gpix[i] * a.Cp + c0 + 4 * c4s);
+        };
+        const int rowlen = fw * kAltCS;   // floats of one footprint row of a slice: contiguous in the level's gradient
+        if (kAhead) load_slice(0);
+        for (int c0 = 0; c0 < a.Cp; c0 += kAltCS) {
+            if (!kAhead) load_slice(c0);
+            __syncthreads();   // the previous slice's accumulator has been flushed
+#pragma unroll
+            for (int i = 0; i < kAltStageItems; ++i)
+                if (gpix[i] >= 0) lds4[c4s * kAltAccPitch + (tid >> 2) + 64 * i] = st[i];
+            if (tid < kAltCS / 4) lds4[tid * kAltAccPitch + kAltMaxFp] = f32x4{0.f, 0.f, 0.f, 0.f};
+            __syncthreads();
+            if (kAhead && c0 + kAltCS < a.Cp) load_slice(c0 + kAltCS);
+            f32x4 av[kAltCS / 4], p[kAltCS / 4];
+#pragma unroll
+            for (int c = 0; c < kAltCS / 4; ++c) {
+                av[c] = valid ? *reinterpret_cast<const f32x4*>(f1q + c0 + 4 * c) : f32x4{0.f, 0.f, 0.f, 0.f};
+                p[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                // the LDS address is formed here, from an index the compiler cannot see through: hoisted out of the slice loop, the
+                // points' byte addresses (two forms each) would double the registers the points hold
+                int o = off[j];
+                asm volatile("" : "+v"(o));
+#pragma unroll
+                for (int c = 0; c < kAltCS / 4; ++c) p[c] += gl[j] * lds4[c * kAltAccPitch + o];
+                __builtin_amdgcn_sched_barrier(0);   // keep the reads of later points behind this one's: registers again
+            }
+            add_f1(p, c0);
+            __syncthreads();   // the partial sums have been read: the buffer becomes the accumulator of dF2's slice
+            for (int i = tid; i < kLds4; i += kAltThreads) lds4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < NP; ++j) {
+                int o = off[j];
+                asm volatile("" : "+v"(o));
+#pragma unroll
+                for (int c = 0; c < kAltCS; ++c) atomicAdd(&lds[c * kAltAccPitch + o], gl[j] * av[c >> 2][c & 3]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();
+            // flush: consecutive lanes -> consecutive floats of a footprint row (pixel-major, 16 channels each)
+            float* dst = g2b + (long)(c0 / kAltCS) * slice_stride;
+            int py = tid / rowlen, e = tid - py * rowlen;
+            while (py < fh) {
+                const float v = lds[(e & (kAltCS - 1)) * kAltAccPitch + py * F + (e >> 4)];
+                if (v != 0.f) atomicAdd(dst + ((long)(mny + py) * w + mnx) * kAltCS + e, v);
+                e += kAltThreads;
+                while (e >= rowlen) {
+                    e -= rowlen;
+                    ++py;
+                }
+            }
+        }
+    } else {
+        for (int c0 = 0; c0 < a.Cp; c0 += kAltCS) {
+            f32x4 av[kAltCS / 4], p[kAltCS / 4];
+#pragma unroll
+            for (int c = 0; c < kAltCS / 4; ++c) {
+                av[c] = valid ? *reinterpret_cast<const f32x4*>(f1q + c0 + 4 * c) : f32x4{0.f, 0.f, 0.f, 0.f};
+                p[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            float* dst = g2b + (long)(c0 / kAltCS) * slice_stride;
+#pragma unroll 1
+            for (int k = wv; k < S * S; k += kAltThreads / kAltTQ) {   // rolled: this path is bound by its atomics
+                const int col = k % S, row = k / S, px = x0 + col, py = y0 + row;
+                if (!(valid && px >= 0 && px < w && py >= 0 && py < h)) continue;
+                const float g = point_grad(row, col);
+                const long pix = (long)py * w + px;
+                const f32x4* src = reinterpret_cast<const f32x4*>(f2b + pix * a.Cp + c0);
+#pragma unroll
+                for (int c = 0; c < kAltCS / 4; ++c) p[c] += g * src[c];
+#pragma unroll
+                for (int c = 0; c < kAltCS; ++c) atomicAdd(dst + pix * kAltCS + c, g * av[c >> 2][c & 3]);
+            }
+            add_f1(p, c0);
+        }
+    }
+}
+
+template <int R>
+int launch_alt_lookup_bwd(AltArgs a, AltGradArgs ga, hipStream_t stream) {
+    void* args[] = {&a, &ga};
+    return launch<corr_alt_lookup_bwd_kernel<R>>(a.nblocks, kAltThreads, 0, stream, "alo_corr_alt_lookup", args);
+}
+
 inline size_t alt_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int alt_cpad(int C) { return (C + kAltCS - 1) / kAltCS * kAltCS; }
 
@@ -254,32 +484,48 @@ int alt_check_sizes(int B, int C, int H, int W, int num_levels, const char* what
 
 using namespace alo;
 
+namespace {
+// num_levels as the entry points take it: the level count in the low byte, ALO_CORR_ALT_GRAD above it
+inline bool alt_stray_bits(int num_levels) { return num_levels > 0 && (num_levels & ~(0xff | ALO_CORR_ALT_GRAD)) != 0; }
+inline bool alt_grad_flag(int num_levels) { return num_levels > 0 && (num_levels & ALO_CORR_ALT_GRAD) != 0; }
+}  // namespace
+
 extern "C" size_t alo_corr_alt_workspace_bytes(int B, int C, int H, int W, int num_levels) {
+    if (alt_stray_bits(num_levels)) return 0;
+    const bool grad = alt_grad_flag(num_levels);
+    if (grad) num_levels &= 0xff;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_levels < 1 || num_levels > kAltMaxLevels || B > 65535 || C > 65536 ||
         (long)H * W > (1L << 26))
         return 0;
     const size_t cp = (size_t)alt_cpad(C);
-    size_t total = alt_align256((size_t)B * H * W * cp * sizeof(float));
+    const size_t plane = alt_align256((size_t)B * H * W * cp * sizeof(float));
+    size_t total = plane;
     for (int l = 0; l < num_levels; ++l) {
         int h, w;
         alo_corr_level_shape(H, W, l, &h, &w);
         total += alt_align256((size_t)B * h * w * cp * sizeof(float));
     }
-    return total;
+    // the gradient region: one grad_fmap1 plane per level, then every level's gradient (the sizes of the prepared parts)
+    return grad ? total + (size_t)num_levels * plane + (total - plane) : total;
 }
 
 namespace {
-// level pointers inside a prepared workspace
-void alt_layout(void* ws, int B, int C, int H, int W, int num_levels, float** f1, float** f2) {
+// level pointers inside a prepared workspace; with g1 / g2 also those of the gradient region behind it
+void alt_layout(void* ws, int B, int C, int H, int W, int num_levels, float** f1, float** f2, float** g1 = nullptr,
+                float** g2 = nullptr) {
     const size_t cp = (size_t)alt_cpad(C);
+    const size_t plane = alt_align256((size_t)B * H * W * cp * sizeof(float));
     unsigned char* p = static_cast<unsigned char*>(ws);
     *f1 = reinterpret_cast<float*>(p);
-    p += alt_align256((size_t)B * H * W * cp * sizeof(float));
-    for (int l = 0; l < num_levels; ++l) {
-        int h, w;
-        alo_corr_level_shape(H, W, l, &h, &w);
-        f2[l] = reinterpret_cast<float*>(p);
-        p += alt_align256((size_t)B * h * w * cp * sizeof(float));
+    p += plane;
+    for (int pass = 0; pass < (g1 ? 2 : 1); ++pass) {
+        for (int l = 0; pass == 1 && l < num_levels; ++l, p += plane) g1[l] = reinterpret_cast<float*>(p);
+        for (int l = 0; l < num_levels; ++l) {
+            int h, w;
+            alo_corr_level_shape(H, W, l, &h, &w);
+            (pass == 0 ? f2 : g2)[l] = reinterpret_cast<float*>(p);
+            p += alt_align256((size_t)B * h * w * cp * sizeof(float));
+        }
     }
 }
 }  // namespace
@@ -316,15 +562,24 @@ extern "C" int alo_corr_alt_lookup(const void* workspace, size_t workspace_bytes
                                    int H, int W, int radius, int num_levels, void* stream_) {
     const char* what = "alo_corr_alt_lookup";
     ALO_REQUIRE(workspace && coords && out, ALO_ERR_INVALID_ARGUMENT, "%s: null pointer argument", what);
+    ALO_REQUIRE(!alt_stray_bits(num_levels), ALO_ERR_UNSUPPORTED,
+                "%s: num_levels 0x%x has bits above the level count other than ALO_CORR_ALT_GRAD (0x%x)", what, (unsigned)num_levels,
+                (unsigned)ALO_CORR_ALT_GRAD);
+    const bool grad = alt_grad_flag(num_levels);
+    const int flag = grad ? ALO_CORR_ALT_GRAD : 0;
+    if (grad) num_levels &= 0xff;
     if (int rc = alt_check_sizes(B, C, H, W, num_levels, what)) return rc;
     ALO_REQUIRE(radius >= 0 && radius <= 7, ALO_ERR_UNSUPPORTED, "%s: radius must be in [0,7], got %d", what, radius);
-    const size_t need = alo_corr_alt_workspace_bytes(B, C, H, W, num_levels);
+    const size_t need = alo_corr_alt_workspace_bytes(B, C, H, W, num_levels | flag);
     ALO_REQUIRE(workspace_bytes >= need && aligned16(workspace), ALO_ERR_INVALID_ARGUMENT,
                 "%s: a 16-byte aligned workspace of %zu bytes is required, %zu given", what, need, workspace_bytes);
     AltArgs a;
     float* f1 = nullptr;
     float* f2[kAltMaxLevels];
-    alt_layout(const_cast<void*>(workspace), B, C, H, W, num_levels, &f1, f2);
+    AltGradArgs ga;
+    alt_layout(const_cast<void*>(workspace), B, C, H, W, num_levels, &f1, f2, grad ? ga.g1 : nullptr, grad ? ga.g2 : nullptr);
+    for (int l = num_levels; grad && l < kAltMaxLevels; ++l) ga.g1[l] = ga.g2[l] = nullptr;
+    ga.B = B;
     a.f1 = f1;
     for (int l = 0; l < kAltMaxLevels; ++l) {
         a.f2[l] = l < num_levels ? f2[l] : nullptr;
@@ -344,6 +599,18 @@ extern "C" int alo_corr_alt_lookup(const void* workspace, size_t workspace_bytes
     a.nblocks = (unsigned)nblocks;
     a.scale = 1.0f / sqrtf((float)C);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (grad) {   // `out` is grad_out (read); the gradient region of the workspace is added to
+        switch (radius) {
+            case 0: return launch_alt_lookup_bwd<0>(a, ga, stream);
+            case 1: return launch_alt_lookup_bwd<1>(a, ga, stream);
+            case 2: return launch_alt_lookup_bwd<2>(a, ga, stream);
+            case 3: return launch_alt_lookup_bwd<3>(a, ga, stream);
+            case 4: return launch_alt_lookup_bwd<4>(a, ga, stream);
+            case 5: return launch_alt_lookup_bwd<5>(a, ga, stream);
+            case 6: return launch_alt_lookup_bwd<6>(a, ga, stream);
+            default: return launch_alt_lookup_bwd<7>(a, ga, stream);
+        }
+    }
     switch (radius) {
         case 0: return launch_alt_lookup<0>(a, stream);
         case 1: return launch_alt_lookup<1>(a, stream);

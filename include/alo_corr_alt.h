@@ -25,8 +25,22 @@
 extern "C" {
 #endif
 
+/* Flag, OR-ed into `num_levels` of alo_corr_alt_workspace_bytes and alo_corr_alt_lookup (the level count is the low byte): the
+ * workspace carries a gradient region, and the lookup is the ADJOINT of a lookup with respect to both feature maps (below).  Any
+ * other bit above the low byte is refused (ALO_ERR_UNSUPPORTED by the lookup, 0 bytes by the size query). */
+#define ALO_CORR_ALT_GRAD 0x100
+
 /* Bytes of the caller-owned workspace that alo_corr_alt_prepare fills and alo_corr_alt_lookup reads: fmap1 and every level of
- * fmap2 in channels-last layout, channels zero-padded to a multiple of 16.  0 when the sizes are outside the limits above. */
+ * fmap2 in channels-last layout, channels zero-padded to a multiple of 16 (Cp), every part rounded up to 256 bytes.  0 when the
+ * sizes are outside the limits above.
+ *
+ * With num_levels | ALO_CORR_ALT_GRAD: those prepared parts PLUS the gradient region behind them, in this order, every part
+ * rounded up to 256 bytes, all float32:
+ *   num_levels planes of grad_fmap1, plane l = the contribution of level l: (B, H*W, Cp) channels-last, as the prepared fmap1;
+ *                grad_fmap1 is the sum of the planes
+ *   then for l = 0 .. num_levels-1 the gradient of fmap2's level l, SLICE-MAJOR: (Cp/16, B, h_l*w_l, 16); element
+ *                [s][b][p][c] belongs to channel 16 s + c of pixel p (the bytes of the prepared level l, in another order)
+ * Channels C..Cp-1 of the region stay as the caller left them plus zero. */
 size_t alo_corr_alt_workspace_bytes(int B, int C, int H, int W, int num_levels);
 
 /*
@@ -47,6 +61,15 @@ int alo_corr_alt_prepare(const float* fmap1, const float* const* fmap2_levels, v
  *   out        (B, num_levels * (2r+1)^2, H, W) float32, fully overwritten.  Channel l*(2r+1)^2 + i*(2r+1) + j is the bilinear
  *              sample at (x/2^l + i - r, y/2^l + j - r) of <fmap1[b,:,query], fmap2_l[b,:,.]> / sqrt(C): the FIRST window
  *              axis offsets x (the layout of alo_corr_lookup)
+ *
+ * With num_levels | ALO_CORR_ALT_GRAD the call is the adjoint of that lookup with respect to fmap1 and every level of fmap2:
+ *   workspace  of the FLAGGED size.  The prepared part is read.  The gradient region is ADDED TO: the call WRITES THROUGH THIS
+ *              `const` POINTER.  The caller zeroes the region before the first of the lookups whose gradients are to be summed;
+ *              calls that share a workspace must be ordered (one stream)
+ *   coords     as above.  A query that reads as an all-zero window adds nothing
+ *   out        is READ: grad_out, (B, num_levels * (2r+1)^2, H, W) float32
+ * The checks are the unflagged call's, in its order, with the flagged workspace size.  grad_fmap1's planes are added to with plain
+ * loads and stores (bitwise reproducible); the levels' gradients with float atomics, so their last bits depend on the run.
  */
 int alo_corr_alt_lookup(const void* workspace, size_t workspace_bytes, const float* coords, float* out, int B, int C, int H,
                         int W, int radius, int num_levels, void* stream);

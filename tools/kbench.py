@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel-level micro-benchmarks of the hot path at BASELINE.json sizes (HIP events on the launch stream).
 
-    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup,alt_corr_lookup] [--reps 20] [--dtype f32|bf16|f16]
+    python tools/kbench.py [--which msda_enc,msda_dec,msda_bwd,corr_build,corr_lookup,alt_corr_lookup,alt_corr_lookup_bwd] [--reps 20] [--dtype f32|bf16|f16]
 
 Prints one JSON object per kernel: average launch time, algorithmic bytes / flops (SURVEY.md section 8d formulas),
 achieved GB/s or TFLOP/s.  Tuning knobs are environment variables of the library (ALO_MSDA_FWD_WAVES, ALO_MSDA_ITERS).
@@ -318,6 +318,84 @@ def bench_alt_corr_lookup(B, reps, H=90, W=160, C=256, r=4, L=4):
     return out
 
 
+def alt_direct_share(coords, L, r, budget=768):
+    """Share of the (8x8 tile, level) workgroups of csrc/corr_alt.hip whose footprint is over the LDS budget (the direct path): the
+    kernel's own rule, evaluated on the host."""
+    B, _, H, W = coords.shape
+    pad = lambda t, v: torch.nn.functional.pad(t, (0, -W % 8, 0, -H % 8), value=v)   # noqa: E731
+    over = total = 0
+    for lvl in range(L):
+        h, w = H >> lvl, W >> lvl
+        c = coords / 2 ** lvl
+        valid = (c.abs() < 1e6).all(1)
+        x0, y0 = torch.floor(c[:, 0]).int() - r, torch.floor(c[:, 1]).int() - r
+        xlo, xhi, ylo, yhi = x0.clamp(min=0), (x0 + 2 * r + 1).clamp(max=w - 1), y0.clamp(min=0), (y0 + 2 * r + 1).clamp(max=h - 1)
+        touch = valid & (xlo <= xhi) & (ylo <= yhi)
+        big = 1 << 30
+        tiles = lambda t, v, fn: fn(fn(pad(torch.where(touch, t, torch.full_like(t, v)), v).unfold(1, 8, 8).unfold(2, 8, 8), -1)[0], -1)[0]  # noqa: E731
+        mnx, mxx, mny, mxy = tiles(xlo, big, torch.min), tiles(xhi, -big, torch.max), tiles(ylo, big, torch.min), tiles(yhi, -big, torch.max)
+        fw, fh = mxx - mnx + 1, mxy - mny + 1
+        pitch = torch.where(fw <= 8, torch.full_like(fw, 8), ((fw - 9) // 16 + 1) * 16 + 8)
+        staged = (fh * pitch <= budget) | (fh * fw <= budget)
+        live = mnx <= mxx
+        over += int((live & ~staged).sum())
+        total += int(live.sum())
+    return over / max(total, 1)
+
+
+def bench_alt_corr_lookup_bwd(B, reps, H=90, W=160, C=256, r=4, L=4):
+    """The adjoint of AlternateCorrBlock's lookup (corr_alt_lookup_bwd_kernel) at configs[2] size on the smooth and the random
+    coordinate set of alt_corr_lookup, next to the forward on the same inputs, the share of workgroups on the direct path, and the
+    backward of one ``lookup_alt_torch`` lookup (stock ops under autograd) at the largest batch <= B where that fits."""
+    from alonet.raft.corr import AlternateCorrBlock, _alt_pyramid, lookup_alt_torch
+
+    f1, f2 = corr_inputs(B, C, H, W)
+    levels = [p[1] for p in _alt_pyramid(f1, f2, L)[:L]]
+    ws = alo_hip.corr_alt_prepare(f1, levels, grad=True)
+    alo_hip.corr_alt_grad_views(ws, (B, C, H, W), L)[0].zero_()
+    ys, xs = torch.meshgrid(torch.arange(H, device=DEV), torch.arange(W, device=DEV), indexing="ij")
+    flow = torch.stack([3 * torch.sin(ys / 9.0) + 2 * torch.cos(xs / 13.0), 2 * torch.cos(xs / 11.0) - 1.5 * torch.sin(ys / 7.0)])
+    gen = torch.Generator(device=DEV).manual_seed(1)
+    sets = {"smooth": torch.stack([xs, ys]).float()[None].repeat(B, 1, 1, 1) + flow[None],
+            "random": torch.stack([torch.rand(B, H, W, generator=gen, device=DEV) * W,
+                                   torch.rand(B, H, W, generator=gen, device=DEV) * H], 1)}
+    gout = torch.randn(B, L * (2 * r + 1) ** 2, H, W, device=DEV)
+    flops = 4.0 * B * H * W * L * (2 * r + 2) ** 2 * C
+    out = []
+    for name, coords in sets.items():
+        share = alt_direct_share(coords, L, r)
+        n = reps if share < 0.5 else max(2, reps // 10)   # the direct path is bound by scattered atomics: few launches are enough
+        fwd = time_launches(lambda: alo_hip.corr_alt_lookup(ws, coords, C, L, r), reps)
+        bwd = time_launches(lambda: alo_hip.corr_alt_lookup_backward(ws, coords, gout, C, L, r), n, warmup=2)
+        out.append(dict(kernel="alt_corr_lookup_bwd", coords=name, B=B, H=H, W=W, C=C, radius=r, levels=L, ms=bwd * 1e3,
+                        forward_ms=fwd * 1e3, direct_share=share, alg_flops=flops, GFLOPs=flops / bwd / 1e9))
+    for b in (B, B // 2, 1):   # the stock-op route keeps a (b, C, HW, 81) tensor per level for its backward
+        if b < 1:
+            continue
+        try:
+            a1, a2 = f1[:b].clone().requires_grad_(True), f2[:b].clone().requires_grad_(True)
+            torch.cuda.reset_peak_memory_stats()
+            ts = []
+            for _ in range(3):
+                pyr = _alt_pyramid(a1, a2, L)
+                loss = (lookup_alt_torch(pyr, sets["smooth"][:b], L, r) * gout[:b]).sum()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                torch.autograd.grad(loss, (a1, a2), retain_graph=False)
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            out.append(dict(kernel="alt_corr_lookup_bwd_torch", coords="smooth", B=b, H=H, W=W, C=C, radius=r, levels=L, ms=min(ts),
+                            ms_per_pair=min(ts) / b, hip_ms_per_pair=out[0]["ms"] / B, ratio_per_pair=(min(ts) / b) / (out[0]["ms"] / B),
+                            max_memory_allocated_GB=torch.cuda.max_memory_allocated() / 1e9))
+            break
+        except torch.OutOfMemoryError:
+            del a1, a2
+            torch.cuda.empty_cache()
+    return out
+
+
 def bench_corr_lookup_bwd(B, reps, H=90, W=160):
     """The lookup's adjoint: read the 324 output gradients, read-modify-write the 4 x 10 x 10 footprints (the gradient maps)."""
     shapes = alo_hip.corr_level_shapes(H, W, 4)
@@ -443,6 +521,8 @@ def main():
             res = [bench_corr_lookup(a.B, a.reps)]
         elif w == "alt_corr_lookup":
             res = bench_alt_corr_lookup(a.B, a.reps)
+        elif w == "alt_corr_lookup_bwd":
+            res = bench_alt_corr_lookup_bwd(a.B, a.reps)
         elif w == "residual_gemms":   # conv3 of the four ResNet stages with and without the identity
             res = bench_residual_gemms(max(a.reps, 50))
         elif w == "epilogues":
