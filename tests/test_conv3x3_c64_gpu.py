@@ -1,6 +1,6 @@
 """conv3x3_c64_kernel (conv.hip): the 64 -> 64 stride-1 convolution with its weights resident in registers.
 
-It replaces conv3x3_kernel<1, true> for that one shape class and keeps its summation: the same K split over two halves, each half
+It replaces conv3x3_kernel<PlanS1<1>, true> for that one shape class and keeps its summation: the same K split over two halves, each half
 accumulated in the same order, half 0 + half 1, + bias, ReLU, one rounding.  So the outputs must be the streaming kernel's bit for
 bit; ALO_CONV3X3_C64=stream (read on every call) routes the shape back to the streaming kernel for the comparison.
 """

@@ -1,4 +1,4 @@
-"""The dilated 3x3 convolution (dilation 2, padding 2, stride 1: ALO_CONV_DILATION_2 of alo_conv3x3_nhwc; conv3x3_d2_kernel of
+"""The dilated 3x3 convolution (dilation 2, padding 2, stride 1: ALO_CONV_DILATION_2 of alo_conv3x3_nhwc; conv3x3_kernel<PlanS1<2>, ..> of
 aloception-oss_amd/csrc/conv.hip in bf16, conv3x3_d2_f32_kernel of conv_f32.hip in fp32) against F.conv2d(..., 1, 2, 2) in fp64 on the
 kernel's own operands, every output element within the bounds of conv_dilated_ref.py (the undilated kernels' bounds over the dilated
 window); then the gates, the routes of a DC5 backbone and a DC5 Deformable-DETR.

@@ -1,7 +1,7 @@
-"""conv3x3_pipe_kernel (conv.hip): the stride-1 3x3 convolution of 128 and more output channels with its LDS reads and weight requests
+"""conv3x3_pipe_kernel<PipeS1<..>> (conv.hip): the stride-1 3x3 convolution of 128 and more output channels with its LDS reads and weight requests
 issued ahead of the MFMAs that use them.
 
-It replaces conv3x3_kernel<1, false> for bf16, stride 1, no dilation, Cout >= 128, no split-K, and keeps that kernel's arithmetic: every
+It replaces conv3x3_kernel<PlanS1<1>, false> for bf16, stride 1, no dilation, Cout >= 128, no split-K, and keeps that kernel's arithmetic: every
 accumulator starts at zero and takes one v_mfma_f32_32x32x16_bf16 per k-step in the order chunk, tap, channel; out-of-image taps are
 zeroed by selection; bias after the sum, ReLU that keeps NaN, one rounding.  So the outputs must be the streaming kernel's bit for bit;
 ALO_CONV3X3_PIPE=off (read on every call) routes the shapes back to the streaming kernel for the comparison.  Cout >= 256 runs tiles of

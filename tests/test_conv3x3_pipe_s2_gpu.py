@@ -1,6 +1,6 @@
-"""conv3x3_pipe_s2_kernel (conv.hip): the stride-2 3x3 convolution of 128 and more output channels on the pipelined loop.
+"""conv3x3_pipe_kernel<PipeS2<..>> (conv.hip): the stride-2 3x3 convolution of 128 and more output channels on the pipelined loop.
 
-It replaces conv3x3_kernel<2, false> for bf16, stride 2, no dilation, Cout >= 128, no split-K, and keeps that kernel's arithmetic and
+It replaces conv3x3_kernel<PlanS2, false> for bf16, stride 2, no dilation, Cout >= 128, no split-K, and keeps that kernel's arithmetic and
 its halo (per tap row a run of odd-column and a run of even-column input pixels, clamped into the image, out-of-image taps zeroed by
 selection), so the outputs must be the streaming kernel's bit for bit.  ALO_CONV3X3_PIPE=stride1 (read on every call) keeps stride 2 on
 the streaming kernel and stride 1 on the pipelined one, "off" sends both back.  Cout >= 256 runs tiles of 96 output pixels x 256

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Compare the device code of two builds of the library, kernel by kernel.
+r"""Compare the device code of two builds of the library, kernel by kernel.
 
-    tools/isa_diff.py TREE_A TREE_B [--out DIR] [--jobs N] [--only a.hip,b.hip] [--lines N]
+    tools/isa_diff.py TREE_A TREE_B [--out DIR] [--jobs N] [--only a.hip,b.hip] [--lines N] [--rename 'OLD=NEW' ...]
 
 Each TREE is a checkout (or any directory that holds aloception-oss_amd/csrc and include/).  Every .hip file of both trees is
 compiled to gfx950 assembly with the command its own Makefile would use for the object file (`make -n`, so per-file flags such
@@ -12,6 +12,11 @@ as msda.hip's -fno-slp-vectorize are kept), `-c` replaced by `--offload-device-o
   * the instruction count and the count per opcode,
   * the instruction sequence in order, register numbers and a branch target's function ordinal (the N of `.LBBN_k`, which counts
     the functions of the file) ignored: class (a) identical, class (b) not.
+
+A kernel that tree B renamed is paired by --rename OLD=NEW (repeatable): OLD is a regular expression, rewritten to NEW (re.sub)
+in the short names of tree A's kernels, the ones the table prints (c++filt's spelling: `> >`), so groups carry template arguments
+over, e.g. 'conv3x3_d2_kernel<([a-z]+)>=conv3x3_kernel<PlanS1<2>, \1>'.  The pair is then classed like any other and listed
+as "old -> new".
 
 Exit status 0: the same kernels on both sides, equal figures and equal counts everywhere (class (b) is reported, not an error).
 Exit status 1: anything else.  The assembly is kept under --out (default: a temporary directory) as A/<file>.s and B/<file>.s.
@@ -112,7 +117,12 @@ def main():
     ap.add_argument("--jobs", type=int, default=min(16, len(os.sched_getaffinity(0))))
     ap.add_argument("--only", default=None, help="comma-separated .hip files instead of all")
     ap.add_argument("--lines", type=int, default=12, help="differing lines shown per class (b) kernel")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="pair tree A's kernel OLD (a regular expression over the short name) with tree B's kernel NEW; repeatable")
     args = ap.parse_args()
+    renames = [r.split("=", 1) for r in args.rename]
+    if any(len(r) != 2 for r in renames):
+        ap.error("--rename takes OLD=NEW")
     out = args.out or tempfile.mkdtemp(prefix="isa_diff_")
     trees = {"A": os.path.abspath(args.tree_a), "B": os.path.abspath(args.tree_b)}
     srcs = {s: sorted(f for f in os.listdir(os.path.join(t, CSRC)) if f.endswith(".hip")) for s, t in trees.items()}
@@ -130,8 +140,23 @@ def main():
             k["file"] = src
             kernels[side][name] = k
 
+    # from here on a kernel goes by its short name; tree A's are rewritten by --rename first, so a renamed kernel meets its successor
+    short = demangle(sorted(set(kernels["A"]) | set(kernels["B"])))
+    pretty, keyed = {}, {"A": {}, "B": {}}
+    for side in ("A", "B"):
+        for mangled, k in kernels[side].items():
+            name = short[mangled]
+            if side == "A":
+                for old, new in renames:
+                    name = re.sub(old, new, name)
+            if name in keyed[side]:
+                sys.exit(f"isa_diff: two kernels of tree {side} are called {name} (after --rename)")
+            keyed[side][name] = k
+            if name != short[mangled]:
+                pretty[name] = f"{short[mangled]} -> {name}"
+    kernels = keyed
     names = sorted(set(kernels["A"]) | set(kernels["B"]))
-    pretty = demangle(names)
+    pretty = {n: pretty.get(n, n) for n in names}
     bad, same, reordered = [], 0, []
     print(f"{'file':18} {'instr':>7} {'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'scratch':>7} {'lds':>7}  class  kernel")
     for n in names:
